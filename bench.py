@@ -23,12 +23,23 @@ configs[2]) and aggregated proofs/sec (configs[0] / configs[3]), one process per
     (gkr_sumcheck_mle_sharded_dev); a step = --split-batch sumchecks; strong scaling.
 
 field-ops: 5 (2^n - 1) per plain sumcheck, 25 (2^{2k} - 1) per layer sumcheck; algorithmic bytes 128 * 2^n
-(SURVEY.md section 8d).  The JSON line also carries
+(SURVEY.md section 8d).
+
+A plain run of --mode mle sets up, warms up, times the K steps and prints the headline line (the contract keys, the
+step times); nothing else.  --full adds the rest: the timed steps with the per-kernel HIP events,
+the check of the timed outputs, and every other leg (batch-1 latency, n16, configs[0] / [3] / [4], the wide layers,
+the split legs on N > 1, large_r1cs, multi_device).  With --full the JSON line also carries
   roofline       the dominant kernel (k_mle_multifold_mfma, the fold pass) timed with HIP events on the library's
                  stream during the timed steps (profile level 2: only the bandwidth-bound kernels carry events)
   cpu_baseline   the plain-C oracle (oracle/c), one sumcheck per host core, on a bounded sample of the same
                  workload; rank 0, N = 1 only; plus cpu_ref_algo (the reference's term-list algorithm restated,
                  largest size under its time cap) and cpu_pipeline (the oracle proving the demo circuit)
+The other modes run as they always did; --full changes nothing there.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes the arrays the timed path returned in its last step as
+DIR/<name>.npy, float64 (see dump_outputs): --mode mle and mle-split coeffs / lengths / challenges (the C ABI's
+C, L, R), layer-split the same for the layer sumcheck, proofs c<j>_<field> for sub-circuit j and every field of
+gkr_proof_buf.  The inputs are seeded: the same arguments give the same arrays.
 """
 
 import argparse
@@ -237,6 +248,34 @@ def timed_steps(world, ctx, step, warmup, steps):
     return world.max_over_ranks(elapsed), each
 
 
+DUMP_LIMIT = 60 * 10**6   # bytes of all the arrays of one --dump-outputs together (under 64 MB with the .npy headers)
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: {name: array} of the last timed step -> directory/<name>.npy, float64.  A field element is four 64-bit
+    limbs, which float64 cannot hold: an array of 64-bit integers is written as its 32-bit words (low word first, so its last
+    axis doubles), every word exact in float64.  Should the arrays exceed DUMP_LIMIT, every array keeps the same evenly spaced
+    entries of its first axis (the sumcheck or proof index, the same length in all of them) and rows.npy lists which."""
+    import numpy as np
+    out = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype.kind in "ui" and a.dtype.itemsize == 8:
+            a = a.view(np.uint32)
+        out[name] = a.astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT:
+        rows = {a.shape[0] for a in out.values()}
+        assert len(rows) == 1, "the arrays to sample do not share their first axis"
+        rows = rows.pop()
+        keep = np.unique(np.linspace(0, rows - 1, max(1, rows * DUMP_LIMIT // total - 1)).round().astype(np.int64))
+        out = {name: a[keep] for name, a in out.items()}
+        out["rows"] = keep.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 # ------------------------------------------------------------------------------------------------ what was timed is checked
 
 def _sha(*arrays):
@@ -356,33 +395,22 @@ def run_mle(args, world):
     for b in range(batch):
         ctx.fill_table(ctypes.c_void_p(tables.value + b * count * 32), count, synth.bench_table_seed(world.rank, b))
     ctx.synchronize()
-    ceilings = ctx.ceilings() if (world.rank == 0 and not args.no_extras) else None   # the box's own copy / product rates (~0.1 s)
+    # the box's own copy / product rates (~0.1 s)
+    ceilings = ctx.ceilings() if (args.full and world.rank == 0 and not args.no_extras) else None
     outputs = [None]   # the proof arrays of the previous step are reused (no fresh pages inside the timed call)
 
     def step():
         outputs[0] = ctx.sumcheck_mle_batch_device(tables, n, batch, out=outputs[0])
 
-    ctx.profile(0 if args.no_profile else 2)   # on during warm-up too: the event pool is created lazily
+    ctx.profile(2 if args.full and not args.no_profile else 0)   # on during warm-up too: the event pool is created lazily
     elapsed, each = timed_steps(world, ctx, step, args.warmup, args.steps)
     ctx.profile(False)
+    if args.dump_outputs and world.rank == 0:
+        dump_outputs(args.dump_outputs, dict(zip(("coeffs", "lengths", "challenges"), outputs[0])))
     ops_per_sumcheck = 5 * (count - 1)
     value = ops_per_sumcheck * batch * args.steps * world.size / elapsed
-    verified, verified_ok = ({"skipped": "--no-verify"}, True) if args.no_verify else verify_mle_outputs(ctx, tables, n, batch, outputs[0], world.rank)
-    ranks_failed = world.max_over_ranks(0.0 if verified_ok else 1.0)
-    threads_per_rank = [int(x) for x in world.per_rank(transcript_threads())]
-    step_ms_per_rank = [round(x, 3) for x in world.per_rank(sum(each) / max(1, len(each)) * 1e3)]
-
-    names = ["mle_multifold", "mle_multifold_late", "mle_sub_sums", "mle_sub_reduce", "mle_pass_small", "mle_fold_plan",   # multi-round passes (default)
-             "mle_fold_sum", "mle_sum_first", "mle_round_reduce", "mle_fold_sum_small", "mle_round_hash"]  # per-round paths
-    prof = {k: ctx.profile_get(k) for k in names}
     line = None
     if world.rank == 0:
-        dom_name = "mle_multifold" if prof["mle_multifold"]["launches"] else "mle_fold_sum"
-        dom = prof[dom_name]
-        achieved = dom["bytes"] / (dom["total_ms"] * 1e-3) / 1e9 if dom["total_ms"] > 0 else 0.0
-        kernel_ms_total = sum(v["total_ms"] for v in prof.values())
-        scheduled_bytes = sum(v["bytes"] for v in prof.values())
-        sumchecks = batch * args.steps
         line = {
             "metric": "BN254-Fr sumcheck field-ops/sec @ 2^20 vars",
             "value": value, "unit": "field-ops/s", "n_gpus": world.size, "steps": args.steps, "warmup": args.warmup,
@@ -395,7 +423,29 @@ def run_mle(args, world):
                        "parallelism": "independent sumchecks per rank, no collective"},
             "sumchecks_per_sec": batch * args.steps * world.size / elapsed,
             "tables_device_address": hex(tables.value),
-            "step_ms_each": [round(x * 1e3, 3) for x in each],
+            "step_ms_each": [round(x * 1e3, 3) for x in each]}
+    if not args.full:
+        ctx.free(raw_tables)
+        ctx.close()
+        if line:
+            emit(line)
+        return
+    verified, verified_ok = ({"skipped": "--no-verify"}, True) if args.no_verify else verify_mle_outputs(ctx, tables, n, batch, outputs[0], world.rank)
+    ranks_failed = world.max_over_ranks(0.0 if verified_ok else 1.0)
+    threads_per_rank = [int(x) for x in world.per_rank(transcript_threads())]
+    step_ms_per_rank = [round(x, 3) for x in world.per_rank(sum(each) / max(1, len(each)) * 1e3)]
+
+    names = ["mle_multifold", "mle_multifold_late", "mle_sub_sums", "mle_sub_reduce", "mle_pass_small", "mle_fold_plan",   # multi-round passes (default)
+             "mle_fold_sum", "mle_sum_first", "mle_round_reduce", "mle_fold_sum_small", "mle_round_hash"]  # per-round paths
+    prof = {k: ctx.profile_get(k) for k in names}
+    if world.rank == 0:
+        dom_name = "mle_multifold" if prof["mle_multifold"]["launches"] else "mle_fold_sum"
+        dom = prof[dom_name]
+        achieved = dom["bytes"] / (dom["total_ms"] * 1e-3) / 1e9 if dom["total_ms"] > 0 else 0.0
+        kernel_ms_total = sum(v["total_ms"] for v in prof.values())
+        scheduled_bytes = sum(v["bytes"] for v in prof.values())
+        sumchecks = batch * args.steps
+        line.update({
             "host_threads": {"usable_cpus": usable_cpus(), "GKR_HOST_THREADS": os.environ.get("GKR_HOST_THREADS"),
                              "LOCAL_WORLD_SIZE": os.environ.get("LOCAL_WORLD_SIZE"), "cgroup_throttling_in_timed_steps": dict(LAST_THROTTLE),
                              "transcript_threads_per_rank": threads_per_rank, "mean_step_ms_per_rank": step_ms_per_rank},
@@ -425,7 +475,7 @@ def run_mle(args, world):
             # SURVEY 8d's per-round accounting (128 * 2^n bytes per sumcheck) over ALL kernel time of the step: the
             # multi-round schedule moves about half of that, so this figure is NOT a bandwidth and can exceed HBM's
             "survey_accounting_GBps": (128.0 * count * sumchecks) / (kernel_ms_total * 1e-3) / 1e9 if kernel_ms_total else None,
-        }
+        })
         # which of the fold pass's placement-dependent bandwidth modes this process drew: the big launches one by one
         avg_bytes = dom["bytes"] / max(1, dom["launches"])
         big = [(ms, by) for ms, by in ctx.profile_samples("mle_multifold") if by >= 0.99 * avg_bytes]   # the 2^n -> 2^(n-5) launches
@@ -850,6 +900,10 @@ def run_proofs(args, world):
         if inputs is not None:
             step_obj.prove_raw_many(ctx, inputs, threads)
     elapsed, each = timed_steps(world, ctx, step, args.warmup, args.steps)
+    if args.dump_outputs and world.rank == 0 and inputs is not None:
+        from gkr_amd._native import ProofBuf
+        fields = [f for f, _ in ProofBuf._fields_]
+        dump_outputs(args.dump_outputs, {"c%d_%s" % (j, f): a for j, arrs in enumerate(step_obj._prepared["outs"]) for f, a in zip(fields, arrs)})
     # what was timed is checked on every rank: every proof of the last step through the library's verifier (gkr_verify)
     native = native_verify_all(step_obj.circuits, step_obj._prepared["outs"]) if inputs is not None and not args.no_verify else None
     bad_ranks = world.max_over_ranks(1.0 if native is not None and not native["ok"] else 0.0)
@@ -875,7 +929,7 @@ def run_proofs(args, world):
 
 # ------------------------------------------------------------------------------------------------ mode: layer-split
 
-def layer_leg(world, k_i, k, steps, warmup, split, ceilings=None, shape="uniform"):
+def layer_leg(world, k_i, k, steps, warmup, split, ceilings=None, shape="uniform", dump=None):
     """BASELINE configs[4]: ONE GKR layer sumcheck (prove_sumcheck_opt, sumcheck.rs:36-156) with 2^k_i random gates
     over a 2^k-entry next layer, gates and their sorted lists resident in HBM before the timed region, a step = one
     sumcheck (new z, W).  split: the gates are divided over the ranks (two sum-over-ranks exchanges per sumcheck);
@@ -917,6 +971,8 @@ def layer_leg(world, k_i, k, steps, warmup, split, ceilings=None, shape="uniform
     # of the same steps with the events on
     ctx.profile(False)
     elapsed, each = timed_steps(world, ctx, step, warmup, steps)
+    if dump and world.rank == 0:
+        dump_outputs(dump, dict(zip(("coeffs", "lengths", "challenges"), result[0])))
     ctx.profile(1)
     ctx.profile_reset()
     for _ in range(steps):
@@ -1093,7 +1149,7 @@ def collective_info(world, exchange=None, exch_prof=None, steps=1):
     return info
 
 
-def mle_split_leg(world, n, batch, steps, warmup, ceilings=None):
+def mle_split_leg(world, n, batch, steps, warmup, ceilings=None, dump=None):
     """ONE plain sumcheck (prove_sumcheck, sumcheck.rs:158-214) on a table of 2^n points split over the ranks
     (gkr_sumcheck_mle_sharded_dev): rank p holds the entries whose index bits log2 P .. 1 are p, every pass's sub-block
     sums cross the ranks in one all-reduce on the library's stream, the last entries are gathered and every rank ends
@@ -1124,6 +1180,8 @@ def mle_split_leg(world, n, batch, steps, warmup, ceilings=None):
     ctx.profile(1)
     elapsed, each = timed_steps(world, ctx, step, warmup, steps)
     ctx.profile(False)
+    if dump and world.rank == 0:
+        dump_outputs(dump, dict(zip(("coeffs", "lengths", "challenges"), result[0][:3])))
     names = ["mle_multifold", "mle_sub_sums", "mle_sub_reduce", "mle_pass_small", "mle_fold_plan"]
     prof = {k: ctx.profile_get(k) for k in names}
     exch = ctx.profile_get("exchange")
@@ -1163,7 +1221,7 @@ def mle_split_leg(world, n, batch, steps, warmup, ceilings=None):
 
 
 def run_mle_split(args, world):
-    out = mle_split_leg(world, args.n, args.split_batch, args.steps, args.warmup)
+    out = mle_split_leg(world, args.n, args.split_batch, args.steps, args.warmup, dump=args.dump_outputs)
     if world.rank == 0:
         emit(out)
         if out.get("matches_golden_digest") is False or out.get("all_ranks_match") is False:
@@ -1171,7 +1229,7 @@ def run_mle_split(args, world):
 
 
 def run_layer_split(args, world):
-    out = layer_leg(world, args.k_i, args.k, args.steps, args.warmup, split=True)
+    out = layer_leg(world, args.k_i, args.k, args.steps, args.warmup, split=True, dump=args.dump_outputs)
     if world.rank == 0:
         emit(out)
         if out["matches_golden_digest"] is False:
@@ -1465,6 +1523,9 @@ def main():
     ap.add_argument("--batch", type=int, default=1024, help="independent sumchecks per rank per step (32 GiB of tables)")
     ap.add_argument("--transcript", choices=["host", "device"], default="host",
                     help="where MiMC7 runs (host cores between launches, or one GPU lane per sumcheck)")
+    ap.add_argument("--full", action="store_true",
+                    help="mle mode: also the roofline, the check of the timed outputs, the CPU baselines and every other leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's output arrays as DIR/<name>.npy (float64)")
     ap.add_argument("--no-profile", action="store_true", help="skip the per-kernel HIP-event timing")
     ap.add_argument("--no-extras", action="store_true", help="skip the batch-1 latency and the 2^16 leg")
     ap.add_argument("--proofs", type=int, default=64, help="inputs of the demo circuit (configs[3]); 0 = skip in mle mode")

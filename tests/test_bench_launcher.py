@@ -49,6 +49,27 @@ def test_launcher_builds_the_documented_command(monkeypatch):
     assert seen["kw"]["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
 
 
+def test_dump_outputs_are_exact_float64_and_bounded(tmp_path, monkeypatch):
+    """(CPU) bench.dump_outputs: 64-bit limbs go out as 32-bit words in float64 and come back bit for bit; above the limit every
+    array keeps the same evenly spaced rows, and rows.npy says which."""
+    import numpy as np
+    sys.path.insert(0, REPO)
+    import bench
+    rng = np.random.default_rng(7)
+    C = rng.integers(0, 2**64, size=(100, 3, 2, 4), dtype=np.uint64)
+    L = rng.integers(0, 3, size=(100, 3), dtype=np.uint32)
+    bench.dump_outputs(str(tmp_path / "all"), {"coeffs": C, "lengths": L})
+    c, l = np.load(tmp_path / "all" / "coeffs.npy"), np.load(tmp_path / "all" / "lengths.npy")
+    assert c.dtype == l.dtype == np.float64 and c.shape == (100, 3, 2, 8) and not (tmp_path / "all" / "rows.npy").exists()
+    assert np.array_equal(c.astype(np.uint32).view(np.uint64), C) and np.array_equal(l, L)
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 20000)
+    bench.dump_outputs(str(tmp_path / "some"), {"coeffs": C, "lengths": L})
+    c, l, rows = (np.load(tmp_path / "some" / (n + ".npy")) for n in ("coeffs", "lengths", "rows"))
+    keep = rows.astype(np.int64)
+    assert c.nbytes + l.nbytes + rows.nbytes <= 20000 and 1 < len(keep) < 100 and keep[0] == 0 and keep[-1] == 99
+    assert np.array_equal(c.astype(np.uint32).view(np.uint64), C[keep]) and np.array_equal(l, L[keep])
+
+
 def test_the_stdout_line_of_a_full_record_stays_short():
     """(CPU) compact_line on the full records committed under profiles/ (every leg of the default line, N = 1 and the two-rank
     gloo run): under 6 000 bytes, every contract key, roofline / cpu_baseline / verified / legs with their scalar fields --

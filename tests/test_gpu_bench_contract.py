@@ -40,9 +40,9 @@ def _run(*args, env=None, timeout=900):
 
 
 def test_the_drivers_exact_command_gives_a_short_line():
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` -- the driver's command, full sizes, every leg: the line parses, is under
-    6 000 bytes and carries roofline + cpu_baseline + verified + the flat legs summary."""
-    line, full = _run("--gpus", "1", "--steps", "20", "--warmup", "5", timeout=1500)
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --full` -- the headline command with every leg, full sizes: the line parses,
+    is under 6 000 bytes and carries roofline + cpu_baseline + verified + the flat legs summary."""
+    line, full = _run("--gpus", "1", "--steps", "20", "--warmup", "5", "--full", timeout=1500)
     assert line["steps"] == 20 and line["warmup"] == 5 and line["n_gpus"] == 1
     r = line["roofline"]
     for key in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "avg_launch_us", "algorithmic_bytes_per_launch"):
@@ -59,9 +59,33 @@ def test_the_drivers_exact_command_gives_a_short_line():
     assert full["aggregated_proofs"]["multi_device"]["device_ids"] == list(range(full["aggregated_proofs"]["multi_device"]["devices_seen"]))
 
 
+def test_a_plain_run_times_the_headline_and_dumps_its_outputs(tmp_path):
+    """`python bench.py --gpus 1 --steps 20 --warmup 5` without --full: the contract keys and the 20 step times, none of the
+    legs; --dump-outputs writes the last timed step's (C, L, R) as float64 words that rebuild the exact arrays -- the whole
+    batch's digest is the committed one (tests/golden/bench_batch_hashes.json)."""
+    import hashlib
+    import numpy as np
+    from gkr_amd import synth
+    line, d = _run("--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", str(tmp_path))
+    assert line["steps"] == 20 and line["warmup"] == 5 and len(d["step_ms_each"]) == 20
+    assert line["ms_per_step"] > 0 and line["metric"] == "BN254-Fr sumcheck field-ops/sec @ 2^20 vars"
+    assert not {"roofline", "cpu_baseline", "verified", "legs"} & set(line), sorted(line)
+    files = {f.name: np.load(f) for f in tmp_path.iterdir()}
+    assert sorted(files) == ["challenges.npy", "coeffs.npy", "lengths.npy"]
+    assert all(a.dtype == np.float64 for a in files.values()) and sum(f.stat().st_size for f in tmp_path.iterdir()) <= 64 * 10**6
+    C = files["coeffs.npy"].astype(np.uint32).view(np.uint64)
+    L = files["lengths.npy"].astype(np.uint32)
+    R = files["challenges.npy"].astype(np.uint32).view(np.uint64)
+    assert C.shape == (1024, 20, 2, 4) and L.shape == (1024, 20) and R.shape == (1024, 20, 4)
+    h = hashlib.sha256()
+    for a in (C, L, R):
+        h.update(np.ascontiguousarray(a).tobytes())
+    assert h.hexdigest() == synth.bench_batch_digests()["whole_batch_by_rank"]["0"]
+
+
 def test_default_mode_line():
     line, d = _run("--batch", "64", "--steps", "2", "--warmup", "1", "--proofs", "4", "--cpu-seconds", "0.5", "--ref-algo-seconds", "1",
-                   "--layer-k-i", "20", "--layer-k", "10")
+                   "--layer-k-i", "20", "--layer-k", "10", "--full")
     for key in ("roofline", "cpu_baseline", "verified", "legs", "exit"):
         assert key in line, key
     assert line["roofline"]["frac"] == pytest.approx(d["roofline"]["frac"], rel=1e-6) and line["cpu_baseline"]["kind"] == "port"
@@ -99,7 +123,8 @@ def test_gpus_flag_starts_its_own_ranks():
     env = {"GKR_BENCH_BACKEND": "gloo", "GKR_BENCH_DEVICE": "0", "HSA_ENABLE_IPC_MODE_LEGACY": "0"}
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         os.environ.pop(k, None)
-    line, d = _run("--gpus", "2", "--batch", "32", "--steps", "2", "--warmup", "1", "--proofs", "4", "--layer-k-i", "20", "--layer-k", "10", env=env)
+    line, d = _run("--gpus", "2", "--batch", "32", "--steps", "2", "--warmup", "1", "--proofs", "4", "--layer-k-i", "20", "--layer-k", "10", "--full",
+                   env=env)
     assert d["n_gpus"] == 2 and d["collective"]["world_size_seen"] == 2 and d["collective"]["backend"] == "gloo"
     assert d["verified"]["ok"] is True and d["verified"]["all_ranks_ok"] is True
     assert d["layer24_split"]["matches_golden_digest"] is True and d["mle_split"]["matches_golden_digest"] is True
@@ -113,7 +138,7 @@ def test_one_process_over_all_devices_leg():
     """aggregated_proofs.multi_device on the N = 1 line: configs[3] through ONE process and gkr_ctx_create_multi over every
     visible device, the proofs checked against the committed digests.  A failure of the leg fails this test, however many
     devices the box has."""
-    line, d = _run("--batch", "16", "--steps", "1", "--warmup", "1", "--proofs", "4", "--no-extras", "--no-cpu-baseline")
+    line, d = _run("--batch", "16", "--steps", "1", "--warmup", "1", "--proofs", "4", "--no-extras", "--no-cpu-baseline", "--full")
     m = d["aggregated_proofs"]["multi_device"]
     assert "error" not in m, m
     assert m["devices_seen"] >= 1 and m["proofs"] == 48 and m["ms"] > 0 and (m["verified"] is None or m["verified"]["ok"] is True)
@@ -129,7 +154,7 @@ def test_a_failed_split_leg_reaches_the_exit_code():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         os.environ.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--batch", "16", "--steps", "1", "--warmup", "1", "--proofs", "0",
-                          "--layer-k-i", "20", "--layer-k", "10", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900,
+                          "--layer-k-i", "20", "--layer-k", "10", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900,
                          env=dict(os.environ, **env))
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1 and out.returncode != 0, (out.returncode, out.stdout[-500:], out.stderr[-2000:])

@@ -1,7 +1,7 @@
 # same box, fresh process each time: the headline's step time, the fold pass's fraction of peak, where the tables landed and the
 # first-fold launches' rates (min / median / max) -- does a process draw a "mode"?
 for i in $(seq 1 ${1:-6}); do
-  GKR_BENCH_DETAIL=/tmp/hm_$i.json python bench.py --steps 10 --warmup 3 --no-extras --no-cpu-baseline --no-verify --proofs 0 $2 > /dev/null 2>&1
+  GKR_BENCH_DETAIL=/tmp/hm_$i.json python bench.py --steps 10 --warmup 3 --full --no-extras --no-cpu-baseline --no-verify --proofs 0 $2 > /dev/null 2>&1
   python - $i <<'P'
 import json,sys
 d=json.load(open('/tmp/hm_%s.json'%sys.argv[1])); r=d['roofline']; f=r.get('first_fold_pass_GBps',{})

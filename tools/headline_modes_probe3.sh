@@ -1,7 +1,7 @@
 # on whatever box this lands: the headline's fold-pass fraction under the launch-geometry switches -- if the box is in the slow mode
 # (frac ~0.75), does any of them recover the fast one (~0.80)?
 run() {
-  GKR_BENCH_DETAIL=/tmp/hm.json env "$@" python bench.py --steps 10 --warmup 3 --no-extras --no-cpu-baseline --no-verify --proofs 0 > /dev/null 2>&1
+  GKR_BENCH_DETAIL=/tmp/hm.json env "$@" python bench.py --steps 10 --warmup 3 --full --no-extras --no-cpu-baseline --no-verify --proofs 0 > /dev/null 2>&1
   python - "$*" <<'P'
 import json,sys
 d=json.load(open('/tmp/hm.json')); r=d['roofline']; f=r.get('first_fold_pass_GBps',{})
