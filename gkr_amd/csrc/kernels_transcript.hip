@@ -18,18 +18,7 @@
 
 namespace gkr {
 
-// xor-shuffle tree over the eight lanes of a group: every lane ends with the modular sum of the eight values
-__device__ __forceinline__ Fr group_sum(Fr x) {
-#pragma unroll
-    for (int off = 1; off <= 4; off <<= 1) {
-        Fr o;
-#pragma unroll
-        for (int l = 0; l < 8; ++l) o.l[l] = (uint32_t)__shfl_xor((int)x.l[l], off, 64);
-        x = fr_add(x, o);
-    }
-    return x;
-}
-
+// (group_sum: mimc_lanes.h)
 // grid = ceil(count / 8), block = 64.  rec / weights / dep_last / out_*: indexed by sumcheck (the caller passes the
 // pointers of the launch's first sumcheck); round0: global index of the pass's first round, n_out: rounds per sumcheck in
 // the output arrays; final_pass: the pass's last round is the sumcheck's last (length rule of sumcheck.rs:206-207:

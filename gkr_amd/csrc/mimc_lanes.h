@@ -13,8 +13,14 @@
 //   bounds:  operands below 3p give a product below 2.7p (a b / 2^256 + p) and no intermediate reaches 2^256
 //            (4p = 0.756 * 2^256); sums are brought back with conditional subtractions of 2p or p (borrow lookahead).
 // Reference call sites replaced: Mimc7::new(91) rust/src/gkr/sumcheck.rs:45; multi_hash sumcheck.rs:84,129,152
-// (mimc-rs: r = key; for a in arr { r += a + hash(a, r) }).  Checked against mimc7.h's one-lane code on the device
-// (gkr_selftest_lanes_hash) and through the sumcheck parity tests with the device-hashed groups forced on.
+// (mimc-rs: r = key; for a in arr { r += a + hash(a, r) }).  Checked primitive by primitive on the device against big
+// integers and a Python MiMC7 (gkr_devtest_lanes, tests/test_gpu_device_arith.py), through the sumcheck parity tests with the
+// device-hashed groups forced on, and the ballot lookahead below on the CPU (tests/test_lanes_lookahead_model.py).
+//
+// Lookahead: lane j of group g is bit 8g + j of a 64-bit ballot; generated carries (borrows) are shifted up one lane and
+// masked so that none leaves its group, and one 64-bit add ripples them through the lanes that propagate.  The propagate
+// mask is cleared at every group's top lane before that add: a carry that reaches the top lane stops there (it still
+// shows in the result bit of that lane) instead of rippling on into lane 0 of the next group -- another transcript.
 #pragma once
 #include "mimc7.h"
 
@@ -68,7 +74,8 @@ __device__ __forceinline__ uint32_t resolve_carries(uint64_t v, uint32_t j) {
     const uint32_t s = limb + from_below;
     const uint64_t g = __ballot(s < limb), p = __ballot(s == 0xffffffffu);
     const uint64_t gs = (g << 1) & 0xfefefefefefefefeull;       // a carry never leaves its group of eight
-    const uint64_t cin = ((gs + p) ^ p);                        // lanes a carry arrives at (runs of all-ones limbs pass it on)
+    const uint64_t pc = p & 0x7f7f7f7f7f7f7f7full;              // nor does a propagated one: the top lane passes nothing on
+    const uint64_t cin = ((gs + pc) ^ pc);                      // lanes a carry arrives at (runs of all-ones limbs pass it on)
     return s + (uint32_t)((cin >> (threadIdx.x & 63u)) & 1u);
 }
 
@@ -107,7 +114,8 @@ __device__ __forceinline__ uint32_t cond_sub(uint32_t x, uint32_t mj, const Ctx&
     const uint32_t d = x - mj;
     const uint64_t g = __ballot(x < mj), p = __ballot(d == 0u);
     const uint64_t gs = (g << 1) & 0xfefefefefefefefeull;
-    const uint64_t bin = ((gs + p) ^ p);                        // lanes a borrow arrives at
+    const uint64_t pc = p & 0x7f7f7f7f7f7f7f7full;              // (see resolve_carries: a borrow stops at the top lane)
+    const uint64_t bin = ((gs + pc) ^ pc);                      // lanes a borrow arrives at
     const uint32_t r = d - (uint32_t)((bin >> (threadIdx.x & 63u)) & 1u);
     // a borrow out of the group's top lane: x < m, keep x.  The top lane generated one, or passed one on
     const uint64_t out = (g | (p & bin)) & 0x8080808080808080ull;
@@ -174,4 +182,17 @@ __device__ __forceinline__ Fr gather(uint32_t mine, bool upper) {
 }
 
 }  // namespace lanes
+
+// xor-shuffle tree over the eight lanes of a group: every lane ends with the modular sum of the eight values
+__device__ __forceinline__ Fr group_sum(Fr x) {
+#pragma unroll
+    for (int off = 1; off <= 4; off <<= 1) {
+        Fr o;
+#pragma unroll
+        for (int l = 0; l < 8; ++l) o.l[l] = (uint32_t)__shfl_xor((int)x.l[l], off, 64);
+        x = fr_add(x, o);
+    }
+    return x;
+}
+
 }  // namespace gkr

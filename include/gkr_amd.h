@@ -217,6 +217,58 @@ int  gkr_selftest_seg_item(const gkr_fr *e_lo, const gkr_fr *t, const uint8_t *i
 /* lo + r (hi - lo) through the fixed-multiplier table the fold kernels use */
 int  gkr_selftest_fold(const gkr_fr *lo, const gkr_fr *hi, const gkr_fr *r, gkr_fr *out);
 
+/* ---- the device arithmetic ON THE DEVICE, for unit tests (csrc/kernels_selftest.hip) ------------------------------- */
+/* Each call copies the inputs to the device, runs one small kernel that calls the kernels' own inline functions, and
+ * copies the results back.  Inputs outside a primitive's stated bound: GKR_ERR_INVALID (nothing runs).  Threads are
+ * grouped in waves of 64 (element i in wave i / 64); an operand the kernels hold wave-uniform is given once per wave. */
+enum {
+    /* gkr_devtest_field: canonical a, b (n each); r: one canonical challenge per wave (the fixed-multiplier ops only,
+     * the table built on the device by make_fixed_mul).  out: n values; the paired ops write their second results at
+     * out[n + i] (MUL_FIXED2: b r; FOLD_FIXED2: b + r (a - b)) */
+    GKR_DEVTEST_FR_ADD = 0, GKR_DEVTEST_FR_SUB, GKR_DEVTEST_MONT_MUL, GKR_DEVTEST_FR_MUL, GKR_DEVTEST_TO_MONT,
+    GKR_DEVTEST_FROM_MONT, GKR_DEVTEST_MUL_FIXED, GKR_DEVTEST_MUL_FIXED2, GKR_DEVTEST_FOLD_FIXED, GKR_DEVTEST_FOLD_FIXED2
+};
+enum {
+    /* gkr_devtest_lazy: one dot product of `len` terms per row (a[row * len + t], canonical), reduced by `red`.
+     * b: per row (b[row * len + t]) for MAC_V, MAC_SEL (term t to the first accumulator iff (row + t) % 3 != 0, else the
+     * second), MAC_V_HI (+ a_t 2^256 where row + t is odd); per wave (b[wave * len + t]) for MAC_S, the MACk_S forms
+     * (chain c: sum_t a_t b_{(t + c) % len}) and WEIGHTED_SUM_4 / _8 (len = 4 / 8).  ACC_SUM: sum_t a_t through the 288-bit
+     * accumulator and acc_reduce (no b, `red` unused).  out[row * 4 + c]: accumulator / chain c (unused slots 0). */
+    GKR_DEVTEST_LAZY_MAC_S = 0, GKR_DEVTEST_LAZY_MAC_V, GKR_DEVTEST_LAZY_MAC_SEL, GKR_DEVTEST_LAZY_MAC_V_HI,
+    GKR_DEVTEST_LAZY_MAC2_S, GKR_DEVTEST_LAZY_MAC3_S, GKR_DEVTEST_LAZY_MAC4_S, GKR_DEVTEST_WEIGHTED_SUM_4,
+    GKR_DEVTEST_WEIGHTED_SUM_8, GKR_DEVTEST_ACC_SUM
+};
+enum {
+    /* the reduction of gkr_devtest_lazy: lazy_reduce (canonical), lazy_reduce_k8 (<= 8 products, canonical),
+     * lazy_reduce_partial32 (<= 32 terms; some representative below 2^256) */
+    GKR_DEVTEST_RED_FULL = 0, GKR_DEVTEST_RED_K8, GKR_DEVTEST_RED_PARTIAL32
+};
+enum {
+    /* gkr_devtest_reduce: raw little-endian 32-bit limbs, n elements; limbs in -> limbs out per element:
+     * MF_REDUCE_274 9 (< 2^274) -> 8; CROSS_REDUCE 17 (< 2^519) -> 8; LAZY_REDUCE 17 -> 8; LAZY_REDUCE_K8 17 (< 8 p^2) -> 8;
+     * LAZY_REDUCE_PARTIAL32 17 (< 32 p 2^256) -> 8; LAZY_ADD_HI 26 (acc 17, x 8 below p, on 1) -> 17 (acc + on x 2^256);
+     * ACC_ADD_FR9 17 (acc 9, x 8 below p) -> 9; ACC_REDUCE9 9 -> 8; ADD256 16 (a, b) -> 8; SUB256 16 (a, b) -> 9 (a - b,
+     * borrow mask); COND_SUB_MOD 8 (< 2p) -> 8 */
+    GKR_DEVTEST_MF_REDUCE_274 = 0, GKR_DEVTEST_CROSS_REDUCE, GKR_DEVTEST_LAZY_REDUCE, GKR_DEVTEST_LAZY_REDUCE_K8,
+    GKR_DEVTEST_LAZY_REDUCE_PARTIAL32, GKR_DEVTEST_LAZY_ADD_HI, GKR_DEVTEST_ACC_ADD_FR9, GKR_DEVTEST_ACC_REDUCE9,
+    GKR_DEVTEST_ADD256, GKR_DEVTEST_SUB256, GKR_DEVTEST_COND_SUB_MOD
+};
+enum {
+    /* gkr_devtest_lanes: the MiMC7 lane code (mimc_lanes.h), eight lanes per element and eight elements per wave as
+     * k_mle_pass_hash_lanes lays them out; n elements (the last wave may be ragged).  MONT_MUL x y / 2^256 (operands < 3p;
+     * the lanes' representative, < 2.7p); ADD3 x + y + z (< 2^256); COND_SUB_P / _2P (any x); RESOLVE x + y 2^32 with
+     * limb j of y the carry lane j holds (< 2^256); PERMUTATION hash(x, key y), both below p, Montgomery form (< 2p);
+     * MULTI_HASHk multi_hash of the first k of x, y, z with key 0 (canonical in and out); GROUP_SUM: x holds 8 n
+     * canonical values, one per lane, out the modular sum of each element's eight in all eight lanes' slots */
+    GKR_DEVTEST_LANES_MONT_MUL = 0, GKR_DEVTEST_LANES_ADD3, GKR_DEVTEST_LANES_COND_SUB_P, GKR_DEVTEST_LANES_COND_SUB_2P,
+    GKR_DEVTEST_LANES_RESOLVE, GKR_DEVTEST_LANES_PERMUTATION, GKR_DEVTEST_LANES_MULTI_HASH1, GKR_DEVTEST_LANES_MULTI_HASH2,
+    GKR_DEVTEST_LANES_MULTI_HASH3, GKR_DEVTEST_LANES_GROUP_SUM
+};
+int  gkr_devtest_field(gkr_ctx *ctx, int op, const gkr_fr *a, const gkr_fr *b, const gkr_fr *r, size_t n, gkr_fr *out);
+int  gkr_devtest_lazy(gkr_ctx *ctx, int op, int red, const gkr_fr *a, const gkr_fr *b, size_t rows, size_t len, gkr_fr *out);
+int  gkr_devtest_reduce(gkr_ctx *ctx, int op, const uint32_t *limbs, size_t n, uint32_t *out);
+int  gkr_devtest_lanes(gkr_ctx *ctx, int op, const gkr_fr *x, const gkr_fr *y, const gkr_fr *z, size_t n, gkr_fr *out);
+
 /* ---- plain multilinear sumcheck: prove_sumcheck(g, v), sumcheck.rs:158-161 --- */
 /* table: 2^n canonical evaluations on the host.  out_coeffs: n rows x 2 slots;
  * out_len[j] in {1,2}; out_r: n challenges.  n >= 2. */

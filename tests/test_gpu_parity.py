@@ -120,7 +120,9 @@ def test_mle_extreme_byte_patterns_match_oracle(ctx, n):
                                  {"GKR_NO_IFMA": "1"}, {"GKR_NO_IFMA": "1", "GKR_NO_ADX": "1"}, {"GKR_HOST_PASS_SCALAR": "1"}, {"GKR_PLAN_MAIN": "1", "GKR_FOLD_BLOCKS": "8192"},
                                  {"GKR_PASS_QUEUE_DEPTH": "1", "GKR_GROUP_SIZE": "3"}, {"GKR_PASS_QUEUE_DEPTH": "16", "GKR_GROUP_SIZE": "2"},
                                  {"GKR_NO_FUSED_REDUCE": "1"}, {"GKR_NO_FUSED_REDUCE": "1", "GKR_NO_MFMA_FOLD": "1"},
-                                 {"GKR_DEVICE_HASH_PERCENT": "50"}, {"GKR_DEVICE_HASH_PERCENT": "90", "GKR_ROUNDS_PER_PASS": "3"}],
+                                 {"GKR_DEVICE_HASH_PERCENT": "50"}, {"GKR_DEVICE_HASH_PERCENT": "90", "GKR_ROUNDS_PER_PASS": "3"},
+                                 {"GKR_NO_LATE_STREAM": "1"}, {"GKR_FOLD_MIN_CHUNK": "64"}, {"GKR_FOLD_MIN_CHUNK": "4096"},
+                                 {"GKR_ITEMS_PER_BLOCK": "256"}, {"GKR_ITEMS_PER_BLOCK": "768"}],
                          ids=lambda e: ",".join("%s=%s" % kv for kv in e.items()))
 def test_fold_pass_variants_match_oracle(env):
     """Every schedule of the host-transcript sumcheck gives the same transcript: the v_mad_u64_u32 fold instead
@@ -309,7 +311,7 @@ def test_layer_sumcheck_matches_oracle(ctx, seed):
 
 @pytest.mark.parametrize("env", [{}, {"GKR_NO_CIRCUIT_CACHE": "1"}, {"GKR_HOST_THREADS": "2", "GKR_HASH_CHUNK": "16"}, {"GKR_NO_IFMA": "1"},
                                  {"GKR_NO_IFMA": "1", "GKR_NO_ADX": "1"}, {"GKR_LINE_STEPWISE": "1"}, {"GKR_NO_FUSED_PUBLISH": "1"},
-                                 {"GKR_GATE_SORT_GLOBAL": "1"}, {"GKR_GATE_GROUPS_MIN_K": "2"}],
+                                 {"GKR_GATE_SORT_GLOBAL": "1"}, {"GKR_GATE_GROUPS_MIN_K": "2"}, {"GKR_PREDICATE_ATOMICS": "1"}],
                          ids=lambda e: ",".join("%s=%s" % kv for kv in e.items()) or "default")
 def test_layer_path_variants_match_oracle(env):
     """The layer sumcheck with the host transcript: linear time over (W, U, V) tables of 2^k entries summed straight from

@@ -56,11 +56,12 @@ def test_matrix_core_product_passes_match_the_checker_and_the_valu_form(k_i, k, 
         W[0::2] = r_minus_1
         W[1::4] = all_ff
     want = cdense.sumcheck_layer_lin_raw(k_i, k, lay.gate_type, lay.left, lay.right, z, W)
-    with Context(0) as a, Context(0) as b, Context(0) as c:
+    with Context(0) as a, Context(0) as b, Context(0) as c, Context(0) as d:
         b.set_option("no_mfma_cross", 1)
         c.set_option("prod_fold_min_log2", 14 if k < 20 else 20)   # (every later pass folds on the matrix cores / only the second)
+        d.set_option("prod_cross_min_log2", 13)                     # (cross sums on the matrix cores from 2^13 entries)
         assert a.get_option("no_mfma_cross") == 0
-        for ctx_ in (a, b, c):
+        for ctx_ in (a, b, c, d):
             assert _same(ctx_.sumcheck_layer_raw(lay, k, z, W), want)
 
 
