@@ -300,8 +300,11 @@ int gkr_verify(const gkr_circuit_desc* circuit, const gkr_proof_buf* proof, int 
         !proof->d_coeffs || !proof->input_coeffs || !circuit->gate_type || !circuit->left || !circuit->right)
         return GKR_ERR_INVALID;
     const uint32_t L = circuit->depth;
-    for (uint32_t i = 0; i <= L; ++i)
+    for (uint32_t i = 0; i <= L; ++i) {
+        // k[i+1] == 0: a layer with no sumcheck rounds, which gkr_prove refuses as well (check_circuit)
+        if (i > 0 && circuit->k[i] == 0) return GKR_ERR_DEGENERATE;
         if (circuit->k[i] > (i == 0 ? (uint32_t)GKR_MAX_K_I : (uint32_t)GKR_MAX_K_NEXT)) return GKR_ERR_INVALID;
+    }
     if (threads <= 0) threads = default_threads();
     *accept = 0;
     uint32_t layer_out = 0, check_out = 0;

@@ -194,17 +194,21 @@ __device__ __forceinline__ void mfma_multifold_block(const Fr* __restrict__ s, F
 #pragma unroll
     for (int r = 0; r < 16; ++r) init[r] = plan->start[h][r];
 
-    const uint32_t wave = tid >> 6;
-    // addresses as (wave-uniform stream base) + (one 32-bit lane offset) + (immediate): the 2^JIN streams cost
-    // scalar registers, not a 64-bit vector address each
+    // (readfirstlane: the compiler cannot see that tid >> 6 is the same on every lane, and the tile start e0 derived
+    // from it must be, to sit in the scalar stream base below)
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // addresses as (wave-uniform 64-bit base: stream + tile start e0) + (one 32-bit lane offset below 2^11) +
+    // (immediate): the 2^JIN streams cost scalar registers, not a 64-bit vector address each.  The tile start stays
+    // out of the lane offset: at S > 2^27 entries, (e0 + c) * 32 bytes passes 2^32.
     auto load_stage = [&](uint32_t e0, int stage, mf_v4u (&x)[2][KS]) {
-        const uint32_t voff = (e0 + c) * 32u + 16u * h;
+        const uint32_t voff = c * 32u + 16u * h;
+        const Fr* tile = s + e0;
 #pragma unroll
         for (int k = 0; k < KS; ++k) {
 #if defined(MF_STREAM_PAD)   // experiment (tools/ubench_mfma_fold.hip): streams MF_STREAM_PAD entries further apart
-            const char* base = reinterpret_cast<const char*>(s + (size_t)(stage * KS + k) * (S + MF_STREAM_PAD));
+            const char* base = reinterpret_cast<const char*>(tile + (size_t)(stage * KS + k) * (S + MF_STREAM_PAD));
 #else
-            const char* base = reinterpret_cast<const char*>(s + (size_t)(stage * KS + k) * S);
+            const char* base = reinterpret_cast<const char*>(tile + (size_t)(stage * KS + k) * S);
 #endif
 #pragma unroll
             for (int t = 0; t < 2; ++t)

@@ -88,6 +88,16 @@ def proof_coeffs_digest(d_coeffs, input_coeffs):
     return transcript_digest(np.ascontiguousarray(d_coeffs), np.ascontiguousarray(input_coeffs))
 
 
+def proof_batch_digest(ks, arrays):
+    """sha256 over a batch of proofs: the nine arrays of gkr_prove_batch (first axis = proof; prove_batch_raw with
+    all_arrays=True), per proof proof_arrays_digest and proof_coeffs_digest in hex, proofs in order."""
+    h = hashlib.sha256()
+    for b in range(arrays[0].shape[0]):
+        h.update(proof_arrays_digest(ks, *[a[b] for a in arrays[:7]]).encode())
+        h.update(proof_coeffs_digest(arrays[7][b], arrays[8][b]).encode())
+    return h.hexdigest()
+
+
 def proof_arrays_from_checker(ref, ks):
     """cdense.prove_raw's dict -> the seven arrays in gkr_proof_buf layout (one proof)."""
     L = len(ks) - 1

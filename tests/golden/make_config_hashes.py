@@ -3,6 +3,8 @@
 
     python tests/golden/make_config_hashes.py      # rewrites tests/golden/config_hashes.json (~1 min of CPU)
     python tests/golden/make_config_hashes.py --bench-batch   # rewrites tests/golden/bench_batch_hashes.json (~6 min, 8 cores)
+    python tests/golden/make_config_hashes.py --limits   # adds the size-limit workloads of tests/test_gpu_limits.py to
+                                                          # config_hashes.json (~10 min on 8 cores, up to ~16 GiB of memory)
 
 For each workload of gkr_amd.synth the C oracle (oracle/c, pinned against the reference-generated fixtures by
 tests/test_oracle_*.py) produces the transcript; what is committed is sha256 over the raw output arrays
@@ -112,7 +114,114 @@ def large_r1cs_digests(nrounds=65536, pair=(2, 3)):
     return out
 
 
+LIMIT_LAYERS = ((28, 12), (28, 14), (20, 24), (28, 24))   # GKR_MAX_K_I = 28, GKR_MAX_K_NEXT = 24 (include/gkr_amd.h)
+LIMIT_PROOF = (18, 24, 24)
+LIMIT_BATCH = (65535, (2, 14))   # gkr_sumcheck_mle_batch_device's cap on sumchecks per call, at two table sizes
+LIMIT_PROOFS = 4096              # GKR_MAX_BATCH: proofs per gkr_prove_batch
+
+
+def batch_table_seed(seed, j, n):
+    """The seed with which oracle/c's fill_table(2^n, .) writes table j of fill_table(B * 2^n, seed) (entry i's limbs hash
+    seed + (4 i + limb + 1) * 0x9E3779B97F4A7C15, so a slice is a fill of its own with the seed moved along)."""
+    return (seed + 4 * (j << n) * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+
+
+def _mle_batch_part(args):
+    n, seed, lo, hi = args
+    cdense.lib().ogkr_set_threads(1)   # (one OpenMP thread per process: eight processes of eight spinning threads crawl)
+    tables = cdense.fill_table((hi - lo) << n, batch_table_seed(seed, lo, n))
+    out = [cdense.sumcheck_mle_raw(tables[(j << n):((j + 1) << n)], n, 1) for j in range(hi - lo)]
+    return lo, [np.stack(x) for x in zip(*out)]
+
+
+def mle_batch_digest(batch, n, seed):
+    """sha256 over the (C | L | R) arrays of gkr_sumcheck_mle_batch_device on fill_table(batch * 2^n, seed), the C ABI's layout
+    for the whole batch; each table's transcript by the C oracle, in spawned processes (one thread each)."""
+    import multiprocessing
+    C = np.zeros((batch, n, 2, 4), dtype=np.uint64)
+    L = np.zeros((batch, n), dtype=np.uint32)
+    R = np.zeros((batch, n, 4), dtype=np.uint64)
+    step = 256
+    parts = [(n, seed, lo, min(batch, lo + step)) for lo in range(0, batch, step)]
+    with multiprocessing.get_context("spawn").Pool(min(8, os.cpu_count() or 1)) as pool:
+        for lo, (c, l, r) in pool.imap_unordered(_mle_batch_part, parts):
+            C[lo:lo + len(c)], L[lo:lo + len(c)], R[lo:lo + len(c)] = c, l, r
+    return digest(C, L, R)
+
+
+def _proof_batch_part(args):
+    lo, hi = args
+    cdense.lib().ogkr_set_threads(1)
+    circuit = synth.proof_batch_circuit()
+    raw, ks = [lay.arrays() for lay in circuit.layer], synth.PROOF_BATCH_KS
+    out = []
+    for w in synth.proof_batch_witnesses(hi - lo, first=lo):
+        ref = cdense.prove_raw(raw, w, 1)
+        out.append(list(synth.proof_arrays_from_checker(ref, ks)) + [cdense.mobius_raw(ref["values"][0], ks[0]), cdense.mobius_raw(ref["values"][-1], ks[-1])])
+    return lo, out
+
+
+def proof_batch_digest(n_proofs):
+    """gkr_amd.synth.proof_batch_digest of the C oracle's proofs of synth.proof_batch_circuit() for the first n_proofs witnesses
+    of synth.proof_batch_witnesses, in spawned processes (one thread each)."""
+    import multiprocessing
+    proofs = [None] * n_proofs
+    step = 128
+    with multiprocessing.get_context("spawn").Pool(min(8, os.cpu_count() or 1)) as pool:
+        for lo, part in pool.imap_unordered(_proof_batch_part, [(lo, min(n_proofs, lo + step)) for lo in range(0, n_proofs, step)]):
+            proofs[lo:lo + len(part)] = part
+    return synth.proof_batch_digest(synth.PROOF_BATCH_KS, [np.stack(x) for x in zip(*proofs)])
+
+
+def limits_digests(path):
+    """The workloads of tests/test_gpu_limits.py, at the ABI's size limits: adds the keys the committed file lacks, writing
+    it after each (the largest take minutes and up to ~16 GiB of host memory)."""
+    import time
+    cur = json.load(open(path))
+
+    def put(kind, key, fn):
+        if key in cur.setdefault(kind, {}):
+            return
+        t = time.time()
+        cur[kind][key] = fn()
+        with open(path, "w") as f:
+            json.dump(cur, f, indent=1, sort_keys=True)
+            f.write("\n")
+        print("%s %s: %.0f s" % (kind, key, time.time() - t), flush=True)
+
+    # (the batches first: their process pool is spawned before this process starts the oracle's OpenMP runtime)
+    batch, ns = LIMIT_BATCH
+    for n in ns:
+        put("mle_batch", "batch=%d,n=%d,seed=%d" % (batch, n, synth.SEED + 11), lambda: mle_batch_digest(batch, n, synth.SEED + 11))
+    put("prove_batch", "k=%s,proofs=%d" % (",".join(map(str, synth.PROOF_BATCH_KS)), LIMIT_PROOFS), lambda: proof_batch_digest(LIMIT_PROOFS))
+
+    def mle_inplace(n):
+        C, L, R = cdense.sumcheck_mle_inplace_raw(cdense.fill_table(1 << n, synth.SEED + 2), n)   # 2^29 points: 16 GiB
+        return digest(C, L, R)
+    put("mle", "n=29,seed=%d" % (synth.SEED + 2), lambda: mle_inplace(29))
+    for k_i, k in LIMIT_LAYERS:
+        def layer():
+            lay, z, W = synth.config5_layer(k_i, k)
+            return digest(*cdense.sumcheck_layer_lin_raw(k_i, k, lay.gate_type, lay.left, lay.right, z, W))
+        put("layer", "k_i=%d,k=%d" % (k_i, k), layer)
+    ks = LIMIT_PROOF
+    key = "k=" + ",".join(map(str, ks))
+    proof = {}
+
+    def prove():
+        circuit, raw, wit = synth.wide_circuit(ks)
+        ref = cdense.prove_raw(raw, wit[0])
+        proof["coeffs"] = synth.proof_coeffs_digest(cdense.mobius_raw(ref["values"][0], ks[0]), cdense.mobius_raw(ref["values"][-1], ks[-1]))
+        return synth.proof_arrays_digest(list(ks), *synth.proof_arrays_from_checker(ref, list(ks)))
+    put("prove", key, prove)
+    if "coeffs" in proof:
+        put("prove_coeffs", key, lambda: proof["coeffs"])
+
+
 def main():
+    if "--limits" in sys.argv:   # only the size-limit workloads (tests/test_gpu_limits.py), added to the committed file
+        limits_digests(os.path.join(os.path.dirname(os.path.abspath(__file__)), "config_hashes.json"))
+        return
     if "--large-r1cs" in sys.argv:
         path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "large_r1cs_digests.json")
         with open(path, "w") as f:

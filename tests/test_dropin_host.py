@@ -131,3 +131,34 @@ def test_native_verifier_on_a_wider_random_circuit_with_many_threads():
     assert verify_native(circ, pr, threads=8) == (True, 0, 0)
     pr.sumcheck_proofs[1][7][0] = (pr.sumcheck_proofs[1][7][0] + 1) % P
     assert verify_native(circ, pr, threads=8) == (False, 1, 4)
+
+
+@pytest.mark.parametrize("ks", [[1, 0], [2, 3, 0], [0, 0]])
+def test_native_verifier_refuses_a_layer_of_no_values_before_reading_the_proof(ks):
+    """k[i+1] == 0: a layer with no sumcheck rounds, which gkr_prove refuses (GKR_ERR_DEGENERATE, sumcheck.rs:49 underflows).
+    gkr_verify refuses it with the same status, before it reads the proof: every array of the proof here is one page
+    that may not be read (a read ends the process)."""
+    import ctypes
+    import mmap
+    from gkr_amd.prover import Context
+    libc = ctypes.CDLL(None)
+    libc.mmap.restype = ctypes.c_void_p
+    libc.mmap.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_long]
+    libc.munmap.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
+    PROT_NONE = 0
+    page = libc.mmap(None, mmap.PAGESIZE, PROT_NONE, mmap.MAP_PRIVATE | mmap.MAP_ANONYMOUS, -1, 0)
+    assert page and page != ctypes.c_void_p(-1).value
+    try:
+        rng = np.random.default_rng(len(ks))
+        circ = GKRCircuit([Layer(ks[i], rng.integers(0, 2, 1 << ks[i]).tolist(), rng.integers(0, 1 << ks[i + 1], 1 << ks[i]).tolist(),
+                                 rng.integers(0, 1 << ks[i + 1], 1 << ks[i]).tolist()) for i in range(len(ks) - 1)], ks[-1])
+        desc, alive = Context._circuit_desc(None, circ)
+        buf = N.ProofBuf(*([page] * 9))
+        accept, layer, check = ctypes.c_int(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+        for threads in (1, 0):
+            rc = N.lib().gkr_verify(ctypes.byref(desc), ctypes.byref(buf), ctypes.c_int(threads), ctypes.byref(accept),
+                                    ctypes.byref(layer), ctypes.byref(check))
+            assert rc == N.GKR_ERR_DEGENERATE, (ks, threads, rc)
+            assert accept.value == 0
+    finally:
+        libc.munmap(page, mmap.PAGESIZE)
