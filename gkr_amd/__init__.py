@@ -6,11 +6,11 @@ reference's prover interface; it has no CPU fallback.
 """
 
 from .field import MODULUS, from_limbs, to_limbs
-from .prover import (Context, GKRCircuit, GkrError, Layer, Proof, default_context, multi_hash, prove,
+from .prover import (Context, GKRCircuit, GkrError, Layer, Proof, VerifyHandle, default_context, multi_hash, prove,
                      prove_sumcheck, prove_sumcheck_opt)
 
 from .verifier import verify
 from .aggregate import aggregated_input, circom_input, circom_meta
 
-__all__ = ["verify", "aggregated_input", "circom_input", "circom_meta", "MODULUS", "from_limbs", "to_limbs", "Context", "GKRCircuit", "GkrError", "Layer", "Proof",
+__all__ = ["verify", "aggregated_input", "circom_input", "circom_meta", "MODULUS", "from_limbs", "to_limbs", "Context", "GKRCircuit", "GkrError", "Layer", "Proof", "VerifyHandle",
            "default_context", "multi_hash", "prove", "prove_sumcheck", "prove_sumcheck_opt"]

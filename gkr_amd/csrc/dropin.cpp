@@ -26,21 +26,17 @@
 #include "../../include/gkr_amd.h"
 #include "fr64.h"
 #include "host_cpus.h"
+#include "verify_core.h"
 
 namespace {
 
 using gkr::h64::F;
 using gkr::h64::Wide;
 
-inline F load(const gkr_fr& x) {
-    F f;
-    memcpy(f.l, x.l, 32);
-    return f;
-}
-inline bool canonical(const gkr_fr& x) { return !gkr::h64::geq_mod(load(x)); }
-inline bool is_one(const gkr_fr& x) { return x.l[0] == 1 && !(x.l[1] | x.l[2] | x.l[3]); }
-inline bool is_zero(const gkr_fr& x) { return !(x.l[0] | x.l[1] | x.l[2] | x.l[3]); }
-inline bool same(const F& a, const F& b) { return memcmp(a.l, b.l, 32) == 0; }
+using gkr::verify::canonical;   // (verify_core.h: the element helpers the verifier's shared relations use)
+using gkr::verify::is_one;
+using gkr::verify::is_zero;
+using gkr::verify::load;
 
 const F kOneCanonical = {{1, 0, 0, 0}};
 inline F mont_one() { return gkr::h64::to_mont(kOneCanonical); }
@@ -141,13 +137,6 @@ void eq_table(const std::vector<F>& point_m, Table& table, int threads) {
     });
 }
 
-// Horner, highest degree first (poly.rs:260-267); coefficients canonical, x Montgomery -> canonical
-F horner(const gkr_fr* c, int n, const F& x_m) {
-    F acc = {{0, 0, 0, 0}};
-    for (int i = 0; i < n; ++i) acc = gkr::h64::add(gkr::h64::mont_mul(acc, x_m), load(c[i]));
-    return acc;
-}
-
 // sum_mask coeff[mask] prod_{i in mask} x_i for a table of 2^k monomial coefficients (mask bit k-1-j <-> variable j+1):
 // the variables are bound one by one, last variable first (c[rest,0] + x c[rest,1]); canonical in, x Montgomery, canonical out
 F eval_monomial_table(const gkr_fr* coeffs, int k, const std::vector<F>& x_m, int threads) {
@@ -197,6 +186,73 @@ bool all_canonical_par(const gkr_fr* v, size_t n, int threads) {
     });
     return !bad.load();
 }
+
+// gkr_verify's provider of the shared relations (verify_core.h): the sums over the gates and over the coefficient tables on
+// `threads` host threads
+struct HostProvider {
+    const gkr_circuit_desc* circuit;
+    const gkr_proof_buf* proof;
+    int threads;
+    Table tab_z, tab_b, tab_c;
+
+    int layer_ready(uint32_t i) const { return !circuit->gate_type[i] || !circuit->left[i] || !circuit->right[i] ? GKR_ERR_INVALID : GKR_OK; }
+    bool table_canonical(int which) const {
+        return all_canonical_par(which ? proof->input_coeffs : proof->d_coeffs, (size_t)1 << circuit->k[which ? circuit->depth : 0], threads);
+    }
+    F table_eval(int which, const std::vector<F>& z_m) const {
+        return eval_monomial_table(which ? proof->input_coeffs : proof->d_coeffs, (int)circuit->k[which ? circuit->depth : 0], z_m, threads);
+    }
+    int hash(size_t, const gkr_fr* g, uint32_t len, gkr_fr* h) const {
+        gkr_fr key = {{0, 0, 0, 0}};
+        return gkr_mimc7_multi_hash(g, len, &key, h);
+    }
+    int wiring(uint32_t i, const std::vector<F>& zi_m, const std::vector<F>& b_m, const std::vector<F>& c_m, F* add_out, F* mult_out) {
+        const int k_i = (int)circuit->k[i], k = (int)circuit->k[i + 1];
+        const size_t gates = (size_t)1 << k_i;
+        const F zero = {{0, 0, 0, 0}};
+        eq_table(zi_m, tab_z, threads);
+        eq_table(b_m, tab_b, threads);
+        eq_table(c_m, tab_c, threads);
+        const F *eq_z = tab_z.p.get(), *eq_b = tab_b.p.get(), *eq_c = tab_c.p.get();
+        const uint8_t* gt = circuit->gate_type[i];
+        const uint32_t *lf = circuit->left[i], *rt = circuit->right[i];
+        const uint32_t limit = (uint32_t)1 << k;
+        std::vector<F> part_add((size_t)threads, zero), part_mult((size_t)threads, zero);
+        std::atomic<int> bad_gate{0};
+        parallel_for(gates, threads, 2048, [&](int t, size_t a, size_t b) {
+            F sa = zero, sm = zero;
+            for (size_t base = a; base < b; base += 4096) {          // one reduction per 4096 products
+                Wide wa = gkr::h64::wide_zero(), wm = gkr::h64::wide_zero();
+                const size_t end = std::min(b, base + 4096);
+                for (size_t g = base; g < end; ++g) {
+                    if (lf[g] >= limit || rt[g] >= limit || gt[g] > 1) {
+                        bad_gate.store(1);
+                        return;
+                    }
+                    if (g + 12 < end && lf[g + 12] < limit && rt[g + 12] < limit) {   // (the operands' eq entries are random reads of 32 MiB tables)
+                        __builtin_prefetch(&eq_b[lf[g + 12]]);
+                        __builtin_prefetch(&eq_c[rt[g + 12]]);
+                    }
+                    const F bc = gkr::h64::mont_mul(eq_b[lf[g]], eq_c[rt[g]]);
+                    gkr::h64::wide_mac(gt[g] ? wm : wa, eq_z[g], bc);
+                }
+                sa = gkr::h64::add(sa, gkr::h64::wide_reduce(wa));
+                sm = gkr::h64::add(sm, gkr::h64::wide_reduce(wm));
+            }
+            part_add[t] = sa;
+            part_mult[t] = sm;
+        });
+        if (bad_gate.load()) return GKR_ERR_INVALID;
+        F add_m = zero, mult_m = zero;
+        for (int t = 0; t < threads; ++t) {
+            add_m = gkr::h64::add(add_m, part_add[t]);
+            mult_m = gkr::h64::add(mult_m, part_mult[t]);
+        }
+        *add_out = add_m;
+        *mult_out = mult_m;
+        return GKR_OK;
+    }
+};
 
 }  // namespace
 
@@ -296,141 +352,11 @@ int gkr_prove_wires(gkr_ctx* ctx, const gkr_wire_circuit* wc, const gkr_fr* inpu
 int gkr_verify(const gkr_circuit_desc* circuit, const gkr_proof_buf* proof, int threads, int* accept, uint32_t* failed_layer,
                uint32_t* failed_check) {
     if (!circuit || !proof || !accept || !circuit->k || circuit->depth < 1 || circuit->depth > 4096) return GKR_ERR_INVALID;
-    if (!proof->sumcheck_coeffs || !proof->sumcheck_len || !proof->sumcheck_r || !proof->q || !proof->q_len || !proof->z || !proof->r ||
-        !proof->d_coeffs || !proof->input_coeffs || !circuit->gate_type || !circuit->left || !circuit->right)
-        return GKR_ERR_INVALID;
-    const uint32_t L = circuit->depth;
-    for (uint32_t i = 0; i <= L; ++i) {
-        // k[i+1] == 0: a layer with no sumcheck rounds, which gkr_prove refuses as well (check_circuit)
-        if (i > 0 && circuit->k[i] == 0) return GKR_ERR_DEGENERATE;
-        if (circuit->k[i] > (i == 0 ? (uint32_t)GKR_MAX_K_I : (uint32_t)GKR_MAX_K_NEXT)) return GKR_ERR_INVALID;
-    }
+    if (!gkr::verify::proof_pointers_set(proof) || !circuit->gate_type || !circuit->left || !circuit->right) return GKR_ERR_INVALID;
+    if (const int rc = gkr::verify::check_k_list(circuit)) return rc;
     if (threads <= 0) threads = default_threads();
-    *accept = 0;
-    uint32_t layer_out = 0, check_out = 0;
-    auto reject = [&](uint32_t layer, uint32_t check) {
-        layer_out = layer;
-        check_out = check;
-        if (failed_layer) *failed_layer = layer;
-        if (failed_check) *failed_check = check;
-        return GKR_OK;
-    };
-    const F zero = {{0, 0, 0, 0}};
-    const F one_m = mont_one();
-    // z[0] = 0 (prover.rs:16-21) and m_0 = D(z[0])
-    const gkr_fr* z = proof->z;
-    std::vector<F> zi_m(circuit->k[0]);
-    for (uint32_t j = 0; j < circuit->k[0]; ++j) {
-        if (!is_zero(z[j])) return reject(0, GKR_VERIFY_Z0);
-        zi_m[j] = zero;
-    }
-    if (!all_canonical_par(proof->d_coeffs, (size_t)1 << circuit->k[0], threads)) return reject(0, GKR_VERIFY_NON_CANONICAL);
-    F m = eval_monomial_table(proof->d_coeffs, (int)circuit->k[0], zi_m, threads);
-    size_t row = 0, qo = 0, zo = circuit->k[0];
-    Table tab_z, tab_b, tab_c;
-    for (uint32_t i = 0; i < L; ++i) {
-        const int k_i = (int)circuit->k[i], k = (int)circuit->k[i + 1];
-        const size_t gates = (size_t)1 << k_i;
-        if (!circuit->gate_type[i] || !circuit->left[i] || !circuit->right[i]) return GKR_ERR_INVALID;
-        // the sumcheck's rounds (python/sumcheck.py:55-70)
-        F expected = m;
-        std::vector<F> rs_m(2 * (size_t)k);
-        for (int j = 0; j < 2 * k; ++j, ++row) {
-            const uint32_t len = proof->sumcheck_len[row];
-            if (len < 1 || len > 3) return reject(i, GKR_VERIFY_SHAPE);
-            const gkr_fr* g = proof->sumcheck_coeffs + row * 3 + (3 - len);
-            for (uint32_t t = 0; t < len; ++t)
-                if (!canonical(g[t])) return reject(i, GKR_VERIFY_NON_CANONICAL);
-            if (!canonical(proof->sumcheck_r[row])) return reject(i, GKR_VERIFY_NON_CANONICAL);
-            F at1 = zero;                                    // g(1) = sum of the coefficients, g(0) = the constant term
-            for (uint32_t t = 0; t < len; ++t) at1 = gkr::h64::add(at1, load(g[t]));
-            if (!same(gkr::h64::add(at1, load(g[len - 1])), expected)) return reject(i, GKR_VERIFY_ROUND_SUM);
-            gkr_fr key = {{0, 0, 0, 0}}, h;
-            if (gkr_mimc7_multi_hash(g, len, &key, &h) != GKR_OK) return GKR_ERR_INVALID;
-            if (memcmp(h.l, proof->sumcheck_r[row].l, 32) != 0) return reject(i, GKR_VERIFY_CHALLENGE);
-            rs_m[j] = gkr::h64::to_mont(load(proof->sumcheck_r[row]));
-            expected = horner(g, (int)len, rs_m[j]);
-        }
-        // q(0), q(1), and the last claim against add(z,b*,c*) (q0 + q1) + mult(z,b*,c*) q0 q1 (python/gkr.py:213-219)
-        const uint32_t qlen = proof->q_len[i];
-        if (qlen < 1 || qlen > (uint32_t)k + 1) return reject(i, GKR_VERIFY_SHAPE);
-        const gkr_fr* q = proof->q + qo + ((size_t)k + 1 - qlen);
-        for (uint32_t t = 0; t < qlen; ++t)
-            if (!canonical(q[t])) return reject(i, GKR_VERIFY_NON_CANONICAL);
-        const F q0 = load(q[qlen - 1]);
-        F q1 = zero;
-        for (uint32_t t = 0; t < qlen; ++t) q1 = gkr::h64::add(q1, load(q[t]));
-        std::vector<F> b_m(rs_m.begin(), rs_m.begin() + k), c_m(rs_m.begin() + k, rs_m.end());
-        eq_table(zi_m, tab_z, threads);
-        eq_table(b_m, tab_b, threads);
-        eq_table(c_m, tab_c, threads);
-        const F *eq_z = tab_z.p.get(), *eq_b = tab_b.p.get(), *eq_c = tab_c.p.get();
-        const uint8_t* gt = circuit->gate_type[i];
-        const uint32_t *lf = circuit->left[i], *rt = circuit->right[i];
-        const uint32_t limit = (uint32_t)1 << k;
-        std::vector<F> part_add((size_t)threads, zero), part_mult((size_t)threads, zero);
-        std::atomic<int> bad_gate{0};
-        parallel_for(gates, threads, 2048, [&](int t, size_t a, size_t b) {
-            F sa = zero, sm = zero;
-            for (size_t base = a; base < b; base += 4096) {          // one reduction per 4096 products
-                Wide wa = gkr::h64::wide_zero(), wm = gkr::h64::wide_zero();
-                const size_t end = std::min(b, base + 4096);
-                for (size_t g = base; g < end; ++g) {
-                    if (lf[g] >= limit || rt[g] >= limit || gt[g] > 1) {
-                        bad_gate.store(1);
-                        return;
-                    }
-                    if (g + 12 < end && lf[g + 12] < limit && rt[g + 12] < limit) {   // (the operands' eq entries are random reads of 32 MiB tables)
-                        __builtin_prefetch(&eq_b[lf[g + 12]]);
-                        __builtin_prefetch(&eq_c[rt[g + 12]]);
-                    }
-                    const F bc = gkr::h64::mont_mul(eq_b[lf[g]], eq_c[rt[g]]);
-                    gkr::h64::wide_mac(gt[g] ? wm : wa, eq_z[g], bc);
-                }
-                sa = gkr::h64::add(sa, gkr::h64::wide_reduce(wa));
-                sm = gkr::h64::add(sm, gkr::h64::wide_reduce(wm));
-            }
-            part_add[t] = sa;
-            part_mult[t] = sm;
-        });
-        if (bad_gate.load()) return GKR_ERR_INVALID;
-        F add_m = zero, mult_m = zero;                        // Montgomery forms of add_i, mult_i at (z, b*, c*)
-        for (int t = 0; t < threads; ++t) {
-            add_m = gkr::h64::add(add_m, part_add[t]);
-            mult_m = gkr::h64::add(mult_m, part_mult[t]);
-        }
-        const F q01 = gkr::h64::mont_mul(gkr::h64::to_mont(q0), q1);             // canonical q0 q1
-        const F want = gkr::h64::add(gkr::h64::mont_mul(add_m, gkr::h64::add(q0, q1)), gkr::h64::mont_mul(mult_m, q01));
-        if (!same(want, expected)) return reject(i, GKR_VERIFY_FINAL_CLAIM);
-        // r* = hash of the last round vector (prover.rs:74-78), z[i+1] = l(r*) (poly.rs:538-551), m = q(r*)
-        {
-            const size_t last = row - 1;
-            const uint32_t len = proof->sumcheck_len[last];
-            gkr_fr key = {{0, 0, 0, 0}}, h;
-            if (gkr_mimc7_multi_hash(proof->sumcheck_coeffs + last * 3 + (3 - len), len, &key, &h) != GKR_OK) return GKR_ERR_INVALID;
-            if (memcmp(h.l, proof->r[i].l, 32) != 0) return reject(i, GKR_VERIFY_R_STAR);
-        }
-        const F rstar_m = gkr::h64::to_mont(load(proof->r[i]));
-        zi_m.assign((size_t)k, zero);
-        for (int j = 0; j < k; ++j) {
-            const F bj = load(proof->sumcheck_r[row - 2 * (size_t)k + j]), cj = load(proof->sumcheck_r[row - (size_t)k + j]);
-            const F zj = gkr::h64::add(bj, gkr::h64::mont_mul(rstar_m, gkr::h64::sub(cj, bj)));
-            if (!canonical(z[zo + j]) || !same(zj, load(z[zo + j]))) return reject(i, GKR_VERIFY_NEXT_Z);
-            zi_m[j] = gkr::h64::to_mont(zj);
-        }
-        m = horner(q, (int)qlen, rstar_m);
-        qo += (size_t)k + 1;
-        zo += (size_t)k;
-    }
-    if (!all_canonical_par(proof->input_coeffs, (size_t)1 << circuit->k[L], threads)) return reject(L, GKR_VERIFY_NON_CANONICAL);
-    if (!same(m, eval_monomial_table(proof->input_coeffs, (int)circuit->k[L], zi_m, threads))) return reject(L, GKR_VERIFY_INPUT);
-    (void)one_m;
-    (void)layer_out;
-    (void)check_out;
-    *accept = 1;
-    if (failed_layer) *failed_layer = 0;
-    if (failed_check) *failed_check = GKR_VERIFY_OK;
-    return GKR_OK;
+    HostProvider prov{circuit, proof, threads};
+    return gkr::verify::relations(circuit->depth, circuit->k, proof, prov, accept, failed_layer, failed_check);
 }
 
 }  // extern "C"

@@ -350,6 +350,36 @@ void launch_predicate_sorted(uint32_t k_i, uint32_t k_next, const uint8_t* gate_
                              hipStream_t s);
 void launch_predicate_normalise(const unsigned long long* wide, Fr* out, size_t cells, hipStream_t s);
 
+// ---- device verifier (kernels_verify.hip) ------------------------------------------------------------------------------------
+// prepare: gate arrays of 2^k_i gates -> packed records {left | type << 31, right}; *bad |= 1 (zeroed by the caller) on an
+// operand >= 2^k or a type > 1
+void launch_verify_pack(const uint8_t* gate_type, const uint32_t* left, const uint32_t* right, uint32_t gates, uint32_t k, uint2* packed,
+                        uint32_t* bad, hipStream_t s);
+// One layer of the wiring pass, as the launch over all layers and proofs of a chunk reads it from device memory: the packed
+// gates and the chunk's tables of this layer (all Montgomery; proof p's table at base + (p << log2 entries)): eq(z_i, .) as the
+// half tables e_hi (k_i - kl leading variables) and e_lo (kl trailing ones), eq(b*, .) and eq(c*, .) of 2^k entries.
+struct VerifyLayer {
+    const uint2* gates;
+    const Fr* e_hi;
+    const Fr* e_lo;
+    const Fr* eq_b;
+    const Fr* eq_c;
+    uint32_t k_i, kl, k, pad;
+};
+static_assert(sizeof(VerifyLayer) == 56, "layer table entry");
+uint32_t verify_wiring_blocks(uint32_t max_k_i);   // blocks per (layer, proof) of the wiring pass
+// out[(proof * n_layers + layer) * 2 + (0 add | 1 mult)] = the wiring predicate at (z, b*, c*), Montgomery; partials: batch x
+// n_layers x 2 x verify_wiring_blocks(max_k_i) elements of scratch.  One launch for the pass, one for the second-level sums.
+void launch_verify_wiring(const VerifyLayer* layers, uint32_t n_layers, uint32_t max_k_i, uint32_t batch, Fr* partials, Fr* out, hipStream_t s);
+// flags[p * flag_stride] |= 1 when proof p's table (2^k coefficients, proofs contiguous) holds an element >= r.  One launch.
+void launch_verify_canonical(const Fr* coeffs, uint32_t k, uint32_t* flags, uint32_t flag_stride, uint32_t batch, hipStream_t s);
+uint32_t verify_mono_blocks(uint32_t k);
+// out[proof] = sum_S coeffs[proof][S] prod_{j in S} x_j (canonical) for `batch` tables of 2^k monomial coefficients (index
+// MSB-first), x = points[proof * stride + first ..+k) canonical.  t_hi: batch x 2^(k - k/2), t_lo: batch x 2^(k/2), partials:
+// batch x verify_mono_blocks(k) elements of scratch.
+void launch_verify_mono_eval(const Fr* points, uint32_t stride, uint32_t first, uint32_t k, const Fr* coeffs, Fr* t_hi, Fr* t_lo, Fr* partials,
+                             Fr* out, uint32_t batch, hipStream_t s);
+
 uint32_t layer_blocks(uint32_t h);
 void launch_layer_round(const Fr* A, const Fr* M, uint32_t h, uint32_t k, uint32_t phase, uint32_t hb, const Fr* Wb,
                         const Fr* Wc, uint32_t nblk, LayerPartial* partials, LayerBatch lb, hipStream_t s);

@@ -52,7 +52,9 @@ namespace gkr {
     X(no_circuit_cache, "no_circuit_cache", "GKR_NO_CIRCUIT_CACHE", 0, "do not keep proven circuits' gate arrays and lists on the device between calls") \
     X(prove_many_pieces, "prove_many_pieces", "GKR_PROVE_MANY_PIECES", 0, "gkr_prove_many: cut the costliest items in two until there are this many")      \
     X(prove_many_lockstep, "prove_many_lockstep", "GKR_PROVE_MANY_LOCKSTEP", 1, "gkr_prove_many: items whose circuits share a k list advance in lockstep, one launch per pass for the group (0: one chain per item)") \
-    X(lockstep_max_proofs, "lockstep_max_proofs", "GKR_LOCKSTEP_MAX_PROOFS", 0, "most proofs one lockstep group may hold (0: 32 -- beyond that independent chains overlap better)")
+    X(lockstep_max_proofs, "lockstep_max_proofs", "GKR_LOCKSTEP_MAX_PROOFS", 0, "most proofs one lockstep group may hold (0: 32 -- beyond that independent chains overlap better)") \
+    /* ---- device verifier (gkr_verify_prepared, capi_verify.hip) ---- */                                                            \
+    X(verify_workspace_mb, "verify_workspace_mb", "GKR_VERIFY_WORKSPACE_MB", 0, "gkr_verify_prepared: MiB of device workspace a chunk of proofs may take (0: 2048; a chunk is never less than one proof)")
 
 enum OptionId : int {
 #define GKR_OPT_ENUM(id, name, env, def, doc) OPT_##id,

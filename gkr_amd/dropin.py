@@ -9,6 +9,7 @@ as a term list [coeff, e_1 .. e_k] (Input.w, gkr.rs:21-33; get_multi_ext, rust/s
     terms_from_coeffs(coeff_limbs, k) -> term list                       gkr_terms_from_coeffs (Proof.d / Proof.input_func)
     prove_reference_types(ctx, layers_as_wires, input_w) -> Proof        prove() on exactly those types
     verify_native(circuit, arrays | Proof) -> (accept, layer, check)     gkr_verify (python/gkr.py:202-231 in C++)
+    verify_device(ctx, circuit, arrays | Proof) -> (accept, layer, check)   gkr_verify_device (the same verdicts, sums on the GPU)
 """
 
 import ctypes
@@ -138,3 +139,13 @@ def verify_native(circuit: GKRCircuit, proof, index: int = 0, threads: int = 0):
     if rc:
         raise GkrError(rc, "gkr_verify")
     return bool(accept.value), int(layer.value), int(check.value)
+
+
+def verify_device(ctx, circuit, proof, index=None):
+    """gkr_verify_device: verify_native's verdict with the sums over the gates and the coefficient tables on ctx's GPU.
+    `circuit` is a GKRCircuit or a VerifyHandle of ctx.prepare_verify; `proof` as verify_native takes it.  index=None: a Proof
+    gives its triple, raw arrays give the list of every proof's triple; index=i picks proof i of raw arrays."""
+    out = ctx.verify_batch(circuit, proof)
+    if isinstance(proof, Proof):
+        return out[0]
+    return out if index is None else out[index]

@@ -161,6 +161,34 @@ def _terms_from_coeffs(coeffs, k):
     return [[c] + [(m >> (k - 1 - j)) & 1 for j in range(k)] for m, c in enumerate(vals) if c]
 
 
+class VerifyHandle:
+    """A circuit prepared for the device verifier (gkr_verify_prepare): its gate arrays live on the context's device until
+    close().  Context.prepare_verify makes one; Context.verify_batch takes it any number of times."""
+
+    def __init__(self, ctx, handle, k_list):
+        self._ctx = ctx
+        self._h = handle
+        self.k = list(k_list)
+
+    def close(self):
+        if self._h:
+            N.lib().gkr_verify_circuit_free(self._ctx._h if self._ctx else None, self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            if self._ctx is not None and self._ctx._h:
+                self.close()
+        except Exception:
+            pass
+
+
 class Context:
     """One GPU context (one HIP stream).  Not thread-safe; use one per thread."""
 
@@ -405,6 +433,43 @@ class Context:
         r_p = (ctypes.c_void_p * L)(*[g[2].ctypes.data for g in gates])
         desc = N.CircuitDesc(L, karr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), gt_p, l_p, r_p)
         return desc, (karr, gates, gt_p, l_p, r_p)
+
+    # -- the device verifier (gkr_verify_prepare / gkr_verify_prepared)
+    def prepare_verify(self, circuit: GKRCircuit) -> VerifyHandle:
+        """The circuit's gate arrays to the device, range-checked there (GkrError GKR_ERR_INVALID for a bad gate)."""
+        desc, alive = self._circuit_desc(circuit)
+        h = ctypes.c_void_p()
+        self._check(N.lib().gkr_verify_prepare(self._h, ctypes.byref(desc), ctypes.byref(h)))
+        return VerifyHandle(self, h, circuit.get_k_list())
+
+    def verify_batch(self, handle_or_circuit, proof_or_arrays):
+        """Verdicts of gkr_verify with the O(gates) sums on the GPU.  handle_or_circuit: a VerifyHandle (prepare_verify), or a
+        GKRCircuit (gkr_verify_device: prepare + verify + free).  proof_or_arrays: a Proof, a list of Proofs, or the nine raw
+        output arrays of prove_batch_raw(all_arrays=True) / a prove_many item (first axis = proof; every proof is verified).
+        -> [(accept, failed_layer, failed_check)] in the proofs' order."""
+        if isinstance(proof_or_arrays, Proof):
+            proof_or_arrays = [proof_or_arrays]
+        if len(proof_or_arrays) and all(isinstance(p, Proof) for p in proof_or_arrays):
+            from .dropin import _arrays_of_proof
+            per = [_arrays_of_proof(p) for p in proof_or_arrays]
+            arrays = [np.ascontiguousarray(np.concatenate([a[j] for a in per], axis=0)) for j in range(9)]
+        else:
+            arrays = [np.ascontiguousarray(a) for a in proof_or_arrays]
+        if len(arrays) != 9:
+            raise GkrError(N.GKR_ERR_INVALID, "nine proof arrays expected")
+        B = arrays[0].shape[0]
+        bufs = _proof_bufs(arrays, B)
+        accept = np.zeros(B, dtype=np.int32)
+        layer, check = np.zeros(B, dtype=np.uint32), np.zeros(B, dtype=np.uint32)
+        if isinstance(handle_or_circuit, VerifyHandle):
+            if not handle_or_circuit._h:
+                raise GkrError(N.GKR_ERR_INVALID, "the verify handle is closed")
+            rc = N.lib().gkr_verify_prepared(self._h, handle_or_circuit._h, bufs, ctypes.c_int(B), _ptr(accept), _ptr(layer), _ptr(check))
+        else:
+            desc, alive = self._circuit_desc(handle_or_circuit)
+            rc = N.lib().gkr_verify_device(self._h, ctypes.byref(desc), bufs, ctypes.c_int(B), _ptr(accept), _ptr(layer), _ptr(check))
+        self._check(rc)
+        return [(bool(accept[b]), int(layer[b]), int(check[b])) for b in range(B)]
 
     def prepare_many(self, work, require_zero_output=False):
         """work: [(GKRCircuit, inputs_limbs (B, 2^input_k, 4) uint64)] -> a prepared item list for prove_many_raw:

@@ -582,6 +582,38 @@ enum {
 int  gkr_verify(const gkr_circuit_desc *circuit, const gkr_proof_buf *proof, int threads, int *accept, uint32_t *failed_layer,
                 uint32_t *failed_check);
 
+/* ---- verifier on the device ------------------------------------------------------------------------------------------
+ * The same verdicts as gkr_verify with the three sums that take its time on the GPU: the wiring predicates over every gate,
+ * the coefficient tables at z[0] / z[L], and the tables' canonical scans.  The challenge hashes of a chunk of proofs run on the
+ * context's host threads (gkr_ctx_set_host_threads) while the device works: a verifier reads every challenge out of the proof,
+ * so all layers of all proofs are launched at once and the call synchronises once per chunk.  After that the relations
+ * themselves -- round sums, q, r*, next z, in gkr_verify's order -- are evaluated proof by proof on the calling thread, from the
+ * hashes and the device's sums.  A verifier checks many proofs of one circuit: the gate arrays reach the device once, through
+ * a handle the caller holds.
+ *   gkr_verify_prepare   the argument checks of gkr_verify (depth, k limits, GKR_ERR_DEGENERATE for k[i] == 0, i >= 1), then
+ *                        the gate arrays go to the device, packed to 8 bytes per gate, and every operand and gate type is
+ *                        range-checked there: GKR_ERR_INVALID for a bad gate (no handle is returned; no pass over the gates
+ *                        ever runs for such a circuit).  The handle keeps its own copy of the k list: the caller's arrays need
+ *                        not outlive the call.  It belongs to the context's device.
+ *   gkr_verify_prepared  proofs: `batch` proof buffers in host memory; accept[batch] is required, failed_layer[batch] and
+ *                        failed_check[batch] may be NULL.  For every proof the triple (accept, failed_layer, failed_check) is
+ *                        what gkr_verify returns for that proof and circuit.  ONE difference: a malformed circuit is
+ *                        GKR_ERR_INVALID at prepare time whatever the proof says, where gkr_verify would report a rejection it
+ *                        meets before the bad gate.  The batch is processed in chunks of as many proofs as fit the context
+ *                        option verify_workspace_mb of device workspace (at least one); verdicts do not depend on the chunking.
+ *   gkr_verify_circuit_free   releases a handle (NULL is allowed, for the handle and for the context).
+ *   gkr_verify_device    prepare + verify + free in one call.
+ * The return value is the status of the CALL (GKR_ERR_NO_DEVICE, GKR_ERR_HIP, GKR_ERR_NOMEM as everywhere).  What needs no
+ * device is checked before the device is touched: NULL pointers and batch < 1 (GKR_ERR_INVALID), a NULL ctx
+ * (GKR_ERR_INVALID), a degenerate k list (GKR_ERR_DEGENERATE; decided from the circuit alone, before ctx or a proof is looked at). */
+typedef struct gkr_verify_circuit gkr_verify_circuit;
+int  gkr_verify_prepare(gkr_ctx *ctx, const gkr_circuit_desc *circuit, gkr_verify_circuit **out);
+int  gkr_verify_prepared(gkr_ctx *ctx, const gkr_verify_circuit *vc, const gkr_proof_buf *proofs, int batch,
+                         int *accept, uint32_t *failed_layer, uint32_t *failed_check);
+void gkr_verify_circuit_free(gkr_ctx *ctx, gkr_verify_circuit *vc);
+int  gkr_verify_device(gkr_ctx *ctx, const gkr_circuit_desc *circuit, const gkr_proof_buf *proofs, int batch,
+                       int *accept, uint32_t *failed_layer, uint32_t *failed_check);   /* prepare + verify + free */
+
 /* ---- the proof as input signals of verifier.circom (host only) -----------
  * What the reference does with a Proof right after the path: pad its ragged vectors to the dimensions of
  * the generated verifier component (get_meta aggregator.rs:92-146, modify_proof_for_circom :148-213), print
