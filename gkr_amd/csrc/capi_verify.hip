@@ -6,14 +6,22 @@
 // the reference's order -- stays on the host, in the ONE routine both verifiers share (verify_core.h).
 //
 // A call, per chunk of proofs (as many as fit verify_workspace_mb of device workspace; verdicts do not depend on the chunking):
-//   1. the host threads of the context start on the chunk's challenge hashes (2 k per layer and proof: 3.6 us each on a host
-//      core, hundreds on the device -- they never leave the host);
+//   1. the chunk's challenge hashes (2 k per layer and proof) start.  A lone hash is 3.6 us on a host core and hundreds on the
+//      device, but a verifier's hashes are a flat array of independent jobs, known before the first launch: a chunk of at
+//      least verify_device_hash_min round vectors sends them to the device (k_verify_hash, kernels_verify_hash.hip: eight lanes
+//      per vector) on the context's side stream, forked from the main stream and joined in front of the result copy, so the
+//      long, narrow hash launch runs beside everything in 2.  A smaller chunk hashes on the context's host threads, 16 vectors
+//      a piece, while the device works;
 //   2. the calling thread uploads z, the challenges and the two coefficient tables of every proof, then launches, for ALL
 //      layers and proofs at once (a verifier reads every challenge out of the proof: nothing waits for a hash):
 //      eq(z_i, .) as two half tables, eq(b*, .), eq(c*, .) per layer (launch_eq_table, one launch per table for the chunk), the
 //      wiring pass as ONE launch over (layer, proof) driven by a layer table in device memory plus its second-level sums,
 //      the canonical scans, and the two coefficient-table evaluations; one copy brings every result back;
-//   3. it joins the hashing, synchronises ONCE, and runs the shared relations per proof with the device's values.
+//   3. it joins the hashing (the side stream's event, or the host pool), synchronises ONCE, and runs the shared relations per
+//      proof with the device's values.  Verdicts do not depend on where the hashes ran: both sides fill the same HashSlot array
+//      by the same rule (hash_piece below is that rule; the kernel restates it).
+//
+// gkr_mimc7_multi_hash_device is the same kernel through the same launcher for a caller's own rows.
 //
 // Requirement (verify_core.h states it where the order lives): the device computes from proof elements nobody has checked yet,
 // so some of its values may be garbage; the relations consult a value only after the elements behind it passed their own checks.
@@ -65,6 +73,8 @@ struct HashSlot {
     gkr_fr h;
     uint32_t valid;
 };
+static_assert(sizeof(HashSlot) == sizeof(gkr::VerifyHashSlot) && offsetof(HashSlot, valid) == offsetof(gkr::VerifyHashSlot, valid),
+              "the kernel writes the slots the relations read");
 // one piece of 16 slots; false when none is left (safe to call from many threads: the shape of a SpinPool job)
 bool hash_piece(const gkr_proof_buf* proofs, size_t rounds, size_t n, std::atomic<size_t>& next, HashSlot* slots) {
     const F* cts = host_mimc_constants64();
@@ -91,6 +101,37 @@ bool hash_piece(const gkr_proof_buf* proofs, size_t rounds, size_t n, std::atomi
         }
     }
     return true;
+}
+
+// Smallest number of round vectors in a chunk that are hashed on the device when verify_device_hash_min is 0; 0: never.
+// Measured (profiles/r08, tools/bench_verify.py --hash both --sweep: the demo circuit k = [5,6,7,7,7,7], 68 vectors per proof,
+// MI355X, 16 host CPUs, median (interquartile range) of 20 alternating calls, ms):
+//     vectors      68     136     272     544    1088    4352   17408   69632  278528
+//     host      0.305   0.318   0.499   0.761   1.616   4.826  18.411  70.622 285.474
+//     device    0.483   0.489   0.518   0.563   0.630   1.058   2.960  10.478  59.930
+// From 544 vectors on, at every larger point, the device median is below the host median by more than the sum of the two
+// interquartile ranges (at 272: 0.019 ms in favour of the host); rounded up to a power of two.
+constexpr long long kVerifyDeviceHashMinRows = 1024;
+constexpr size_t kHashRowWords = 24, kHashLaunchRows = (size_t)1 << 24;   // (rows per launch: the grid stays far below 2^31 blocks)
+constexpr double kHashRowBytes = 96.0 + 4.0 + 36.0;                       // a row in, its length, hash and valid word out
+
+bool device_hash_wanted(size_t rows) {
+    long long min_rows = gkr::opt(gkr::OPT_verify_device_hash_min);
+    if (min_rows == 0) min_rows = kVerifyDeviceHashMinRows;
+    return min_rows > 0 && rows >= (size_t)min_rows;
+}
+
+// n rows and their lengths, in device memory -> their slots in device memory, on stream s: THE launcher of both entry points
+int hash_rows_device(gkr_ctx* ctx, const uint32_t* d_rows, const uint32_t* d_len, size_t n, gkr::VerifyHashSlot* d_slots, hipStream_t s) {
+    for (size_t a = 0; a < n; a += kHashLaunchRows) {
+        const size_t m = std::min(kHashLaunchRows, n - a);
+        {
+            Timed t(ctx, "verify_hash", (double)m * kHashRowBytes, s);
+            gkr::launch_verify_hash(d_rows + a * kHashRowWords, d_len + a, (uint32_t)m, ctx->d_cts, d_slots + a, s);
+        }
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return GKR_OK;
 }
 
 // gkr_verify_prepared's provider of the shared relations: what the kernels left, read back (pinned host memory)
@@ -134,7 +175,9 @@ struct Shape {
     size_t out_elems = 0;      // 2 L + 2
     std::vector<size_t> z_off, row_off, last_row;
     size_t bytes_per_proof() const {
-        return (zlen + rounds + n_d + n_in + table_elems + mono_elems + partial_elems + out_elems) * sizeof(Fr) + 2 * sizeof(uint32_t);
+        // (the last term: a round vector, its length and its hash slot, for the chunks whose hashes run on the device)
+        return (zlen + rounds + n_d + n_in + table_elems + mono_elems + partial_elems + out_elems) * sizeof(Fr) + 2 * sizeof(uint32_t) +
+               rounds * (kHashRowWords * sizeof(uint32_t) + sizeof(uint32_t) + sizeof(gkr::VerifyHashSlot));
     }
 };
 Shape shape_of(const std::vector<uint32_t>& k) {
@@ -167,13 +210,24 @@ int verify_chunk(gkr_ctx* ctx, const gkr_verify_circuit* vc, const Shape& sh, co
     const std::vector<uint32_t>& k = vc->k;
     const uint32_t L = sh.L;
     hipStream_t st = ctx->stream;
-    // ---- 1. the hashes start on the context's host pool (its workers take pieces for as long as the session is open; the
-    //         guard closes it on every way out, before `slots` goes)
-    std::vector<HashSlot> slots((size_t)nb * sh.rounds);
-    std::atomic<size_t> next{0};
-    const std::function<bool()> hash_work = [&] { return hash_piece(proofs, sh.rounds, slots.size(), next, slots.data()); };
-    gkr::SpinPool* pool = slots.size() >= 64 ? ctx->host_pool() : nullptr;   // waking the pool is worth some tens of hashes
+    // ---- 1. the hashes start: on the context's host pool (its workers take pieces for as long as the session is open; the
+    //         guard closes it on every way out, before `host_slots` goes), or -- a chunk of enough round vectors -- on the device,
+    //         further down, once the workspaces are there (no piece is left for the pool then)
+    const size_t n_rows = (size_t)nb * sh.rounds;
+    const bool dev_hash = device_hash_wanted(n_rows);
+    std::vector<HashSlot> host_slots(dev_hash ? 0 : n_rows);
+    const HashSlot* slots = host_slots.data();
+    std::atomic<size_t> next{dev_hash ? n_rows : 0};
+    const std::function<bool()> hash_work = [&] { return hash_piece(proofs, sh.rounds, n_rows, next, host_slots.data()); };
+    gkr::SpinPool* pool = !dev_hash && n_rows >= 64 ? ctx->host_pool() : nullptr;   // waking the pool is worth some tens of hashes
     gkr::SpinPool::Session hashing(pool, &hash_work);
+    // the side stream's work is joined on every way out: nothing may still read or write a workspace the next call reuses
+    struct SideJoin {
+        hipStream_t forked = nullptr;
+        ~SideJoin() {
+            if (forked) (void)hipStreamSynchronize(forked);
+        }
+    } side;
     // ---- 2. upload, every launch, one copy back
     const uint32_t pstride = (uint32_t)(sh.zlen + sh.rounds);
     Fr *d_pts, *d_dco, *d_ico, *d_tables, *d_mono, *d_partials, *d_out;
@@ -196,6 +250,30 @@ int verify_chunk(gkr_ctx* ctx, const gkr_verify_circuit* vc, const Shape& sh, co
     HIP_TRY(ctx, ctx->pinned_host("verify_out", out_bytes, reinterpret_cast<void**>(&h_out)));
     HIP_TRY(ctx, ctx->pinned_host("verify_layers", (size_t)L * sizeof(gkr::VerifyLayer), reinterpret_cast<void**>(&h_layers)));
     if (stage) HIP_TRY(ctx, ctx->pinned_host("verify_coeffs", coeff_bytes, reinterpret_cast<void**>(&h_co)));
+    if (dev_hash) {
+        // round vectors, then lengths, in ONE staging buffer and one copy up; the slots come back into pinned memory on the side
+        // stream, whose last event the main stream waits for in front of its own result copy
+        uint32_t *d_hin, *h_hin;
+        gkr::VerifyHashSlot *d_hout, *h_hout;
+        VERIFY_WS(ctx, "verify_hash_in", uint32_t, n_rows * (kHashRowWords + 1), d_hin);
+        VERIFY_WS(ctx, "verify_hash_out", gkr::VerifyHashSlot, n_rows, d_hout);
+        HIP_TRY(ctx, ctx->pinned_host("verify_hash_in", n_rows * (kHashRowWords + 1) * sizeof(uint32_t), reinterpret_cast<void**>(&h_hin)));
+        HIP_TRY(ctx, ctx->pinned_host("verify_hash_out", n_rows * sizeof(gkr::VerifyHashSlot), reinterpret_cast<void**>(&h_hout)));
+        uint32_t* h_hlen = h_hin + n_rows * kHashRowWords;
+        for (uint32_t p = 0; p < nb; ++p) {
+            memcpy(h_hin + (size_t)p * sh.rounds * kHashRowWords, proofs[p].sumcheck_coeffs, sh.rounds * kHashRowWords * sizeof(uint32_t));
+            memcpy(h_hlen + (size_t)p * sh.rounds, proofs[p].sumcheck_len, sh.rounds * sizeof(uint32_t));
+        }
+        HIP_TRY(ctx, ctx->aux_stream(2));
+        HIP_TRY(ctx, hipEventRecord(ctx->aux_events[0], st));             // fork: after whatever the main stream still holds
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux, ctx->aux_events[0], 0));
+        side.forked = ctx->aux;
+        HIP_TRY(ctx, hipMemcpyAsync(d_hin, h_hin, n_rows * (kHashRowWords + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->aux));
+        if (const int rc = hash_rows_device(ctx, d_hin, d_hin + n_rows * kHashRowWords, n_rows, d_hout, ctx->aux)) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(h_hout, d_hout, n_rows * sizeof(gkr::VerifyHashSlot), hipMemcpyDeviceToHost, ctx->aux));
+        HIP_TRY(ctx, hipEventRecord(ctx->aux_events[1], ctx->aux));
+        slots = reinterpret_cast<const HashSlot*>(h_hout);
+    }
     for (uint32_t p = 0; p < nb; ++p) {
         if (sh.zlen) memcpy(h_pts + (size_t)p * pstride, proofs[p].z, sh.zlen * sizeof(Fr));
         memcpy(h_pts + (size_t)p * pstride + sh.zlen, proofs[p].sumcheck_r, sh.rounds * sizeof(Fr));
@@ -250,17 +328,19 @@ int verify_chunk(gkr_ctx* ctx, const gkr_verify_circuit* vc, const Shape& sh, co
         gkr::launch_verify_mono_eval(d_pts, pstride, (uint32_t)sh.z_off[L], kL, d_ico, mono, mono + ((size_t)nb << (kL - kL / 2)), part, d_ev + nb, nb, st);
     }
     HIP_TRY(ctx, hipGetLastError());
+    if (dev_hash) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->aux_events[1], 0));   // join: the slots are back before the results are
     HIP_TRY(ctx, hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
-    // ---- 3. this thread hashes too, then the one synchronisation and the relations
+    // ---- 3. this thread hashes too (the host's pieces, if there are any), then the one synchronisation and the relations
     while (hash_work()) {
     }
     hashing.close();
     HIP_TRY(ctx, hipStreamSynchronize(st));
+    side.forked = nullptr;   // (joined: the main stream waited for the side stream's last event)
     const Fr* h_evals = h_out + (size_t)nb * 2 * L;
     const uint32_t* h_flags = reinterpret_cast<const uint32_t*>(h_out + (size_t)nb * sh.out_elems);
     for (uint32_t p = 0; p < nb; ++p) {
         const Fr evals[2] = {h_evals[p], h_evals[nb + p]};
-        DeviceProvider prov{L, sh.rounds, sh.last_row.data(), slots.data() + (size_t)p * sh.rounds, h_out + (size_t)p * 2 * L, evals, h_flags + 2 * (size_t)p};
+        DeviceProvider prov{L, sh.rounds, sh.last_row.data(), slots + (size_t)p * sh.rounds, h_out + (size_t)p * 2 * L, evals, h_flags + 2 * (size_t)p};
         uint32_t fl = 0, fc = 0;
         const int rc = V::relations(L, k.data(), &proofs[p], prov, &accept[p], &fl, &fc);
         if (rc) return ctx->fail(rc, "gkr_verify_prepared: the relations of a proof could not be evaluated");
@@ -339,6 +419,33 @@ int gkr_verify_prepared(gkr_ctx* ctx, const gkr_verify_circuit* vc, const gkr_pr
         const int rc = verify_chunk(ctx, vc, sh, proofs + b, nb, accept + b, failed_layer ? failed_layer + b : nullptr,
                                     failed_check ? failed_check + b : nullptr);
         if (rc) return rc;
+    }
+    return GKR_OK;
+}
+
+int gkr_mimc7_multi_hash_device(gkr_ctx* ctx, const gkr_fr* rows, const uint32_t* len, size_t n, gkr_fr* out, uint32_t* valid) {
+    if (!ctx || !rows || !len || !out || !valid || n == 0) return GKR_ERR_INVALID;
+    GKR_ENTER(ctx);
+    constexpr size_t kPieceRows = (size_t)1 << 18;   // 25 MiB up, 10 MiB back per piece
+    const size_t cap = std::min(n, kPieceRows);
+    uint32_t *d_in, *h_in;
+    gkr::VerifyHashSlot *d_out, *h_out;
+    VERIFY_WS(ctx, "verify_hash_in", uint32_t, cap * (kHashRowWords + 1), d_in);
+    VERIFY_WS(ctx, "verify_hash_out", gkr::VerifyHashSlot, cap, d_out);
+    HIP_TRY(ctx, ctx->pinned_host("verify_hash_in", cap * (kHashRowWords + 1) * sizeof(uint32_t), reinterpret_cast<void**>(&h_in)));
+    HIP_TRY(ctx, ctx->pinned_host("verify_hash_out", cap * sizeof(gkr::VerifyHashSlot), reinterpret_cast<void**>(&h_out)));
+    for (size_t a = 0; a < n; a += cap) {
+        const size_t m = std::min(cap, n - a);
+        memcpy(h_in, rows + a * 3, m * kHashRowWords * sizeof(uint32_t));
+        memcpy(h_in + m * kHashRowWords, len + a, m * sizeof(uint32_t));
+        HIP_TRY(ctx, hipMemcpyAsync(d_in, h_in, m * (kHashRowWords + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        if (const int rc = hash_rows_device(ctx, d_in, d_in + m * kHashRowWords, m, d_out, ctx->stream)) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(h_out, d_out, m * sizeof(gkr::VerifyHashSlot), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        for (size_t i = 0; i < m; ++i) {
+            memcpy(out[a + i].l, h_out[i].h, 32);
+            valid[a + i] = h_out[i].valid;
+        }
     }
     return GKR_OK;
 }

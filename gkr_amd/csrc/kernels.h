@@ -379,6 +379,20 @@ uint32_t verify_mono_blocks(uint32_t k);
 // batch x verify_mono_blocks(k) elements of scratch.
 void launch_verify_mono_eval(const Fr* points, uint32_t stride, uint32_t first, uint32_t k, const Fr* coeffs, Fr* t_hi, Fr* t_lo, Fr* partials,
                              Fr* out, uint32_t batch, hipStream_t s);
+// ---- the verifier's challenge hashes (kernels_verify_hash.hip) -----------------------------------------------------------------
+// One row's result: the canonical hash as eight little-endian limbs and whether the row was well-formed (36 bytes written, 40
+// with the padding of capi_verify.hip's HashSlot {gkr_fr, uint32_t}, whose layout this is: the relations read what the kernel
+// wrote without a conversion).
+struct VerifyHashSlot {
+    uint32_t h[8];
+    uint32_t valid;
+    uint32_t pad;
+};
+static_assert(sizeof(VerifyHashSlot) == 40, "hash slot");
+// out[i] = {multi_hash(row i's trailing len[i] slots, key 0), 1} for n >= 1 rows of 3 right-aligned slots (24 words per row, the
+// layout of gkr_proof_buf.sumcheck_coeffs); {0, 0} when len[i] is outside 1 .. 3 or a used slot holds an element >= r (an
+// unused leading slot is never looked at).  cts: the 91 round constants in Montgomery form.  Eight lanes per row, one launch.
+void launch_verify_hash(const uint32_t* rows, const uint32_t* len, uint32_t n, const Fr* cts, VerifyHashSlot* out, hipStream_t s);
 
 uint32_t layer_blocks(uint32_t h);
 void launch_layer_round(const Fr* A, const Fr* M, uint32_t h, uint32_t k, uint32_t phase, uint32_t hb, const Fr* Wb,

@@ -471,6 +471,21 @@ class Context:
         self._check(rc)
         return [(bool(accept[b]), int(layer[b]), int(check[b])) for b in range(B)]
 
+    def multi_hash_batch(self, rows, lens):
+        """gkr_mimc7_multi_hash_device: many independent multi_hash calls (key 0) in one device call, the verifier's hash kernel.
+        rows: (n, 3, 4) uint64 limbs, right-aligned as a proof's round vectors are; lens: n lengths.  -> (hashes (n, 4) uint64,
+        valid (n,) uint32): a row whose length is outside 1..3 or whose used slots hold an element >= r has valid 0 and hash 0."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        n = lens.shape[0]
+        if rows.shape != (n, 3, 4):
+            raise GkrError(N.GKR_ERR_INVALID, "rows of shape (n, 3, 4) and n lengths expected")
+        out = np.zeros((n, 4), dtype=np.uint64)
+        valid = np.zeros(n, dtype=np.uint32)
+        N.lib().gkr_mimc7_multi_hash_device.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_size_t] + [ctypes.c_void_p] * 2
+        self._check(N.lib().gkr_mimc7_multi_hash_device(self._h, _ptr(rows), _ptr(lens), ctypes.c_size_t(n), _ptr(out), _ptr(valid)))
+        return out, valid
+
     def prepare_many(self, work, require_zero_output=False):
         """work: [(GKRCircuit, inputs_limbs (B, 2^input_k, 4) uint64)] -> a prepared item list for prove_many_raw:
         circuit descriptions, output arrays and the gkr_prove_item array built once (an aggregation step proves the same

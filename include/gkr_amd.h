@@ -161,7 +161,9 @@ int  gkr_host_accounting_read(double *out_us, size_t count);
  * left alone so that the event records do not show in the wall time being measured.
  * kernel: "mle_multifold" (streaming fold passes on the main stream), "mle_multifold_late" (the small late fold
  * passes on the high-priority stream, overlapping other groups' passes), "mle_sub_sums", "mle_sub_reduce", "mle_pass_small", "mle_fold_plan",
- * "mle_fold_sum", "mle_sum_first", "mle_round_hash", "layer_round", "layer_fold", "layer_round_hash". */
+ * "mle_fold_sum", "mle_sum_first", "mle_round_hash", "layer_round", "layer_fold", "layer_round_hash", "verify_hash" (the
+ * verifier's challenge hashes on the device, gkr_verify_prepared and gkr_mimc7_multi_hash_device: bytes = rows x (96 + 4 + 36);
+ * no launches under this name means the host hashed). */
 int  gkr_ctx_profile(gkr_ctx *ctx, int enable);
 int  gkr_ctx_profile_get(gkr_ctx *ctx, const char *kernel, uint64_t *launches, double *total_ms,
                          double *algorithmic_bytes);
@@ -584,9 +586,12 @@ int  gkr_verify(const gkr_circuit_desc *circuit, const gkr_proof_buf *proof, int
 
 /* ---- verifier on the device ------------------------------------------------------------------------------------------
  * The same verdicts as gkr_verify with the three sums that take its time on the GPU: the wiring predicates over every gate,
- * the coefficient tables at z[0] / z[L], and the tables' canonical scans.  The challenge hashes of a chunk of proofs run on the
- * context's host threads (gkr_ctx_set_host_threads) while the device works: a verifier reads every challenge out of the proof,
- * so all layers of all proofs are launched at once and the call synchronises once per chunk.  After that the relations
+ * the coefficient tables at z[0] / z[L], and the tables' canonical scans.  A verifier reads every challenge out of the proof,
+ * so all layers of all proofs are launched at once and the call synchronises once per chunk.  The challenge hashes of a chunk
+ * of proofs are independent of one another for the same reason: a chunk with at least verify_device_hash_min round vectors
+ * (context option; 0 the measured default, -1 never, 1 always) hashes them on the device too, on a second stream beside the
+ * sums; a smaller chunk hashes on the context's host threads (gkr_ctx_set_host_threads) while the device works.  Verdicts do
+ * not depend on where the hashes ran.  After that the relations
  * themselves -- round sums, q, r*, next z, in gkr_verify's order -- are evaluated proof by proof on the calling thread, from the
  * hashes and the device's sums.  A verifier checks many proofs of one circuit: the gate arrays reach the device once, through
  * a handle the caller holds.
@@ -605,7 +610,9 @@ int  gkr_verify(const gkr_circuit_desc *circuit, const gkr_proof_buf *proof, int
  *   gkr_verify_device    prepare + verify + free in one call.
  * The return value is the status of the CALL (GKR_ERR_NO_DEVICE, GKR_ERR_HIP, GKR_ERR_NOMEM as everywhere).  What needs no
  * device is checked before the device is touched: NULL pointers and batch < 1 (GKR_ERR_INVALID), a NULL ctx
- * (GKR_ERR_INVALID), a degenerate k list (GKR_ERR_DEGENERATE; decided from the circuit alone, before ctx or a proof is looked at). */
+ * (GKR_ERR_INVALID), a degenerate k list (GKR_ERR_DEGENERATE; decided from the circuit alone, before ctx or a proof is looked at).
+ *   gkr_mimc7_multi_hash_device   the verifier's hash kernel for a caller's own round vectors (below).
+ */
 typedef struct gkr_verify_circuit gkr_verify_circuit;
 int  gkr_verify_prepare(gkr_ctx *ctx, const gkr_circuit_desc *circuit, gkr_verify_circuit **out);
 int  gkr_verify_prepared(gkr_ctx *ctx, const gkr_verify_circuit *vc, const gkr_proof_buf *proofs, int batch,
@@ -613,6 +620,12 @@ int  gkr_verify_prepared(gkr_ctx *ctx, const gkr_verify_circuit *vc, const gkr_p
 void gkr_verify_circuit_free(gkr_ctx *ctx, gkr_verify_circuit *vc);
 int  gkr_verify_device(gkr_ctx *ctx, const gkr_circuit_desc *circuit, const gkr_proof_buf *proofs, int batch,
                        int *accept, uint32_t *failed_layer, uint32_t *failed_check);   /* prepare + verify + free */
+/* n independent Mimc7 multi_hash calls (key 0) on the device: rows of 3 slots, right-aligned as in gkr_proof_buf.sumcheck_coeffs;
+ * len[i] in 1..3.  out[i] = multi_hash of row i's trailing len[i] slots, valid[i] = 1; a row whose length is outside 1..3 or whose
+ * used slots hold an element >= r gets valid[i] = 0 and out[i] = 0 (the call still returns GKR_OK: a verifier meets such rows).
+ * Processed in pieces of the device workspace; n >= 1.  NULL pointers, a NULL ctx and n == 0 are GKR_ERR_INVALID before the
+ * device is touched.  The kernel and its launcher are gkr_verify_prepared's ("verify_hash" in the context's profile). */
+int gkr_mimc7_multi_hash_device(gkr_ctx *ctx, const gkr_fr *rows, const uint32_t *len, size_t n, gkr_fr *out, uint32_t *valid);
 
 /* ---- the proof as input signals of verifier.circom (host only) -----------
  * What the reference does with a Proof right after the path: pad its ragged vectors to the dimensions of
