@@ -1,6 +1,7 @@
 // Internals shared by the translation units of the C ABI (gkr_capi.hip: contexts, transcript helpers, self-tests, device
-// memory; capi_mle.hip: the plain sumcheck; capi_layer.hip: the layer sumcheck; capi_prove.hip: whole proofs): the context,
-// its caches and workspaces, profiling brackets, the host transcript's helpers, the hand-off wait.  Not a public header.
+// memory; capi_mle.hip: the plain sumcheck; capi_layer.hip: the layer sumcheck over gate lists; capi_layer_dense.hip: its dense
+// form; capi_prove.hip: whole proofs): the context, its caches and workspaces, profiling brackets, the host transcript's
+// helpers, the hand-off wait.  Not a public header.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <sched.h>
@@ -647,8 +648,14 @@ int run_layer_batch(gkr_ctx* ctx, int batch, int k_i, int k, const uint8_t* d_gt
 // the cached gate lists of one circuit layer, built and validated as a call of its own (a lone circuit builds them inside its
 // first layer sumcheck; a lockstep group needs every member's before its first launch)
 int build_cached_gate_lists(gkr_ctx* ctx, int k_i, int k, const uint8_t* d_gt, const uint32_t* d_l, const uint32_t* d_r, GateLists* cached);
-int run_layer(gkr_ctx* ctx, int k_i, int k, const uint8_t* d_gt, const uint32_t* d_l, const uint32_t* d_r, const gkr_fr* z, const Fr* d_W,
-              gkr_fr* out_coeffs, uint32_t* out_len, gkr_fr* out_r);
+// the host-side argument checks of a layer given as host arrays, and its gate arrays' upload
+int check_layer_args(gkr_ctx* ctx, int k_i, int k_next, const uint8_t* gt, const uint32_t* l, const uint32_t* r, const gkr_fr* z);
+int upload_gates(gkr_ctx* ctx, size_t gates, const uint8_t* gt, const uint32_t* l, const uint32_t* r, DevBuf<uint8_t>& dgt, DevBuf<uint32_t>& dl,
+                 DevBuf<uint32_t>& dr);
+// ---- defined in capi_layer_dense.hip
+// run_layer_batch's other form, for the device transcript: over dense predicate tables, the proofs of a batch one after the other
+int run_layer_dense(gkr_ctx* ctx, int batch, int k_i, int k, const uint8_t* d_gt, const uint32_t* d_l, const uint32_t* d_r, const gkr_fr* z,
+                    const Fr* d_W, gkr_fr* const* out_coeffs, uint32_t* const* out_len, gkr_fr* const* out_r);
 // ---- defined in capi_prove.hip
 void mobius_msb(std::vector<gkr::h64::F>& c, int k);
 void line_restriction(const std::vector<gkr::h64::F>& vals, const std::vector<gkr::h64::F>& coeffs, int k, const gkr_fr* b, const gkr_fr* c,

@@ -53,13 +53,10 @@ void host_pass_scalar(const uint64_t* sums, size_t sums_row_words, int count, in
     }
 }
 
-// The host's share of one product pass of the layer sumcheck, scalar form (the IFMA-lane form is gkr_ifma_prod_pass,
-// mimc_ifma.cpp; same arguments, same results).  Lane k: the 8 x 8 cross-sum matrix m[a][b] (W sub-block a times X
-// sub-block b) and the Y sums sy[a] of its 2^J sub-blocks.  Round t (half = 2^(J-t-1)): with
-//     P_xy = sum_{a < half} m[x half + a][y half + a],   S_x = sum_{a < half} sy[x half + a]
-// the round polynomial is c2 X^2 + lin X + c0,  c0 = P_00 + S_0,  g(1) = P_11 + S_1,  c2 = P_11 - P_10 - P_01 + P_00,
-// lin = g(1) - c0 - c2; the challenge is the hash of [c2, lin, c0] (2 + dep entries); binding the variable folds the
-// matrix along both indices and sy along its one.  At the end the 2^J weights of the fold that binds the J variables.
+// Host transcript, default schedule (kernels.hip "Multi-round passes"): a pass hands the host the
+// 2^J sub-block sums of the current table; the host runs J rounds on them (J <= 5 hashes in a row,
+// eight or sixteen sumchecks per IFMA call), derives the 2^J fold weights, and the next pass binds all J
+// variables at once.  Length rules as in run_mle_batch.
 int run_mle_batch_passes(gkr_ctx* ctx, const Fr* d_tables, int n, int batch, gkr_fr* out_coeffs, uint32_t* out_len,
                          gkr_fr* out_r, const MleTailArgs* tail) {
     using gkr::h64::F;

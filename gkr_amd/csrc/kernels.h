@@ -250,7 +250,6 @@ void launch_copy_rows(const void* src, size_t src_stride_words, void* dst, size_
 // out[proof][g] = eq(points[proof * stride + first ..+nvars), g), nvars <= 28; points may be pinned host memory
 // wu_job / wu_out (both or neither): the launch also leaves W(u) = sum_{i < 2^jp} Wb[i] * weights[i] of every proof (Montgomery;
 // k_prod_c_setup's scalar) in wu_out[proof] -- the wide layers' row pass writes the c-phase's tables with it (WideCFuse)
-struct CPhaseFuse;
 void launch_eq_table(const Fr* points, uint32_t stride, uint32_t first, uint32_t nvars, Fr* out, bool montgomery, uint32_t batch,
                      hipStream_t s, const CPhaseFuse* wu_job = nullptr, Fr* wu_out = nullptr, uint32_t wstride = 0);
 // one launch for a layer's set-up: E_hi (canonical, kh leading coordinates of the proof's point), E_lo (Montgomery, kl

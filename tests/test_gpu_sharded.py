@@ -162,12 +162,71 @@ def _decode(C, L, R, k):
     return proof, from_limbs(R)
 
 
-def test_resident_layer_many_sumchecks_and_bad_gates(ctx):
+@pytest.fixture(scope="module")
+def failure_case():
+    """Inputs and oracle transcripts of _fails_then_proves, computed once for both forms: an (8, 4) layer with one operand out
+    of range and a good one, and two circuits with the k list [3, 4, 4], the first with such an operand in its first layer."""
+    rng = random.Random(1701)
+    bad = _layer(rng, 8, 4)
+    bad.right[17] = 16
+    good = _layer(rng, 8, 4)
+    z, w = [rng.randrange(P) for _ in range(8)], [rng.randrange(P) for _ in range(16)]
+    ks = [3, 4, 4]
+    circuits = []
+    for _ in range(2):
+        circuits.append([([rng.randint(0, 1) for _ in range(1 << ks[i])], [rng.randrange(1 << ks[i + 1]) for _ in range(1 << ks[i])],
+                          [rng.randrange(1 << ks[i + 1]) for _ in range(1 << ks[i])]) for i in range(2)])
+    circuits[0][0][1][5] = 1 << ks[1]
+    inputs = [rng.randrange(P) for _ in range(1 << ks[-1])]
+    assert max(bad.right) >= 1 << 4 and max(circuits[0][0][1]) >= 1 << ks[1]
+    return dict(bad=bad, good=good, z=z, w=w, ref=cdense.sumcheck_layer(8, 4, good.gate_type, good.left, good.right, z, w), ks=ks,
+                circuits=circuits, inputs=inputs, proof=cdense.prove(circuits[1], inputs))
+
+
+def _fails_then_proves(ctx, case):
+    """A gate out of range fails the first sumcheck on a resident layer (and the one after it) with GKR_ERR_INVALID; the same
+    context then proves a good layer of the same size, on resident gates and through prove_sumcheck_opt, as the oracle does.
+    Likewise a whole proof: a circuit the context has not seen is refused for such a gate in its first layer (by the host's
+    check of the gate arrays), and a good circuit with the same k list is proven afterwards."""
+    from gkr_amd import GKRCircuit, GkrError
+    from gkr_amd.field import as_limbs
+    z, w = case["z"], case["w"]
+    gates = parallel.ResidentGates(ctx, 8, 0, *case["bad"].arrays())
+    try:
+        for _ in range(2):
+            with pytest.raises(GkrError):
+                gates.sumcheck_raw(4, as_limbs(z), as_limbs(w))
+    finally:
+        gates.close()
+    good = case["good"]
+    gates = parallel.ResidentGates(ctx, 8, 0, *good.arrays())
+    try:
+        assert _decode(*gates.sumcheck_raw(4, as_limbs(z), as_limbs(w)), 4) == case["ref"]
+    finally:
+        gates.close()
+    assert ctx.prove_sumcheck_opt(good, 4, z, w) == case["ref"]
+    ks = case["ks"]
+    bad_c, good_c = (GKRCircuit([Layer(ks[i], *c[i]) for i in range(2)], ks[-1]) for c in case["circuits"])
+    with pytest.raises(GkrError):
+        ctx.prove(bad_c, case["inputs"])
+    pr, ref = ctx.prove(good_c, case["inputs"]), case["proof"]
+    assert pr.sumcheck_proofs == ref["sumcheck_proofs"] and pr.sumcheck_r == ref["sumcheck_r"]
+    assert pr.q == ref["q"] and pr.z == ref["z"] and pr.r == ref["r"]
+
+
+@pytest.mark.parametrize("form", ["bucket", "wide"])
+def test_resident_layer_many_sumchecks_and_bad_gates(ctx, failure_case, form):
     """gkr_resident_layer_*: the gates and their sorted lists stay on the device; several (z, W) on one layer -- widths
     with passes of one and of several blocks per proof -- equal the oracle, a second next-layer width gets its own lists,
-    a gate out of range fails the first sumcheck (and the one after it) with GKR_ERR_INVALID."""
-    from gkr_amd import GkrError
+    and a context that has failed a call proves correctly afterwards (_fails_then_proves).  `wide`: the failure and what
+    follows it once more on a context of its own whose option gate_groups_min_k = 2 sends these layers through the wide
+    form's item passes, plan and arrival counters."""
     from gkr_amd.field import as_limbs
+    if form == "wide":
+        with Context(0) as wide_ctx:
+            wide_ctx.set_option("gate_groups_min_k", 2)
+            _fails_then_proves(wide_ctx, failure_case)
+        return
     rng = random.Random(1700)
     for k_i, k in ((9, 5), (12, 9), (3, 1), (0, 2)):
         lay = _layer(rng, k_i, k)
@@ -180,16 +239,7 @@ def test_resident_layer_many_sumchecks_and_bad_gates(ctx):
                 assert _decode(C, L, R, k) == cdense.sumcheck_layer(k_i, k, lay.gate_type, lay.left, lay.right, z, w), (k_i, k, trial)
         finally:
             gates.close()
-    lay = _layer(rng, 8, 4)
-    lay.right[17] = 16
-    gates = parallel.ResidentGates(ctx, 8, 0, *lay.arrays())
-    try:
-        z, w = [rng.randrange(P) for _ in range(8)], [rng.randrange(P) for _ in range(16)]
-        for _ in range(2):
-            with pytest.raises(GkrError):
-                gates.sumcheck_raw(4, as_limbs(z), as_limbs(w))
-    finally:
-        gates.close()
+    _fails_then_proves(ctx, failure_case)
 
 
 def test_layer_sumcheck_logical_ranks_wide(ctx):
