@@ -147,7 +147,8 @@ def test_an_operand_out_of_range_is_refused_at_prepare_time(ctx, wide):
 
 def test_large_circuit_in_a_worker():
     """tests/verify_device_worker.py: k = [18, 20, 20] accepted; the last input coefficient flipped is check 9 at layer 2; the
-    last gate of the last layer flipped is rejected -- each equal to gkr_verify's verdict."""
+    last gate of the last layer flipped is rejected -- each equal to gkr_verify's verdict; the last input coefficient set to r is
+    check 2; a right operand of 2^20 at the last gate of layer 1 is refused at prepare time."""
     out = subprocess.run([sys.executable, os.path.join(HERE, "verify_device_worker.py")], env=dict(os.environ), capture_output=True, text=True,
                          timeout=900)
     assert out.returncode == 0 and "OK" in out.stdout, out.stdout + out.stderr

@@ -8,8 +8,10 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from gkr_amd import Context, GKRCircuit, Layer, synth  # noqa: E402
+from gkr_amd import Context, GKRCircuit, GkrError, Layer, synth  # noqa: E402
+from gkr_amd import _native as N  # noqa: E402
 from gkr_amd.dropin import verify_native  # noqa: E402
+from gkr_amd.field import MODULUS  # noqa: E402
 
 
 def main():
@@ -34,6 +36,14 @@ def main():
             print("input coefficient", got, want)
             if got != want or got != [(False, 2, 9)]:
                 bad.append(("input coefficient", got, want))
+            # the last input coefficient set to the modulus r: check 2 at layer 2, from the last thread of the canonical
+            # scan's stride loop (2^20 coefficients over 2048 blocks)
+            flipped = [a.copy() for a in arrs]
+            flipped[8][0, -1] = [(MODULUS >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)]
+            got, want = ctx.verify_batch(handle, flipped), [verify_native(circuit, flipped, index=0)]
+            print("input coefficient = r", got, want)
+            if got != want or got != [(False, 2, 2)]:
+                bad.append(("input coefficient = r", got, want))
         # the last gate of the last layer with the other type: a second handle
         gt = raw[-1][0].copy()
         gt[-1] ^= 1
@@ -43,6 +53,18 @@ def main():
             print("gate type", got, want)
             if got != want or got[0][0]:
                 bad.append(("gate type", got, want))
+        # a right operand of 2^20 at the last gate of layer 1: refused at prepare (the pack kernel's stride loop)
+        right = raw[1][2].copy()
+        right[-1] = 1 << ks[2]
+        broken = GKRCircuit([Layer(ks[0], *raw[0]), Layer(ks[1], raw[1][0], raw[1][1], right)], ks[-1])
+        try:
+            ctx.prepare_verify(broken).close()
+            status = 0
+        except GkrError as e:
+            status = e.status
+        print("operand out of range", status)
+        if status != N.GKR_ERR_INVALID:
+            bad.append(("operand out of range", status, N.GKR_ERR_INVALID))
     print("MISMATCH %r" % bad if bad else "OK")
     return 1 if bad else 0
 
