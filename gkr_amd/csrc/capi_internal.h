@@ -656,6 +656,11 @@ int upload_gates(gkr_ctx* ctx, size_t gates, const uint8_t* gt, const uint32_t* 
 // run_layer_batch's other form, for the device transcript: over dense predicate tables, the proofs of a batch one after the other
 int run_layer_dense(gkr_ctx* ctx, int batch, int k_i, int k, const uint8_t* d_gt, const uint32_t* d_l, const uint32_t* d_r, const gkr_fr* z,
                     const Fr* d_W, gkr_fr* const* out_coeffs, uint32_t* const* out_len, gkr_fr* const* out_r);
+// ---- defined in capi_verify.hip
+// does a chunk of `rows` round vectors hash on the device (option verify_device_hash_min)?  and THE launcher of the hash kernel:
+// n rows of three right-aligned slots and their lengths, in device memory -> their slots in device memory, on stream s
+bool verify_device_hash_wanted(size_t rows);
+int verify_hash_rows_device(gkr_ctx* ctx, const uint32_t* d_rows, const uint32_t* d_len, size_t n, gkr::VerifyHashSlot* d_slots, hipStream_t s);
 // ---- defined in capi_prove.hip
 void mobius_msb(std::vector<gkr::h64::F>& c, int k);
 void line_restriction(const std::vector<gkr::h64::F>& vals, const std::vector<gkr::h64::F>& coeffs, int k, const gkr_fr* b, const gkr_fr* c,

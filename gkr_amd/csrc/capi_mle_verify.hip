@@ -1,0 +1,305 @@
+// The plain sumcheck's verifier and the multilinear evaluation behind it: gkr_mle_eval_batch_device,
+// gkr_sumcheck_mle_verify_batch_device, gkr_sumcheck_mle_verify.
+//
+// verify_sumcheck (python/sumcheck.py:55-70) is O(n) per transcript; what makes a transcript of prove_sumcheck checkable is the
+// relation behind it, g_n(r_n) = T(r_1 .. r_n), one pass over the table.  A verifier reads every challenge out of the transcript,
+// so nothing on the device waits for the host: per chunk of tables (as many as fit verify_workspace_mb of workspace; verdicts
+// do not depend on the chunking)
+//   1. the points (the transcripts' challenges) go up in ONE copy and the evaluation is launched (kernels_mle_eval.hip: a few
+//      set-up launches for the chunk, one streaming read of every table, the second-level sums; one copy back);
+//   2. the chunk's batch x n challenge hashes start: a chunk of at least verify_device_hash_min round vectors sends them to the
+//      device (k_verify_hash through capi_verify.hip's launcher, on the side stream beside the evaluation; the rows are repacked
+//      from the plain sumcheck's two slots to the kernel's three on the way into the staging buffer), a smaller one hashes on
+//      the context's host threads.  Both fill the same slots by the same rule, so verdicts do not depend on where the hashes ran;
+//   3. meanwhile the host threads run everything that needs neither: shape, canonical checks, the round sums and the Horner
+//      steps of every transcript (pre_relations);
+//   4. ONE synchronisation, then per transcript the challenge comparisons and the last relation (finish).
+// The order of the checks is the reference's; a value computed from unchecked elements (a hash of a malformed row, T at a
+// non-canonical point) is never consulted: checks 1 and 2 come first.
+#include <atomic>
+
+#include "capi_internal.h"
+#include "verify_core.h"
+
+namespace {
+
+using gkr::h64::F;
+namespace V = gkr::verify;
+
+struct HashSlot {
+    gkr_fr h;
+    uint32_t valid;
+};
+static_assert(sizeof(HashSlot) == sizeof(gkr::VerifyHashSlot) && offsetof(HashSlot, valid) == offsetof(gkr::VerifyHashSlot, valid),
+              "the kernel writes the slots the relations read");
+constexpr size_t kHashRowWords = 24;          // the hash kernel's rows: three right-aligned slots
+constexpr int kRelPiece = 8, kHashPiece = 16; // transcripts / round vectors per piece of host work
+
+// what the host knows about a transcript before the hashes and the device's value are there
+struct Pre {
+    uint32_t check = 0, round = 0;   // the first failure among checks 1 and 2 (check 0: none)
+    uint32_t sum_round = 0;          // the first round whose sum check fails (n: none)
+    F last = {{0, 0, 0, 0}};         // g_n(r_n)
+    F proved = {{0, 0, 0, 0}};       // g_1(0) + g_1(1)
+};
+
+Pre pre_relations(int n, const gkr_fr* claim, const gkr_fr* coeffs, const uint32_t* len, const gkr_fr* r) {
+    Pre p;
+    p.sum_round = (uint32_t)n;
+    for (int j = 0; j < n; ++j)
+        if (len[j] < 1 || len[j] > 2) {
+            p.check = GKR_VERIFY_SHAPE;
+            p.round = (uint32_t)j;
+            return p;
+        }
+    if (claim && !V::canonical(*claim)) {
+        p.check = GKR_VERIFY_NON_CANONICAL;
+        return p;
+    }
+    for (int j = 0; j < n; ++j) {
+        bool ok = V::canonical(r[j]);
+        for (uint32_t t = 2 - len[j]; t < 2; ++t) ok = ok && V::canonical(coeffs[2 * j + t]);
+        if (!ok) {
+            p.check = GKR_VERIFY_NON_CANONICAL;
+            p.round = (uint32_t)j;
+            return p;
+        }
+    }
+    F running = claim ? V::load(*claim) : F{{0, 0, 0, 0}};
+    for (int j = 0; j < n; ++j) {
+        const gkr_fr* g = coeffs + 2 * j + (2 - len[j]);
+        const F c0 = V::load(g[len[j] - 1]);
+        F sum = gkr::h64::add(c0, c0);                                  // g(0) + g(1) = 2 c0 (+ c1)
+        if (len[j] == 2) sum = gkr::h64::add(sum, V::load(g[0]));
+        if (j == 0) p.proved = sum;
+        if ((j > 0 || claim) && !V::same(sum, running)) {
+            p.sum_round = (uint32_t)j;
+            return p;   // (challenges of earlier rounds are still compared: finish)
+        }
+        running = V::horner(g, (int)len[j], gkr::h64::to_mont(V::load(r[j])));
+    }
+    p.last = running;
+    return p;
+}
+
+// the host's rule for a slot -- the kernel's, restated for rows of two slots
+void hash_slot(const gkr_fr* row, uint32_t len, HashSlot* slot) {
+    slot->valid = 0;
+    if (len < 1 || len > 2) return;
+    F v[2];
+    for (uint32_t t = 0; t < len; ++t) {
+        if (!V::canonical(row[2 - len + t])) return;
+        v[t] = V::load(row[2 - len + t]);
+    }
+    const F h = host_multi_hash(v, (int)len, host_mimc_constants64());
+    memcpy(slot->h.l, h.l, 32);
+    slot->valid = 1;
+}
+
+// the verdict of one transcript from what the host found, its hash slots and the device's T(r)
+int finish(gkr_ctx* ctx, int n, const Pre& p, const HashSlot* slots, const gkr_fr* r, const Fr& value, int* accept, uint32_t* failed_round,
+           uint32_t* failed_check) {
+    uint32_t check = p.check, round = p.round;
+    if (!check) {
+        for (uint32_t j = 0; j < (uint32_t)n && j < p.sum_round && !check; ++j) {
+            if (!slots[j].valid) return ctx->fail(GKR_ERR_HIP, "gkr_sumcheck_mle_verify: no hash for a well-formed round vector");
+            if (memcmp(slots[j].h.l, r[j].l, 32) != 0) {
+                check = GKR_VERIFY_CHALLENGE;
+                round = j;
+            }
+        }
+        if (!check && p.sum_round < (uint32_t)n) {
+            check = GKR_VERIFY_ROUND_SUM;
+            round = p.sum_round;
+        }
+        if (!check && memcmp(p.last.l, &value, 32) != 0) {
+            check = GKR_VERIFY_EVALUATION;
+            round = (uint32_t)n;
+        }
+    }
+    *accept = check == 0 ? 1 : 0;
+    if (failed_round) *failed_round = round;
+    if (failed_check) *failed_check = check;
+    return GKR_OK;
+}
+
+int alloc_status(gkr_ctx* ctx, hipError_t e, const char* what) {
+    if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError();
+        return ctx->fail(GKR_ERR_NOMEM, std::string(what) + ": out of device memory");
+    }
+    return ctx->hip_fail(e, what);
+}
+#define MLEV_WS(ctx, slot, bytes, ptr)                                                              \
+    do {                                                                                            \
+        const hipError_t _e = (ctx)->workspace(slot, (bytes), reinterpret_cast<void**>(&(ptr)));    \
+        if (_e != hipSuccess) return alloc_status(ctx, _e, slot);                                   \
+    } while (0)
+
+// tables of a chunk: what fits verify_workspace_mb (a table's share: its plan, weights, half tables, partials, point, hash rows)
+size_t chunk_tables(int n, int batch, bool hashes) {
+    long long mb = gkr::opt(gkr::OPT_verify_workspace_mb);
+    if (mb <= 0) mb = 2048;
+    const size_t one = gkr::mle_eval_ws_bytes((uint32_t)n, 1) + (size_t)n * sizeof(Fr) + sizeof(Fr) +
+                       (hashes ? (size_t)n * (kHashRowWords * sizeof(uint32_t) + sizeof(uint32_t) + sizeof(gkr::VerifyHashSlot)) : 0);
+    const size_t chunk = ((size_t)mb << 20) / one;
+    return std::max<size_t>(1, std::min<size_t>({chunk, 32768, (size_t)batch}));   // (the table is a grid dimension of the launches)
+}
+
+// the device side of a chunk, queued on the main stream: points up (h_pts: pinned, nb x n), evaluation, values down (h_out: pinned)
+int queue_eval(gkr_ctx* ctx, const Fr* d_tables, int n, uint32_t nb, const Fr* h_pts, Fr* h_out) {
+    Fr *d_pts, *d_out;
+    void* d_ws;
+    MLEV_WS(ctx, "mlev_pts", (size_t)nb * n * sizeof(Fr), d_pts);
+    MLEV_WS(ctx, "mlev_out", (size_t)nb * sizeof(Fr), d_out);
+    MLEV_WS(ctx, "mlev_ws", gkr::mle_eval_ws_bytes((uint32_t)n, nb), d_ws);
+    HIP_TRY(ctx, hipMemcpyAsync(d_pts, h_pts, (size_t)nb * n * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+    {
+        Timed t(ctx, "mle_eval", (double)nb * 32.0 * (double)((size_t)1 << n));
+        gkr::launch_mle_eval(d_tables, (uint32_t)n, nb, d_pts, d_ws, d_out, ctx->stream);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(h_out, d_out, (size_t)nb * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+    return GKR_OK;
+}
+
+int verify_chunk(gkr_ctx* ctx, const Fr* d_tables, int n, uint32_t nb, const gkr_fr* claims, const gkr_fr* coeffs, const uint32_t* len,
+                 const gkr_fr* r, int* accept, uint32_t* failed_round, uint32_t* failed_check, gkr_fr* out_claims) {
+    hipStream_t st = ctx->stream;
+    const size_t n_rows = (size_t)nb * n;
+    const bool dev_hash = verify_device_hash_wanted(n_rows);
+    // ---- the host's share, in pieces: the relations of kRelPiece transcripts, then (host hashing) kHashPiece round vectors
+    std::vector<Pre> pre(nb);
+    std::vector<HashSlot> host_slots(dev_hash ? 0 : n_rows);
+    const HashSlot* slots = host_slots.data();
+    const size_t rel_pieces = (nb + kRelPiece - 1) / kRelPiece, hash_pieces = dev_hash ? 0 : (n_rows + kHashPiece - 1) / kHashPiece;
+    std::atomic<size_t> next{0};
+    const std::function<bool()> host_work = [&] {
+        const size_t a = next.fetch_add(1, std::memory_order_relaxed);
+        if (a < hash_pieces) {   // (the hashes first: they are the long pieces)
+            for (size_t s = a * kHashPiece; s < std::min(n_rows, (a + 1) * kHashPiece); ++s) hash_slot(coeffs + 2 * s, len[s], &host_slots[s]);
+            return true;
+        }
+        if (a < hash_pieces + rel_pieces) {
+            for (size_t b = (a - hash_pieces) * kRelPiece; b < std::min<size_t>(nb, (a - hash_pieces + 1) * kRelPiece); ++b)
+                pre[b] = pre_relations(n, claims ? claims + b : nullptr, coeffs + 2 * b * n, len + b * n, r + b * n);
+            return true;
+        }
+        return false;
+    };
+    // the side stream's work is joined on every way out: nothing may still read or write a workspace the next call reuses
+    struct SideJoin {
+        hipStream_t forked = nullptr;
+        ~SideJoin() {
+            if (forked) (void)hipStreamSynchronize(forked);
+        }
+    } side;
+    // ---- the device's share: hashes on the side stream, the evaluation on the main stream
+    Fr *h_pts, *h_out;
+    HIP_TRY(ctx, ctx->pinned_host("mlev_pts", n_rows * sizeof(Fr), reinterpret_cast<void**>(&h_pts)));
+    HIP_TRY(ctx, ctx->pinned_host("mlev_out", (size_t)nb * sizeof(Fr), reinterpret_cast<void**>(&h_out)));
+    if (dev_hash) {
+        uint32_t *d_hin, *h_hin;
+        gkr::VerifyHashSlot *d_hout, *h_hout;
+        MLEV_WS(ctx, "mlev_hash_in", n_rows * (kHashRowWords + 1) * sizeof(uint32_t), d_hin);
+        MLEV_WS(ctx, "mlev_hash_out", n_rows * sizeof(gkr::VerifyHashSlot), d_hout);
+        HIP_TRY(ctx, ctx->pinned_host("mlev_hash_in", n_rows * (kHashRowWords + 1) * sizeof(uint32_t), reinterpret_cast<void**>(&h_hin)));
+        HIP_TRY(ctx, ctx->pinned_host("mlev_hash_out", n_rows * sizeof(gkr::VerifyHashSlot), reinterpret_cast<void**>(&h_hout)));
+        for (size_t s = 0; s < n_rows; ++s) {   // two slots -> the kernel's three; the leading one is never looked at for len <= 2
+            memset(h_hin + s * kHashRowWords, 0, 32);
+            memcpy(h_hin + s * kHashRowWords + 8, coeffs + 2 * s, 64);
+        }
+        memcpy(h_hin + n_rows * kHashRowWords, len, n_rows * sizeof(uint32_t));
+        HIP_TRY(ctx, ctx->aux_stream(2));
+        HIP_TRY(ctx, hipEventRecord(ctx->aux_events[0], st));             // fork: after whatever the main stream still holds
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux, ctx->aux_events[0], 0));
+        side.forked = ctx->aux;
+        HIP_TRY(ctx, hipMemcpyAsync(d_hin, h_hin, n_rows * (kHashRowWords + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->aux));
+        if (const int rc = verify_hash_rows_device(ctx, d_hin, d_hin + n_rows * kHashRowWords, n_rows, d_hout, ctx->aux)) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(h_hout, d_hout, n_rows * sizeof(gkr::VerifyHashSlot), hipMemcpyDeviceToHost, ctx->aux));
+        HIP_TRY(ctx, hipEventRecord(ctx->aux_events[1], ctx->aux));
+        slots = reinterpret_cast<const HashSlot*>(h_hout);
+    }
+    memcpy(h_pts, r, n_rows * sizeof(Fr));
+    if (const int rc = queue_eval(ctx, d_tables, n, nb, h_pts, h_out)) return rc;
+    if (dev_hash) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->aux_events[1], 0));   // join: the main stream's end is the side stream's too
+    // ---- the host works while the device streams (waking the pool is worth some tens of hashes or transcripts)
+    {
+        gkr::SpinPool* pool = hash_pieces + rel_pieces >= 8 ? ctx->host_pool() : nullptr;
+        gkr::SpinPool::Session session(pool, &host_work);
+        while (host_work()) {
+        }
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    side.forked = nullptr;
+    for (uint32_t b = 0; b < nb; ++b) {
+        const int rc = finish(ctx, n, pre[b], slots + (size_t)b * n, r + (size_t)b * n, h_out[b], &accept[b], failed_round ? failed_round + b : nullptr,
+                              failed_check ? failed_check + b : nullptr);
+        if (rc) return rc;
+        if (out_claims) {
+            memset(&out_claims[b], 0, sizeof(gkr_fr));
+            if (!pre[b].check) memcpy(out_claims[b].l, pre[b].proved.l, 32);
+        }
+    }
+    return GKR_OK;
+}
+
+int verify_batch(gkr_ctx* ctx, const Fr* d_tables, int n, int batch, const gkr_fr* claims, const gkr_fr* coeffs, const uint32_t* len,
+                 const gkr_fr* r, int* accept, uint32_t* failed_round, uint32_t* failed_check, gkr_fr* out_claims) {
+    const size_t chunk = chunk_tables(n, batch, true);
+    for (size_t b = 0; b < (size_t)batch; b += chunk) {
+        const uint32_t nb = (uint32_t)std::min(chunk, (size_t)batch - b);
+        const int rc = verify_chunk(ctx, d_tables + (b << n), n, nb, claims ? claims + b : nullptr, coeffs + 2 * b * n, len + b * n, r + b * n,
+                                    accept + b, failed_round ? failed_round + b : nullptr, failed_check ? failed_check + b : nullptr,
+                                    out_claims ? out_claims + b : nullptr);
+        if (rc) return rc;
+    }
+    return GKR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gkr_mle_eval_batch_device(gkr_ctx* ctx, const void* d_tables, int n, int batch, const gkr_fr* points, gkr_fr* out) {
+    // (plain returns: these are decided before the context is looked at)
+    if (!ctx || !d_tables || !points || !out || batch < 1 || n < 1 || n > 30) return GKR_ERR_INVALID;
+    if (!all_canonical(points, (size_t)batch * n)) return ctx->fail(GKR_ERR_NON_CANONICAL, "coordinate of a point >= r");
+    GKR_ENTER(ctx);
+    const size_t chunk = chunk_tables(n, batch, false);
+    for (size_t b = 0; b < (size_t)batch; b += chunk) {
+        const uint32_t nb = (uint32_t)std::min(chunk, (size_t)batch - b);
+        Fr *h_pts, *h_out;
+        HIP_TRY(ctx, ctx->pinned_host("mlev_pts", (size_t)nb * n * sizeof(Fr), reinterpret_cast<void**>(&h_pts)));
+        HIP_TRY(ctx, ctx->pinned_host("mlev_out", (size_t)nb * sizeof(Fr), reinterpret_cast<void**>(&h_out)));
+        memcpy(h_pts, points + b * n, (size_t)nb * n * sizeof(Fr));
+        if (const int rc = queue_eval(ctx, static_cast<const Fr*>(d_tables) + (b << n), n, nb, h_pts, h_out)) return rc;
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        memcpy(out + b, h_out, (size_t)nb * sizeof(Fr));
+    }
+    return GKR_OK;
+}
+
+int gkr_sumcheck_mle_verify_batch_device(gkr_ctx* ctx, const void* d_tables, int n, int batch, const gkr_fr* claims, const gkr_fr* coeffs,
+                                         const uint32_t* len, const gkr_fr* r, int* accept, uint32_t* failed_round, uint32_t* failed_check,
+                                         gkr_fr* out_claims) {
+    if (!ctx || !d_tables || !coeffs || !len || !r || !accept || batch < 1 || n < 2 || n > 30) return GKR_ERR_INVALID;
+    GKR_ENTER(ctx);
+    return verify_batch(ctx, static_cast<const Fr*>(d_tables), n, batch, claims, coeffs, len, r, accept, failed_round, failed_check, out_claims);
+}
+
+int gkr_sumcheck_mle_verify(gkr_ctx* ctx, const gkr_fr* table, int n, const gkr_fr* claim, const gkr_fr* coeffs, const uint32_t* len,
+                            const gkr_fr* r, int* accept, uint32_t* failed_round, uint32_t* failed_check) {
+    if (!ctx || !table || !coeffs || !len || !r || !accept || n < 2 || n > 30) return GKR_ERR_INVALID;
+    GKR_ENTER(ctx);
+    const size_t count = (size_t)1 << n;
+    DevBuf<Fr> d;
+    {
+        const hipError_t e = d.alloc(count);
+        if (e != hipSuccess) return alloc_status(ctx, e, "gkr_sumcheck_mle_verify: the table");
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(d.p, table, count * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+    return verify_batch(ctx, d.p, n, 1, claim, coeffs, len, r, accept, failed_round, failed_check, nullptr);
+}
+
+}  // extern "C"

@@ -352,6 +352,14 @@ int verify_chunk(gkr_ctx* ctx, const gkr_verify_circuit* vc, const Shape& sh, co
 
 }  // namespace
 
+// the plain sumcheck's verifier (capi_mle_verify.hip) hashes its round vectors through the same threshold and the same launcher
+namespace gkr_host {
+bool verify_device_hash_wanted(size_t rows) { return device_hash_wanted(rows); }
+int verify_hash_rows_device(gkr_ctx* ctx, const uint32_t* d_rows, const uint32_t* d_len, size_t n, gkr::VerifyHashSlot* d_slots, hipStream_t s) {
+    return hash_rows_device(ctx, d_rows, d_len, n, d_slots, s);
+}
+}  // namespace gkr_host
+
 extern "C" {
 
 int gkr_verify_prepare(gkr_ctx* ctx, const gkr_circuit_desc* circuit, gkr_verify_circuit** out) {

@@ -393,6 +393,19 @@ static_assert(sizeof(VerifyHashSlot) == 40, "hash slot");
 // unused leading slot is never looked at).  cts: the 91 round constants in Montgomery form.  Eight lanes per row, one launch.
 void launch_verify_hash(const uint32_t* rows, const uint32_t* len, uint32_t n, const Fr* cts, VerifyHashSlot* out, hipStream_t s);
 
+// ---- multilinear evaluation at a point (kernels_mle_eval.hip) ---------------------------------------------------------------------
+// The streaming matrix-core form binds five variables per pass over 2^(n-5) outputs in wave tiles of 64: it applies from
+// kMleEvalMfmaValidN on.  From kMleEvalMfmaMinN on it is used (option mle_eval_mfma_min_n overrides; below, one block per table
+// does the whole sum: one launch instead of six, and a table of 2^12 entries is 16 entries per thread).  Above kMleEvalSmallMaxN the
+// streaming form is used whatever the option says: one block walking a table of gigabytes would hold the device for minutes.
+constexpr uint32_t kMleEvalMfmaValidN = 11, kMleEvalMfmaMinN = 13, kMleEvalSmallMaxN = 24;
+bool mle_eval_uses_mfma(uint32_t n);
+uint32_t mle_eval_blocks(uint32_t n, uint32_t batch);      // blocks per table of the streaming form
+size_t mle_eval_ws_bytes(uint32_t n, uint32_t batch);      // device workspace of one launch_mle_eval
+// out[b] = sum_i eq(points[b * n ..+n), i) tables[(b << n) + i] (canonical) for `batch` tables of 2^n entries, 1 <= n <= 30;
+// points: batch x n canonical elements in device memory, variable 1 = most significant index bit.  ws: mle_eval_ws_bytes().
+void launch_mle_eval(const Fr* tables, uint32_t n, uint32_t batch, const Fr* points, void* ws, Fr* out, hipStream_t s);
+
 uint32_t layer_blocks(uint32_t h);
 void launch_layer_round(const Fr* A, const Fr* M, uint32_t h, uint32_t k, uint32_t phase, uint32_t hb, const Fr* Wb,
                         const Fr* Wc, uint32_t nblk, LayerPartial* partials, LayerBatch lb, hipStream_t s);

@@ -163,7 +163,7 @@ __device__ __forceinline__ Fr mf_finish(const mf_v16i& a0, const mf_v16i& a1) {
     return mf_reduce_274(l);
 }
 
-// One pass for a (sumcheck, chunk) block: same contract as k_mle_multifold (kernels.hip).  256 threads = 4 waves;
+// One pass over a (sumcheck, chunk) block's sources: same contract as k_mle_multifold (kernels.hip).  256 threads = 4 waves;
 // a wave turns 64 consecutive output entries per iteration (two 32-entry MFMA tiles); (end - begin) % 64 == 0.
 // The 2^JIN source entries of an output are taken in stages of (at most) eight k-steps: the loads of the next
 // stage (of this or the next iteration) are issued before the current stage's arithmetic, so a wave keeps
@@ -171,10 +171,12 @@ __device__ __forceinline__ Fr mf_finish(const mf_v16i& a0, const mf_v16i& a1) {
 // in registers for JIN <= 2), unused otherwise.
 // `rot`: each block starts at its own iteration and wraps around, so the blocks of a launch do not walk
 // their chunks in step.
-template <int JIN>
-__device__ __forceinline__ void mfma_multifold_block(const Fr* __restrict__ s, Fr* __restrict__ d, uint32_t S,
-                                                     const MfmaFoldPlan* __restrict__ plan, uint32_t begin, uint32_t end,
-                                                     uint32_t rot, Acc<9>& acc_out, unsigned char* lds) {
+// `sink(e0, h, c, y)`: what becomes of a finished output -- y is entry e0 + 32 h + c of the folded table, 32 h + c = the lane's place
+// in the wave's 64-entry tile (h its half, c its column), e0 (a multiple of 64 past `begin`) wave-uniform.  The fold pass stores it (mfma_multifold_block below);
+// the multilinear evaluation (kernels_mle_eval.hip) multiplies it into a sum and stores nothing.
+template <int JIN, class Sink>
+__device__ __forceinline__ void mfma_multifold_stream(const Fr* __restrict__ s, uint32_t S, const MfmaFoldPlan* __restrict__ plan,
+                                                      uint32_t begin, uint32_t end, uint32_t rot, unsigned char* lds, Sink&& sink) {
     constexpr int NB = 1 << JIN;
     constexpr int KS = NB < 8 ? NB : 8;     // k-steps per stage
     constexpr int NST = NB / KS;            // stages per iteration: 1, 2 or 4
@@ -228,14 +230,7 @@ __device__ __forceinline__ void mfma_multifold_block(const Fr* __restrict__ s, F
             a1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(w, (mf_v4i)f1, a1, 0, 0, 0);
         }
     };
-    auto store_entry = [&](uint32_t e0, const mf_v16i& a0, const mf_v16i& a1) {
-        const Fr y = mf_finish(a0, a1);
-        mf_v4u* o = reinterpret_cast<mf_v4u*>(d + e0 + 32u * h + c);
-        const mf_v4u y0 = {y.l[0], y.l[1], y.l[2], y.l[3]}, y1 = {y.l[4], y.l[5], y.l[6], y.l[7]};
-        __builtin_nontemporal_store(y0, o);
-        __builtin_nontemporal_store(y1, o + 1);
-        acc_add_fr(acc_out, y);
-    };
+    auto store_entry = [&](uint32_t e0, const mf_v16i& a0, const mf_v16i& a1) { sink(e0, h, c, mf_finish(a0, a1)); };
 
     const uint32_t span = end - begin;
     const uint32_t iters = (span + 255u) / 256u;
@@ -296,6 +291,20 @@ __device__ __forceinline__ void mfma_multifold_block(const Fr* __restrict__ s, F
             e0 = e1;
         }
     }
+}
+
+// the fold pass: every output is stored (non-temporal) and added to the block's sum of outputs
+template <int JIN>
+__device__ __forceinline__ void mfma_multifold_block(const Fr* __restrict__ s, Fr* __restrict__ d, uint32_t S,
+                                                     const MfmaFoldPlan* __restrict__ plan, uint32_t begin, uint32_t end,
+                                                     uint32_t rot, Acc<9>& acc_out, unsigned char* lds) {
+    mfma_multifold_stream<JIN>(s, S, plan, begin, end, rot, lds, [&](uint32_t e0, uint32_t h, uint32_t c, const Fr& y) {
+        mf_v4u* o = reinterpret_cast<mf_v4u*>(d + e0 + 32u * h + c);
+        const mf_v4u y0 = {y.l[0], y.l[1], y.l[2], y.l[3]}, y1 = {y.l[4], y.l[5], y.l[6], y.l[7]};
+        __builtin_nontemporal_store(y0, o);
+        __builtin_nontemporal_store(y1, o + 1);
+        acc_add_fr(acc_out, y);
+    });
 }
 
 #endif

@@ -54,8 +54,10 @@ namespace gkr {
     X(prove_many_lockstep, "prove_many_lockstep", "GKR_PROVE_MANY_LOCKSTEP", 1, "gkr_prove_many: items whose circuits share a k list advance in lockstep, one launch per pass for the group (0: one chain per item)") \
     X(lockstep_max_proofs, "lockstep_max_proofs", "GKR_LOCKSTEP_MAX_PROOFS", 0, "most proofs one lockstep group may hold (0: 32 -- beyond that independent chains overlap better)") \
     /* ---- device verifier (gkr_verify_prepared, capi_verify.hip) ---- */                                                            \
-    X(verify_workspace_mb, "verify_workspace_mb", "GKR_VERIFY_WORKSPACE_MB", 0, "gkr_verify_prepared: MiB of device workspace a chunk of proofs may take (0: 2048; a chunk is never less than one proof)") \
-    X(verify_device_hash_min, "verify_device_hash_min", "GKR_VERIFY_DEVICE_HASH_MIN", 0, "gkr_verify_prepared: smallest number of round vectors in a chunk whose challenge hashes run on the device (0: the measured default, capi_verify.hip kVerifyDeviceHashMinRows; -1: never, the host threads hash; 1: always)")
+    X(verify_workspace_mb, "verify_workspace_mb", "GKR_VERIFY_WORKSPACE_MB", 0, "gkr_verify_prepared / gkr_sumcheck_mle_verify*: MiB of device workspace a chunk of proofs may take (0: 2048; a chunk is never less than one proof)") \
+    X(verify_device_hash_min, "verify_device_hash_min", "GKR_VERIFY_DEVICE_HASH_MIN", 0, "gkr_verify_prepared / gkr_sumcheck_mle_verify*: smallest number of round vectors in a chunk whose challenge hashes run on the device (0: the measured default, capi_verify.hip kVerifyDeviceHashMinRows; -1: never, the host threads hash; 1: always)") \
+    /* ---- multilinear evaluation / plain-sumcheck verifier (gkr_mle_eval_batch_device, capi_mle_verify.hip) ---- */                     \
+    X(mle_eval_mfma_min_n, "mle_eval_mfma_min_n", "GKR_MLE_EVAL_MFMA_MIN_N", 0, "gkr_mle_eval_batch_device / gkr_sumcheck_mle_verify*: smallest n whose tables are evaluated by the streaming matrix-core kernel (0: the default, kernels.h kMleEvalMfmaMinN; never below 11, where the kernel starts to apply; above 24: the one-block kernel up to n = 24, its largest)")
 
 enum OptionId : int {
 #define GKR_OPT_ENUM(id, name, env, def, doc) OPT_##id,

@@ -22,7 +22,7 @@ from .field import from_limbs, to_limbs
 from .prover import GKRCircuit, GkrError, Layer, Proof, _proof_bufs, _ptr
 
 VERIFY_CHECKS = {0: "ok", 1: "shape", 2: "non-canonical element", 3: "z[0] != 0", 4: "round sum", 5: "round challenge", 6: "final claim",
-                 7: "r*", 8: "next z", 9: "input layer"}
+                 7: "r*", 8: "next z", 9: "input layer", 10: "table evaluation (plain sumcheck)"}
 
 
 def _rows(vectors: Sequence[Sequence[int]], width: int) -> np.ndarray:

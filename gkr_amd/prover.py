@@ -345,6 +345,60 @@ class Context:
         C, L, R = self.sumcheck_mle_raw(as_limbs(table), v)
         return [from_limbs(C[j])[2 - int(L[j]):] for j in range(v)], from_limbs(R)
 
+    # -- the plain sumcheck's verifier (verify_sumcheck, python/sumcheck.py:55-70, plus g_n(r_n) = T(r)) and the evaluation behind it
+    def mle_eval_batch_device(self, d_tables, n, batch, points):
+        """gkr_mle_eval_batch_device: the multilinear extension of each of `batch` resident tables of 2^n entries at its own point.
+        points: (batch, n, 4) uint64 limbs (canonical; GkrError GKR_ERR_NON_CANONICAL otherwise), variable 1 = most significant
+        index bit.  -> (batch, 4) uint64 limbs."""
+        points = np.ascontiguousarray(points, dtype=np.uint64)
+        if points.shape != (batch, n, 4):
+            raise GkrError(N.GKR_ERR_INVALID, "points of shape (batch, n, 4) expected")
+        out = np.zeros((batch, 4), dtype=np.uint64)
+        self._check(N.lib().gkr_mle_eval_batch_device(self._h, d_tables, ctypes.c_int(n), ctypes.c_int(batch), _ptr(points), _ptr(out)))
+        return out
+
+    def verify_sumcheck_batch_device(self, d_tables, n, batch, C, L, R, claims=None):
+        """gkr_sumcheck_mle_verify_batch_device on the arrays sumcheck_mle_batch_device returned (C (batch, n, 2, 4), L (batch, n),
+        R (batch, n, 4)); claims: (batch, 4) uint64 limbs or None (round 0's sum check is skipped, the proven sums are returned).
+        -> (accept (batch,) bool, failed_round (batch,) uint32, failed_check (batch,) uint32, claims (batch, 4) uint64)."""
+        C = np.ascontiguousarray(C, dtype=np.uint64)
+        L = np.ascontiguousarray(L, dtype=np.uint32)
+        R = np.ascontiguousarray(R, dtype=np.uint64)
+        if C.shape != (batch, n, 2, 4) or L.shape != (batch, n) or R.shape != (batch, n, 4):
+            raise GkrError(N.GKR_ERR_INVALID, "transcript arrays do not match (batch, n)")
+        if claims is not None:
+            claims = np.ascontiguousarray(claims, dtype=np.uint64)
+            if claims.shape != (batch, 4):
+                raise GkrError(N.GKR_ERR_INVALID, "claims of shape (batch, 4) expected")
+        accept = np.zeros(batch, dtype=np.int32)
+        rnd, check = np.zeros(batch, dtype=np.uint32), np.zeros(batch, dtype=np.uint32)
+        out = np.zeros((batch, 4), dtype=np.uint64)
+        self._check(N.lib().gkr_sumcheck_mle_verify_batch_device(
+            self._h, d_tables, ctypes.c_int(n), ctypes.c_int(batch), _ptr(claims) if claims is not None else None, _ptr(C), _ptr(L), _ptr(R),
+            _ptr(accept), _ptr(rnd), _ptr(check), _ptr(out)))
+        return accept.astype(bool), rnd, check, out
+
+    def verify_sumcheck(self, table, proof, r, claim=None):
+        """gkr_sumcheck_mle_verify on what prove_sumcheck returned: proof[j] the round vector (one or two coefficients, highest
+        degree first), r the challenges; claim: the sum the transcript is to prove, or None.  -> (accept, failed_round, failed_check)."""
+        limbs = as_limbs(table)
+        n = len(proof)
+        if n < 1 or limbs.shape[0] != 1 << n or len(r) != n:
+            raise GkrError(N.GKR_ERR_INVALID, "a table of 2^n entries, n round vectors and n challenges expected")
+        C = np.zeros((n, 2, 4), dtype=np.uint64)
+        L = np.zeros(n, dtype=np.uint32)
+        for j, g in enumerate(proof):
+            if not 1 <= len(g) <= 2:
+                raise GkrError(N.GKR_ERR_INVALID, "a round vector has one or two coefficients")
+            L[j] = len(g)
+            C[j, 2 - len(g):] = to_limbs(g)
+        R = to_limbs(r)
+        cl = to_limbs([claim]) if claim is not None else None
+        accept, rnd, check = ctypes.c_int(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+        self._check(N.lib().gkr_sumcheck_mle_verify(self._h, _ptr(limbs), ctypes.c_int(n), _ptr(cl) if cl is not None else None, _ptr(C), _ptr(L),
+                                                    _ptr(R), ctypes.byref(accept), ctypes.byref(rnd), ctypes.byref(check)))
+        return bool(accept.value), int(rnd.value), int(check.value)
+
     # -- layer sumcheck (prove_sumcheck_opt, sumcheck.rs:36-156)
     def sumcheck_layer_raw(self, layer: Layer, k_next, z, W):
         gt, l, r = layer.arrays()

@@ -73,6 +73,27 @@ def verify_sumcheck(claim: int, rounds: List[List[int]], challenges: List[int]):
     return True, expected
 
 
+def mle_eval(table: List[int], point: List[int]) -> int:
+    """The multilinear extension of a table of 2^n values at a point, variable 1 = most significant index bit: n folds
+    T'[i] = T[i] + r (T[i + half] - T[i]) (partial_eval_i, rust/src/gkr/poly.rs:160-179)."""
+    t = [x % P for x in table]
+    if len(t) != 1 << len(point):
+        raise ValueError("a table of 2^n values and a point of n coordinates expected")
+    for r in point:
+        half = len(t) // 2
+        t = [(t[i] + r * (t[i + half] - t[i])) % P for i in range(half)]
+    return t[0]
+
+
+def verify_sumcheck_table(table: List[int], rounds: List[List[int]], challenges: List[int], claim=None) -> bool:
+    """What Context.verify_sumcheck decides on the device, on plain integers: python/sumcheck.py:55-70 on the claim (the first
+    round vector's own sum when none is given) and the relation that ties the transcript to its table, g_n(r_n) = T(r_1 .. r_n)."""
+    if claim is None:
+        claim = eval_univariate(rounds[0], 0) + eval_univariate(rounds[0], 1)
+    ok, last = verify_sumcheck(claim, rounds, challenges)
+    return ok and last == mle_eval(table, [r % P for r in challenges])
+
+
 def verify(proof: Proof, circuit: GKRCircuit) -> bool:
     """python/gkr.py:202-231 on the Rust-shaped proof."""
     L = circuit.depth()

@@ -283,6 +283,41 @@ int  gkr_sumcheck_mle(gkr_ctx *ctx, const gkr_fr *table, int n, gkr_fr *out_coef
 int  gkr_sumcheck_mle_batch_device(gkr_ctx *ctx, const void *d_tables, int n, int batch,
                                    gkr_fr *out_coeffs, uint32_t *out_len, gkr_fr *out_r);
 
+/* ---- the plain sumcheck's verifier: verify_sumcheck, python/sumcheck.py:55-70, and the relation behind it -------------
+ * A transcript of prove_sumcheck proves "sum of the table = claim" only together with g_n(r_n) = T~(r_1 .. r_n), the table's
+ * multilinear extension at the challenges: one read of the table (32 * 2^n bytes, where the prover's default schedule moves
+ * 66 * 2^n), with every challenge known up front. */
+
+/* W~(point) for `batch` tables resident in device memory (layout of gkr_sumcheck_mle_batch_device: table b at
+ * d_tables + b * 2^n elements, variable 1 = most significant index bit).  points: batch x n canonical elements
+ * (host), each table its own point; out: batch elements (host).  1 <= n <= 30, batch >= 1.  Tables are not modified. */
+int gkr_mle_eval_batch_device(gkr_ctx *ctx, const void *d_tables, int n, int batch, const gkr_fr *points, gkr_fr *out);
+
+/* Verifier of gkr_sumcheck_mle_batch_device's transcripts (python/sumcheck.py:55-70 plus the final evaluation).
+ * coeffs / len / r: exactly the arrays the prover wrote (batch x n rows of 2 right-aligned slots, len in {1,2}, batch x n
+ * challenges).  claims: batch elements or NULL.
+ * accept[batch] required; failed_round / failed_check / out_claims may be NULL.
+ * Per transcript, in this order, the first failure reported (failed_check: the GKR_VERIFY_* values below):
+ *   1. GKR_VERIFY_SHAPE           some len[j] outside 1..2; failed_round = the first such j
+ *   2. GKR_VERIFY_NON_CANONICAL   a used slot, an r_j or the claim >= r (unused slots are never read); failed_round = the
+ *                                 first such row, 0 for the claim
+ *   3. for j = 0 .. n-1:  GKR_VERIFY_ROUND_SUM  g_j(0) + g_j(1) != the running claim;  GKR_VERIFY_CHALLENGE  r_j !=
+ *      multi_hash(used slots of row j, key 0);  the running claim becomes g_j(r_j)
+ *   4. GKR_VERIFY_EVALUATION      g_n(r_n) != T~(r_1 .. r_n); failed_round = n
+ * claims == NULL: round 0's sum check is skipped.  out_claims[b] = g_1(0) + g_1(1), the sum the transcript proves, for every
+ * transcript that passes checks 1 and 2, zero for the others.
+ * The return value is the status of the CALL, not the verdict: NULL ctx / required pointer, batch < 1, n outside 2..30 are
+ * GKR_ERR_INVALID before a device is touched (gkr_mle_eval_batch_device: n outside 1..30; a point's coordinate >= r is
+ * GKR_ERR_NON_CANONICAL).  Table entries are read as integers modulo r.  Processed in chunks of verify_workspace_mb of device
+ * workspace; a chunk of verify_device_hash_min round vectors and more hashes them on the device; verdicts depend on neither. */
+int gkr_sumcheck_mle_verify_batch_device(gkr_ctx *ctx, const void *d_tables, int n, int batch, const gkr_fr *claims,
+                                         const gkr_fr *coeffs, const uint32_t *len, const gkr_fr *r,
+                                         int *accept, uint32_t *failed_round, uint32_t *failed_check, gkr_fr *out_claims);
+
+/* one table in host memory: upload + the call above with batch 1 */
+int gkr_sumcheck_mle_verify(gkr_ctx *ctx, const gkr_fr *table, int n, const gkr_fr *claim, const gkr_fr *coeffs,
+                            const uint32_t *len, const gkr_fr *r, int *accept, uint32_t *failed_round, uint32_t *failed_check);
+
 /* ---- GKR layer sumcheck: prove_sumcheck_opt, sumcheck.rs:36-44 ----------- */
 /* Layer i has 2^k_i gates; gate g is add (0) or mult (1) of entries left[g],
  * right[g] of layer i+1, which has 2^k_next entries W.  z: k_i challenges.
@@ -579,7 +614,8 @@ enum {
     GKR_VERIFY_FINAL_CLAIM = 6,    /* g_v(r_v) != add (q0 + q1) + mult q0 q1 */
     GKR_VERIFY_R_STAR = 7,         /* r* != multi_hash(last round vector) */
     GKR_VERIFY_NEXT_Z = 8,         /* z[i+1] != b* + r* (c* - b*) */
-    GKR_VERIFY_INPUT = 9           /* q(r*) of the last layer != input_func(z[L]) */
+    GKR_VERIFY_INPUT = 9,          /* q(r*) of the last layer != input_func(z[L]) */
+    GKR_VERIFY_EVALUATION = 10     /* plain sumcheck (gkr_sumcheck_mle_verify*): g_n(r_n) != T~(r_1 .. r_n) */
 };
 int  gkr_verify(const gkr_circuit_desc *circuit, const gkr_proof_buf *proof, int threads, int *accept, uint32_t *failed_layer,
                 uint32_t *failed_check);
