@@ -1,7 +1,8 @@
 // Internals shared by the translation units of the C ABI (gkr_capi.hip: contexts, transcript helpers, self-tests, device
-// memory; capi_mle.hip: the plain sumcheck; capi_layer.hip: the layer sumcheck over gate lists; capi_layer_dense.hip: its dense
-// form; capi_prove.hip: whole proofs): the context, its caches and workspaces, profiling brackets, the host transcript's
-// helpers, the hand-off wait.  Not a public header.
+// memory; capi_mle.hip: the plain sumcheck's entry points, per-round schedules and sessions; capi_mle_passes.hip: its multi-round
+// schedule, whole tables and tables split over ranks; capi_layer.hip: the layer sumcheck over gate lists; capi_layer_dense.hip:
+// its dense form; capi_prove.hip: whole proofs): the context, its caches and workspaces, profiling brackets, the host
+// transcript's helpers, the hand-off wait, the plain sumcheck's group hand-off.  Not a public header.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <sched.h>
@@ -608,7 +609,89 @@ inline int mle_pass_rounds(int m, int n, int jmax) {
     return j < 1 ? 1 : j;
 }
 
-// ---- defined in capi_mle.hip
+// ---- shared by the plain sumcheck's two host-transcript drivers (capi_mle.hip: one round per pass; capi_mle_passes.hip: multi-round passes)
+// One round of one sumcheck in the caller's arrays (row = sumcheck x rounds per sumcheck + round; c0, c1, r: 32 canonical bytes
+// each): the linear slot is zero unless the round vector has two coefficients.
+inline void write_round_output(gkr_fr* out_coeffs, uint32_t* out_len, gkr_fr* out_r, size_t row, const void* c0, const void* c1, uint32_t ln,
+                               const void* r) {
+    memset(&out_coeffs[row * 2], 0, 32);
+    if (ln == 2) memcpy(&out_coeffs[row * 2], c1, 32);
+    memcpy(&out_coeffs[row * 2 + 1], c0, 32);
+    out_len[row] = ln;
+    memcpy(&out_r[row], r, 32);
+}
+// A scheduling group of a batch (sumchecks b0 .. b0 + nb - 1) and its hand-off: the driving thread queues the group's next pass
+// under a fresh ticket, sees its records land, opens a generation for the hashing threads, which claim the group's sumchecks
+// chunk by chunk and report them finished; when all are, the driving thread queues the pass after.
+struct GroupHandoff {
+    int b0 = 0, nb = 0;
+    int state = 0;   // 0 waiting for the GPU, 1 hashing, 2 finished (the driving thread's)
+    uint32_t ticket = 0;
+    std::atomic<uint64_t> claim{0};   // (generation << 32) | next sumcheck to hash; generation 0: nothing open
+    std::atomic<int> done{0};
+    template <typename Rec>
+    bool records_landed(const Rec* rec) const {
+        for (int i = nb - 1; i >= 0; --i)
+            if (__atomic_load_n(&rec[b0 + i].seq, __ATOMIC_ACQUIRE) != ticket) return false;
+        return true;
+    }
+    void open(uint32_t generation) {
+        done.store(0, std::memory_order_relaxed);
+        claim.store((uint64_t)generation << 32, std::memory_order_release);
+        state = 1;
+    }
+    // the generation whose sumchecks are not all taken yet, 0 if there is none
+    uint32_t open_generation() const {
+        const uint64_t c = claim.load(std::memory_order_acquire);
+        return (uint32_t)c < (uint32_t)nb ? (uint32_t)(c >> 32) : 0u;
+    }
+    // a hashing thread: the next `chunk` sumchecks (fewer at the end) of the open generation; false: none open, or all taken
+    bool try_claim(uint32_t chunk, uint32_t* first, uint32_t* take, uint32_t* generation = nullptr) {
+        uint64_t c = claim.load(std::memory_order_acquire);
+        while ((c >> 32) != 0 && (uint32_t)c < (uint32_t)nb) {
+            const uint32_t left = (uint32_t)nb - (uint32_t)c, t = left < chunk ? left : chunk;
+            if (!claim.compare_exchange_weak(c, c + t, std::memory_order_acq_rel)) continue;   // lost a race: look again
+            *first = (uint32_t)c;
+            *take = t;
+            if (generation) *generation = (uint32_t)(c >> 32);
+            return true;
+        }
+        return false;
+    }
+    void finish(uint32_t count) { done.fetch_add((int)count, std::memory_order_release); }
+    // the driving thread: every sumcheck of the open generation is hashed (closes the generation)
+    bool all_done() {
+        if (done.load(std::memory_order_acquire) != nb) return false;
+        claim.store(0, std::memory_order_release);
+        return true;
+    }
+};
+// The driving thread's watch over such a loop (`unit`: "pass" or "round"): launch errors after every step that made progress;
+// while nothing moves, a stream query every 2^16 spins and a limit of 60 s on the time WITHOUT progress, not on the whole call.
+struct HandoffWatch {
+    gkr_ctx* ctx;
+    hipStream_t s;
+    std::string unit;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    uint32_t idle = 0;
+    int progressed() {
+        idle = 0;
+        t0 = std::chrono::steady_clock::now();
+        if (hipError_t le = hipGetLastError(); le != hipSuccess) return ctx->hip_fail(le, ("launch of a sumcheck " + unit).c_str());
+        return GKR_OK;
+    }
+    int idled() {
+        GKR_CPU_RELAX();
+        if ((++idle & 0xFFFF) != 0) return GKR_OK;
+        const hipError_t q = hipStreamQuery(s);
+        if (q != hipSuccess && q != hipErrorNotReady) return ctx->hip_fail(q, ("stream failed during a sumcheck " + unit).c_str());
+        if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(60))
+            return ctx->fail(GKR_ERR_HIP, "timed out waiting for the device to publish a " + unit);
+        return GKR_OK;
+    }
+};
+
+// ---- defined in capi_mle_passes.hip
 void host_pass_scalar(const uint64_t* sums, size_t sums_row_words, int count, int J, const uint32_t* final_len, uint64_t (*c0)[16][4],
                       uint64_t (*c1)[16][4], uint64_t (*r)[16][4], uint32_t (*len)[16], uint64_t* weights, size_t w_row_words);
 // `tail` (may be null): the tables are the TAIL of longer sumchecks (gkr_sumcheck_mle_sharded_dev: what is left of a table
@@ -621,6 +704,7 @@ struct MleTailArgs {
 };
 int run_mle_batch_passes(gkr_ctx* ctx, const Fr* d_tables, int n, int batch, gkr_fr* out_coeffs, uint32_t* out_len, gkr_fr* out_r,
                          const MleTailArgs* tail = nullptr);
+// ---- defined in capi_mle.hip
 int run_mle_batch(gkr_ctx* ctx, const Fr* d_tables, int n, int batch, gkr_fr* out_coeffs, uint32_t* out_len, gkr_fr* out_r);
 // ---- defined in capi_layer.hip
 void host_tail_pass(gkr::h64::F* tables, size_t stride, uint32_t m, uint32_t jp, const gkr::h64::F* weights, uint32_t J, gkr::h64::F* rec);

@@ -1,0 +1,708 @@
+// The plain multilinear sumcheck (prove_sumcheck, rust/src/gkr/sumcheck.rs:158-214) on the multi-round schedule with the host
+// transcript: the tables of a run and THE pass launcher, the schedule of a batch, the driver of whole tables (run_mle_batch_passes)
+// and of one table split over ranks (gkr_sumcheck_mle_sharded_dev).  C ABI: include/gkr_amd.h.
+#include "capi_internal.h"
+
+namespace gkr_host {
+
+// ------------------------------------------------------------- plain MLE sumcheck, multi-round passes
+// The host's share of one multi-round pass, scalar form (the IFMA-lane form is gkr_ifma_pass, mimc_ifma.cpp; same
+// arguments, same results): per lane k and round t the round polynomial's coefficients from the sub-block sums, the
+// vector's length, the challenge, then the sums with that variable bound; at the end the 2^J weights of the fold pass
+// that binds the J variables, w_b = prod_t (bit_t(b) ? r_t : 1 - r_t), bit_0 = most significant, Montgomery form.
+void host_pass_scalar(const uint64_t* sums, size_t sums_row_words, int count, int J, const uint32_t* final_len,
+                             uint64_t (*c0)[16][4], uint64_t (*c1)[16][4], uint64_t (*r)[16][4], uint32_t (*len)[16],
+                             uint64_t* weights, size_t w_row_words) {
+    using gkr::h64::F;
+    const F* cts = host_mimc_constants64();
+    const F one_m = gkr::h64::to_mont(F{{1, 0, 0, 0}});
+    for (int k = 0; k < count; ++k) {
+        F S[gkr::kMleMaxSub], rm[gkr::kMlePassMaxRounds];
+        memcpy(S, sums + (size_t)k * sums_row_words, sizeof(F) << J);
+        for (int t = 0; t < J; ++t) {
+            const int half = 1 << (J - t - 1);
+            F lo = S[0], hi = S[half];
+            for (int b = 1; b < half; ++b) {
+                lo = gkr::h64::add(lo, S[b]);
+                hi = gkr::h64::add(hi, S[half + b]);
+            }
+            const F d = gkr::h64::sub(hi, lo);
+            const uint32_t ln = (final_len && t == J - 1) ? final_len[k] : (gkr::h64::is_zero(d) ? 1u : 2u);
+            const F vec[2] = {d, lo};
+            const F rc = host_multi_hash(vec + (2 - ln), (int)ln, cts);
+            memcpy(c0[t][k], &lo, 32);
+            memcpy(c1[t][k], &d, 32);
+            memcpy(r[t][k], &rc, 32);
+            len[t][k] = ln;
+            rm[t] = gkr::h64::to_mont(rc);
+            for (int b = 0; b < half; ++b) S[b] = gkr::h64::add(S[b], gkr::h64::mont_mul(gkr::h64::sub(S[half + b], S[b]), rm[t]));
+        }
+        if (!weights) continue;
+        F* w = reinterpret_cast<F*>(weights + (size_t)k * w_row_words);
+        F tmp[gkr::kMleMaxSub];
+        tmp[0] = one_m;
+        int cur = 1;
+        for (int t = 0; t < J; ++t) {
+            const F nr = gkr::h64::sub(one_m, rm[t]);
+            for (int b = cur; b-- > 0;) {
+                tmp[2 * b + 1] = gkr::h64::mont_mul(tmp[b], rm[t]);
+                tmp[2 * b] = gkr::h64::mont_mul(tmp[b], nr);
+            }
+            cur <<= 1;
+        }
+        memcpy(w, tmp, sizeof(F) << J);
+    }
+}
+
+// ------------------------------------------------------------- the tables a run's passes work on, and THE pass launcher
+struct MlePassTables {
+    const Fr* input = nullptr;   // the caller's tables, in_stride = 2^n entries apart: pass 0 and the first fold read them
+    size_t in_stride = 0;
+    Fr* work = nullptr;          // every fold's output, work_len entries (the first folded table) apart
+    size_t work_len = 0;
+    gkr::MleSubPartial* partials = nullptr;
+    unsigned char* plans = nullptr;        // per sumcheck: the digit matrix of the matrix-core fold pass
+    Fr* h_w = nullptr;                     // pinned: up to 32 Montgomery weights per sumcheck
+    gkr::MleHostRecSub* h_rec = nullptr;   // pinned: the records the host reads
+    gkr::MleHostRecSub* rec = nullptr;     // the records the passes publish to: h_rec, or device records on their way through an exchange
+    uint32_t* arrivals = nullptr;          // zeroed counters of passes that publish from their last block; null: no pass does
+    Fr* h_tail = nullptr;                  // pinned: the host tail's tables, 2^kMleTailLog2 entries apart; null: no host tail
+};
+// (slots `prefix`.work / .partials / .plans / .rec / .w: the context caches the allocations by these names)
+static int mle_pass_tables(gkr_ctx* ctx, const std::string& prefix, const Fr* input, size_t len, size_t work_len, int batch, MlePassTables& T) {
+    T.input = input;
+    T.in_stride = len;
+    T.work_len = work_len;
+    WS(ctx, (prefix + ".work").c_str(), Fr, (size_t)batch * (work_len ? work_len : 1), T.work);
+    WS(ctx, (prefix + ".partials").c_str(), gkr::MleSubPartial, (size_t)batch * gkr::kMaxBlocksPerTable, T.partials);
+    WS(ctx, (prefix + ".plans").c_str(), unsigned char, (size_t)batch * gkr::mle_fold_plan_bytes(), T.plans);
+    HIP_TRY(ctx, ctx->pinned_host((prefix + ".rec").c_str(), sizeof(gkr::MleHostRecSub) * batch, reinterpret_cast<void**>(&T.h_rec)));
+    HIP_TRY(ctx, ctx->pinned_host((prefix + ".w").c_str(), sizeof(Fr) * gkr::kMleMaxSub * batch, reinterpret_cast<void**>(&T.h_w)));
+    T.rec = T.h_rec;
+    return GKR_OK;
+}
+
+// Latency-bound passes (a few sumchecks of moderate size: at most kFusedPublishBytes read per launch) publish from their
+// last block instead of through k_mle_sub_reduce: one launch and one dependent-launch gap less per pass on the round
+// path of a lone sumcheck.  Streaming passes keep the second launch (see mle_publish_from_last_block).
+constexpr double kFusedPublishBytes = 64.0 * 1024 * 1024;
+constexpr uint32_t kFusedPublishBlocks = 256;   // blocks per launch: each pays one L2 write-back (~30 ns, one after the other)
+constexpr size_t kArrivalCounters = 4096;       // (one size: zeroed once per allocation, every pass leaves them zero)
+static int mle_arrival_counters(gkr_ctx* ctx, size_t len, MlePassTables& T) {
+    if (gkr::opt(gkr::OPT_no_fused_reduce) != 0 || (double)len * 32.0 > kFusedPublishBytes) return GKR_OK;
+    WS(ctx, "mlep.arrivals", uint32_t, kArrivalCounters, T.arrivals);
+    if (ctx->mle_arrivals_zeroed != T.arrivals) {
+        HIP_TRY(ctx, hipMemsetAsync(T.arrivals, 0, sizeof(uint32_t) * kArrivalCounters, ctx->stream));
+        ctx->mle_arrivals_zeroed = T.arrivals;
+    }
+    return GKR_OK;
+}
+static bool fused_publish(const MlePassTables& T, int b0, int nb, uint32_t nblk, double bytes_read, uint32_t ticket, int jout, gkr::MlePublish& pub) {
+    if (!T.arrivals || (size_t)(b0 + nb) > kArrivalCounters || bytes_read > kFusedPublishBytes || (uint64_t)nblk * nb > kFusedPublishBlocks || nblk > 128u)
+        return false;
+    pub.rec = T.rec + b0;
+    pub.arrivals = T.arrivals + b0;
+    pub.ticket = ticket;
+    pub.jout = (uint32_t)jout;
+    return true;
+}
+
+constexpr uint32_t kMleTailLog2 = 7;   // the host tail (run_mle_batch_passes): tables of 2^7 entries and fewer
+// What differs between the callers of a pass (the stream is an argument): a scheduling group, the device-hashed chain, the
+// driver of a table split over ranks.
+struct MlePassPolicy {
+    const char* row = nullptr;   // profile row of the streaming kernel
+    int plan_event = -1;         // >= 0: the fold's digit matrices on the side stream, ordered by this aux event; -1: on the pass's own stream, untimed
+    Fr* export_tail = nullptr;   // a one-block fold leaves its tables here as well (the host tail's slice of h_tail)
+};
+static void queue_sub_reduce(gkr_ctx* ctx, const MlePassTables& T, int b0, int nb, uint32_t nblk, int jout, uint32_t ticket, hipStream_t st) {
+    Timed t(ctx, "mle_sub_reduce", 0.0, st, true);
+    gkr::launch_mle_sub_reduce(T.partials + (size_t)b0 * gkr::kMaxBlocksPerTable, nblk, (uint32_t)jout, nb, T.rec + b0, ticket, st);
+}
+// pass 0 of the sumchecks [b0, b0 + nb): the 2^jout sub-block sums of the input tables
+static void queue_pass0(gkr_ctx* ctx, const MlePassTables& T, int b0, int nb, int jout, uint32_t ticket, hipStream_t st, const MlePassPolicy& P) {
+    const size_t len = T.in_stride;
+    const Fr* src = T.input + (size_t)b0 * len;
+    const double bytes = (double)nb * len * 32.0;
+    if (len <= gkr::kSmallPassEntries) {
+        Timed t(ctx, "mle_pass_small", bytes, st, true);
+        gkr::launch_mle_multifold_small(0, src, len, nullptr, 0, (uint32_t)len, (uint32_t)jout, nb, T.h_w + (size_t)b0 * gkr::kMleMaxSub, T.rec + b0, ticket, st);
+        return;
+    }
+    const uint32_t nblk = gkr::mle_pass_blocks((uint32_t)len, (uint32_t)jout, nb);
+    gkr::MlePublish pub;
+    const bool fused = fused_publish(T, b0, nb, nblk, bytes, ticket, jout, pub);
+    {
+        Timed t(ctx, P.row, bytes, st, fused);
+        gkr::launch_mle_sub_sums(src, len, (uint32_t)len, nb, nblk, T.partials + (size_t)b0 * gkr::kMaxBlocksPerTable, st, fused ? &pub : nullptr);
+    }
+    if (!fused) queue_sub_reduce(ctx, T, b0, nb, nblk, jout, ticket, st);
+}
+// a fold pass: bind the jin variables just hashed of tables of 2^m_src entries (the input, or work), produce the sums of the next jout rounds
+static void queue_fold(gkr_ctx* ctx, const MlePassTables& T, int b0, int nb, bool from_input, int m_src, int jin, int jout, uint32_t ticket,
+                       hipStream_t st, const MlePassPolicy& P) {
+    const size_t src_len = (size_t)1 << m_src, S = src_len >> jin;
+    const Fr* src = from_input ? T.input + (size_t)b0 * T.in_stride : T.work + (size_t)b0 * T.work_len;
+    const size_t src_stride = from_input ? T.in_stride : T.work_len;
+    Fr* dst = T.work + (size_t)b0 * T.work_len;
+    const Fr* w = T.h_w + (size_t)b0 * gkr::kMleMaxSub;
+    const double bytes = (double)nb * ((double)src_len + (double)S) * 32.0;
+    if (S <= gkr::kSmallPassEntries) {
+        Timed t(ctx, "mle_pass_small", bytes, st, true);
+        gkr::launch_mle_multifold_small(jin, src, src_stride, dst, T.work_len, (uint32_t)S, (uint32_t)jout, nb, w, T.rec + b0, ticket, st, P.export_tail,
+                                        1u << kMleTailLog2);
+        return;
+    }
+    const uint32_t nblk = gkr::mle_multifold_blocks((uint32_t)S, (uint32_t)jout, nb);
+    unsigned char* plan = T.plans + (size_t)b0 * gkr::mle_fold_plan_bytes();
+    if (gkr::mle_multifold_uses_mfma((uint32_t)S, nblk)) {
+        // the digit matrices only depend on the weights the host just wrote: built on the side stream, the main stream (busy
+        // with another group's pass) pays one event wait, not a launch round trip -- where the caller asks for it
+        if (P.plan_event < 0) {
+            gkr::launch_mle_fold_plan(jin, w, plan, nb, st);
+        } else {
+            {
+                Timed t(ctx, "mle_fold_plan", 0.0, ctx->aux, true);
+                gkr::launch_mle_fold_plan(jin, w, plan, nb, ctx->aux);
+            }
+            (void)hipEventRecord(ctx->aux_events[P.plan_event], ctx->aux);
+            (void)hipStreamWaitEvent(st, ctx->aux_events[P.plan_event], 0);
+        }
+    }
+    gkr::MlePublish pub;
+    const bool fused = fused_publish(T, b0, nb, nblk, (double)nb * (double)src_len * 32.0, ticket, jout, pub);
+    {
+        Timed t(ctx, P.row, bytes, st, fused);
+        gkr::launch_mle_multifold(jin, src, src_stride, dst, T.work_len, (uint32_t)S, nb, nblk, w, plan, T.partials + (size_t)b0 * gkr::kMaxBlocksPerTable, st,
+                                  fused ? &pub : nullptr);
+    }
+    if (!fused) queue_sub_reduce(ctx, T, b0, nb, nblk, jout, ticket, st);
+}
+
+// ------------------------------------------------------------- the schedule of a batch: arithmetic only, no device
+struct MleSchedule {
+    int jmax = 0, j_first = 0;    // rounds per pass at most; rounds of pass 0
+    int n_dev = 0;                // sumchecks [0, n_dev) are hashed on the device, as one chain on a stream of its own
+    int groups = 0, depth = 0;    // scheduling groups of the host-hashed rest; groups whose pass 0 is queued up front
+    int bound[kMaxGroups + 1];    // group g: sumchecks [bound[g], bound[g + 1])
+    uint32_t chunk[kMaxGroups];   // sumchecks a hashing thread takes at a time from group g
+    bool tail_on = false;         // the host finishes tables of 2^kMleTailLog2 entries and fewer
+};
+static MleSchedule mle_schedule(int n, int batch, int hash_threads, bool is_tail, const gkr::Options& o) {
+    MleSchedule sc;
+    const double len = (double)((size_t)1 << n);
+    // rounds per pass: up to 5 with the matrix-core fold (fewer passes, ~2.07 N elements moved instead of 2.29 N),
+    // up to 3 with the v_mad_u64_u32 fold (option no_mfma_fold)
+    const int jcap = o.v[gkr::OPT_no_mfma_fold] ? 3 : gkr::kMlePassMaxRounds;
+    const int jwant = o.v[gkr::OPT_rounds_per_pass] > 0 ? (int)o.v[gkr::OPT_rounds_per_pass] : jcap;
+    sc.jmax = jwant > jcap ? jcap : jwant;
+    sc.j_first = mle_pass_rounds(n, n, sc.jmax);
+    // Groups of ~4 GiB of tables, at least four and at most eight (1024 x 2^20: eight groups of 128); sixteen for batches
+    // beyond 96 GiB (4096 x 2^20: 4.64e11 field-ops/s with sixteen groups of 256, 4.48e11 with eight of 512).  Larger launches
+    // stream slightly better, smaller groups feed the host's hashing more evenly and leave a shorter exposed tail (the
+    // last group's late passes); measured on MI355X, 1024 x 2^20, interleaved repeats on one box, ms per step with
+    // 14 / 3 / 2 host threads: 4 groups, all pass 0s queued first 12.3-12.9 / 15.0-16.3 / 18.5-19.0; 8 groups, pass 0
+    // queue depth 2 (below) 12.0-12.5 / 13.5-14.0 / 16.5-17.8; 6, 10 and 12 groups in between.
+    // Sumchecks hashed ON THE DEVICE (kernels_transcript.hip): the first n_dev of the batch run as one chain of kernels on
+    // a stream of their own -- pass, the pass's rounds with MiMC7 on eight lanes per element, fold, ... -- without the host;
+    // the host hashes the rest as always.  A device-hashed pass takes 0.33 ms per round whatever the number of sumchecks
+    // (the chain of 2 x 91 x 4 dependent products), so this is for steps that are bound by the host's hashing: a rank with
+    // two or three host threads, tables so small that the GPU is mostly idle.  Option device_hash_percent = share of the batch
+    // (0 = none, the default).
+    const long long dp = o.v[gkr::OPT_device_hash_percent];
+    const int dev_percent = dp < 0 ? 0 : (dp > 90 ? 90 : (int)dp);
+    if (dev_percent > 0 && !is_tail && batch >= 64 && sc.j_first >= 1) {
+        sc.n_dev = (int)((long long)batch * dev_percent / 100) & ~7;
+        if (batch - sc.n_dev < 16) sc.n_dev = (batch - 16) & ~7;
+        if (sc.n_dev < 8) sc.n_dev = 0;
+    }
+    const int host_batch = batch - sc.n_dev;
+    const double batch_bytes = (double)host_batch * len * 32.0;
+    int want_groups = (int)(batch_bytes / (4.0 * 1024 * 1024 * 1024));
+    want_groups = want_groups < 4 ? 4 : (want_groups > 8 ? (batch_bytes > 96.0 * 1024 * 1024 * 1024 ? 16 : 8) : want_groups);
+    // Small tables (BASELINE configs[1]: 4096 x 2^16) are bound by the host's hashing, not by the stream: sixteen groups
+    // with pass 0 of four of them queued ahead keep the hashing threads fed from start to end (MI355X, 14 threads, ms per
+    // 4096 x 2^16: 4 groups 8.1 - 8.2, 8 groups 8.1, 16 groups 7.2, 16 groups / depth 4 7.0 - 7.2, 32 groups / depth 8 7.1;
+    // profiles/r03/f_n16_groups*.jsonl)
+    const bool small_tables = n <= 17 && host_batch >= 256;
+    if (small_tables) want_groups = 16;
+    // A rank with two or three host threads (eight ranks on a 16-core host) is bound by its hashing: smaller groups shorten
+    // the stretch before the first hashes and after the last fold (1024 x 2^20, two threads: 16.3 - 16.7 ms with eight
+    // groups, 16.0 with sixteen; profiles/r03/w_two_host_threads_group_size.jsonl)
+    if (hash_threads <= 3 && host_batch >= 256 && want_groups < 16) want_groups = 16;
+    int group_size = host_batch >= 128 ? (host_batch + want_groups - 1) / want_groups : (host_batch >= 16 ? (host_batch + 1) / 2 : host_batch);
+    if (sc.n_dev && hash_threads <= 3 && host_batch >= 256) group_size = 64;   // (whole sixteen-lane chunks for both threads, as without a device share)
+    if (o.v[gkr::OPT_group_size] > 0) group_size = (int)o.v[gkr::OPT_group_size];
+    sc.groups = (host_batch + group_size - 1) / group_size;
+    if (sc.groups > kMaxGroups) sc.groups = kMaxGroups;
+    // Sumchecks a hashing thread takes at a time, per group: sixteen (full IFMA calls: throughput) when the group has plenty
+    // for every thread; otherwise ONE chunk per thread where that fits the sixteen lanes -- a pass's J hashes of a sumcheck
+    // are a serial chain, so a group of 128 on 14 threads is done in one chain of 16-lane calls filled to 10 (J x 20 us)
+    // instead of two chains of 8-lane calls (2 x J x 16 us), at the same cost per hash; the option hash_chunk forces 8 or 16
+    const long long forced = o.v[gkr::OPT_hash_chunk];
+    for (int g = 0; g <= sc.groups; ++g) sc.bound[g] = sc.n_dev + (int)((long long)host_batch * g / sc.groups);
+    for (int g = 0; g < sc.groups; ++g) {
+        const int nb = sc.bound[g + 1] - sc.bound[g], per = (nb + hash_threads - 1) / hash_threads;
+        sc.chunk[g] = forced == 8 || forced == 16 ? (uint32_t)forced : (nb >= 32 * hash_threads ? 16u : (uint32_t)(per <= 8 ? 8 : (per <= 16 ? per : 16)));
+    }
+    // Pass 0 of the first `depth` groups is queued up front, pass 0 of a later group right behind the first fold of an
+    // earlier one: the stream then alternates between pass 0 of later groups and the first fold of earlier ones
+    // (P0 P0 F0 P0 F1 P0 F2 F3 with four groups), and the host's hashing -- which with few threads takes as long as the
+    // GPU's work -- is fed from the first millisecond to the last instead of in one burst after all the pass 0s.
+    // (All pass 0s first: 2 host threads 19.0 ms per 1024 x 2^20 at 77 % hashing occupancy, 3 threads 15.6 ms at 63 %.)
+    sc.depth = o.v[gkr::OPT_pass_queue_depth] > 0 ? (int)o.v[gkr::OPT_pass_queue_depth] : (small_tables ? 4 : 2);
+    // The host tail: the last fold pass of a sumcheck works on a table of 2^7 entries and fewer -- 128 products, and ~30 us as a
+    // device pass (launch, 15 us of kernel, the record's way back).  For a few sumchecks at a time (a latency chain, not a
+    // throughput problem) the pass before it leaves its folded table in pinned memory as well, and the host binds the remaining
+    // variables itself: exact field arithmetic, the same canonical sums.
+    sc.tail_on = o.v[gkr::OPT_host_tail_log2] >= 0 && sc.n_dev == 0 && batch <= (o.v[gkr::OPT_host_tail_max_batch] > 0 ? o.v[gkr::OPT_host_tail_max_batch] : 8);
+    return sc;
+}
+
+// ------------------------------------------------------------- the driver
+namespace {
+struct PassGroup : GroupHandoff {   // (generation of the hand-off = pass number + 1)
+    int m = 0;        // variables left in the current table
+    int j = 0;        // rounds the landed sums cover (the pass in flight produces 2^j sums)
+    int round0 = 0;   // global index of the first of those rounds
+    int pass = 0, index = 0;
+    hipStream_t chain = nullptr;   // a device-hashed group: the stream its whole chain runs on
+    bool on_host = false;          // the host tail: the group's tables (2^m entries each) are in h_tail, the device is done with them
+};
+// GKR_DEBUG_TIMING: the phases of a call on the host clock
+struct MlePassClock {
+    const bool on = gkr::debug_timing();
+    const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    double a = 0, b = 0, c = 0, d = 0, e = 0;
+    std::atomic<uint64_t> busy_ns{0};   // time inside process_chunk, all threads
+    double us() const { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); }
+    void report(int threads) const {
+        if (!on) return;
+        fprintf(stderr,
+                "[gkr timing] setup %.0f us, first launches %.0f, loop %.0f, end_session %.0f, sync %.0f, drain %.0f; hashing %.0f us "
+                "over %d threads = %.0f%% of the loop\n",
+                a, b - a, c - b, d - c, e - d, us() - e, busy_ns.load() * 1e-3, threads, busy_ns.load() * 1e-3 / ((c - b) * threads) * 100.0);
+    }
+};
+
+struct MlePassRun {
+    gkr_ctx* ctx;
+    const int n, batch;
+    const MleTailArgs* tail;
+    gkr_fr* out_coeffs;
+    uint32_t* out_len;
+    gkr_fr* out_r;
+    MleSchedule sc;
+    MlePassTables T;
+    hipStream_t s = nullptr, late = nullptr, chain = nullptr;
+    std::vector<PassGroup> grp;
+    std::vector<uint32_t> dep_last;
+    int next_first = 0;   // groups [next_first, groups): pass 0 still to launch
+    gkr_fr *stage_c = nullptr, *stage_r = nullptr;   // pinned: the device-hashed sumchecks' outputs, in the caller's layout
+    uint32_t* stage_len = nullptr;
+    MlePassClock clock;
+
+    int rounds_for(int m) const { return mle_pass_rounds(m, n, sc.jmax); }
+    void advance(PassGroup& G, int jin) {
+        G.m -= jin;
+        G.round0 += jin;
+        G.j = rounds_for(G.m);
+        G.ticket = ++ctx->ticket;
+    }
+    // pass 0: sub-block sums of the input tables
+    void launch_first(PassGroup& G) {
+        G.ticket = ++ctx->ticket;
+        MlePassPolicy P;
+        P.row = G.chain ? "mle_sub_sums_dev" : "mle_sub_sums";
+        queue_pass0(ctx, T, G.b0, G.nb, G.j, G.ticket, G.chain ? G.chain : s, P);
+    }
+    void launch_next_first() {
+        if (next_first < sc.groups) launch_first(grp[next_first++]);
+    }
+    // a fold pass: bind the jin variables just hashed, produce the sums of the next rounds
+    void launch_fold(PassGroup& G, int jin) {
+        const int m_src = G.m;
+        const bool from_input = m_src == n;
+        // small source tables: a latency-bound late pass, not to be queued behind other groups' streaming passes
+        hipStream_t st = G.chain ? G.chain : ((!from_input && m_src <= 16) ? late : s);
+        advance(G, jin);
+        MlePassPolicy P;
+        // late passes run beside other groups' streaming passes: their elapsed time is not their own cost, so they
+        // are booked under their own name and stay out of the streaming fold pass's bandwidth figure
+        P.row = G.chain ? "mle_multifold_dev" : (st == s ? "mle_multifold" : "mle_multifold_late");
+        // (one group: nothing else is streaming, and the event between the two streams costs the round path ~10 us
+        // more than a second launch on the same stream -- 15 us against 5 between the plan and the fold)
+        if (!gkr::opt(gkr::OPT_plan_main) && st == s && sc.groups != 1) P.plan_event = G.index;
+        // (the table it leaves is small enough for the host to finish, and there is a pass left to save)
+        G.on_host = sc.tail_on && !G.chain && G.m <= (int)kMleTailLog2 && G.m - G.j > 0;
+        if (G.on_host) P.export_tail = T.h_tail + ((size_t)G.b0 << kMleTailLog2);
+        queue_fold(ctx, T, G.b0, G.nb, from_input, m_src, jin, G.j, G.ticket, st, P);
+    }
+    // the same pass on the host (the group's tables are in h_tail): T'[i] = sum_t w_t T[t S + i], then the sub-block sums of the
+    // next rounds into the record the device pass would have written
+    void host_fold(PassGroup& G, int jin) {
+        using gkr::h64::F;
+        advance(G, jin);
+        const size_t S = (size_t)1 << G.m, nsub = (size_t)1 << G.j, sub = S >> G.j;
+        for (int b = G.b0; b < G.b0 + G.nb; ++b) {
+            F* tab = reinterpret_cast<F*>(T.h_tail + ((size_t)b << kMleTailLog2));
+            const F* w = reinterpret_cast<const F*>(T.h_w + (size_t)b * gkr::kMleMaxSub);
+            for (size_t i = 0; i < S; ++i) {
+                gkr::h64::Wide acc = gkr::h64::wide_zero();
+                for (size_t t = 0; t < ((size_t)1 << jin); ++t) gkr::h64::wide_mac(acc, tab[t * S + i], w[t]);
+                tab[i] = gkr::h64::wide_reduce(acc);
+            }
+            F* sums = reinterpret_cast<F*>(T.h_rec[b].sums);
+            for (size_t a = 0; a < nsub; ++a) {
+                F v = tab[a * sub];
+                for (size_t i = 1; i < sub; ++i) v = gkr::h64::add(v, tab[a * sub + i]);
+                sums[a] = v;
+            }
+            __atomic_store_n(&T.h_rec[b].seq, G.ticket, __ATOMIC_RELEASE);
+        }
+    }
+    // the J rounds of up to sixteen sumchecks whose sub-block sums have landed
+    void process_chunk(const PassGroup& G, int b_first, int count) {
+        static const bool scalar_book = gkr::process_switch("GKR_HOST_PASS_SCALAR");   // A/B switch: host_pass_scalar even where the CPU has IFMA
+        const int J = G.j, n_out = tail ? tail->n_total : n, r_off = tail ? tail->round_offset : 0;
+        uint64_t c0[gkr::kMlePassMaxRounds][16][4], c1[gkr::kMlePassMaxRounds][16][4], r[gkr::kMlePassMaxRounds][16][4];
+        uint32_t ln[gkr::kMlePassMaxRounds][16], final_len[16];
+        const bool final_pass = G.round0 + J == n;
+        for (int i = 0; i < count; ++i) {
+            if (G.round0 == 0) dep_last[b_first + i] = tail && tail->dep_last ? tail->dep_last[b_first + i] : T.h_rec[b_first + i].dep;
+            final_len[i] = dep_last[b_first + i] ? 2u : 1u;
+        }
+        static_assert(sizeof(gkr::MleHostRecSub) % 8 == 0, "hand-off records are addressed in 64-bit words");
+        const uint64_t* sums = reinterpret_cast<const uint64_t*>(T.h_rec[b_first].sums);
+        uint64_t* weights = G.m - J > 0 ? reinterpret_cast<uint64_t*>(T.h_w + (size_t)b_first * gkr::kMleMaxSub) : nullptr;
+        (host_ifma_ready() && count >= 3 && !scalar_book ? gkr::gkr_ifma_pass : host_pass_scalar)(
+            sums, sizeof(gkr::MleHostRecSub) / 8, count, J, final_pass ? final_len : nullptr, c0, c1, r, ln, weights, 4 * gkr::kMleMaxSub);
+        for (int i = 0; i < count; ++i)
+            for (int t = 0; t < J; ++t)
+                write_round_output(out_coeffs, out_len, out_r, (size_t)(b_first + i) * n_out + r_off + G.round0 + t, c0[t][i], c1[t][i], ln[t][i], r[t][i]);
+    }
+    // A hashing thread takes its next chunk from the group that is EARLIEST in its schedule (generation = pass number):
+    // the hashes of an early pass release the next streaming pass, whose results are most of the host work still to
+    // come, while the late passes' hashes release microseconds of GPU work -- they fill the time in between.
+    bool try_work() {
+        for (;;) {
+            int best = -1;
+            uint32_t best_gen = 0;
+            for (int g = 0; g < sc.groups; ++g)
+                if (const uint32_t gen = grp[g].open_generation(); gen && (best < 0 || gen < best_gen)) best = g, best_gen = gen;
+            if (best < 0) return false;
+            PassGroup& G = grp[best];
+            uint32_t first, take;
+            if (!G.try_claim(sc.chunk[best], &first, &take)) continue;   // the others took the rest meanwhile: look again
+            const double t_in = clock.on ? clock.us() : 0.0;
+            process_chunk(G, G.b0 + (int)first, (int)take);
+            G.finish(take);
+            if (clock.on) clock.busy_ns.fetch_add((uint64_t)((clock.us() - t_in) * 1e3), std::memory_order_relaxed);
+            return true;
+        }
+    }
+    // the device-hashed sumchecks [0, n_dev): their whole chain is queued here, on its own stream
+    int queue_device_chain() {
+        const int n_dev = sc.n_dev;
+        HIP_TRY(ctx, ctx->chain_stream(&chain));
+        uint32_t* dep_dev = nullptr;
+        WS(ctx, "mlep.dev_dep", uint32_t, (size_t)n_dev, dep_dev);
+        HIP_TRY(ctx, ctx->pinned_host("mlep.stage_c", sizeof(gkr_fr) * 2 * (size_t)n_dev * n, reinterpret_cast<void**>(&stage_c)));
+        HIP_TRY(ctx, ctx->pinned_host("mlep.stage_r", sizeof(gkr_fr) * (size_t)n_dev * n, reinterpret_cast<void**>(&stage_r)));
+        HIP_TRY(ctx, ctx->pinned_host("mlep.stage_len", sizeof(uint32_t) * (size_t)n_dev * n, reinterpret_cast<void**>(&stage_len)));
+        PassGroup dev;
+        dev.nb = n_dev;
+        dev.m = n;
+        dev.j = sc.j_first;
+        dev.index = sc.groups;
+        dev.chain = chain;
+        launch_first(dev);
+        for (bool first = true;; first = false) {
+            const int J = dev.j;
+            {
+                Timed t(ctx, "mle_pass_hash_dev", 0.0, chain);
+                gkr::launch_mle_pass_hash_lanes(T.rec, (uint32_t)n_dev, (uint32_t)J, (uint32_t)dev.round0, (uint32_t)n, dev.round0 + J == n, first, ctx->d_cts,
+                                                dep_dev, dev.m - J > 0 ? T.h_w : nullptr, reinterpret_cast<Fr*>(stage_c), stage_len,
+                                                reinterpret_cast<Fr*>(stage_r), chain);
+            }
+            if (dev.m - J <= 0) return GKR_OK;
+            launch_fold(dev, J);
+        }
+    }
+    // one look at a group by the driving thread; true: it moved on
+    bool step(PassGroup& G, int& active) {
+        if (G.state == 0 && G.records_landed(T.h_rec)) {
+            G.open((uint32_t)++G.pass);
+            return true;
+        }
+        if (G.state != 1 || !G.all_done()) return false;
+        if (G.m - G.j > 0) {
+            const bool first_fold = G.m == n;
+            if (G.on_host)
+                host_fold(G, G.j);
+            else
+                launch_fold(G, G.j);
+            G.state = 0;
+            if (first_fold) launch_next_first();
+        } else {
+            G.state = 2;
+            --active;
+            launch_next_first();   // single-pass sumchecks: no fold to ride on
+        }
+        return true;
+    }
+    int loop() {
+        int rc = GKR_OK, active = sc.groups;
+        HandoffWatch watch{ctx, s, "pass"};
+        while (active > 0 && rc == GKR_OK) {
+            bool progress = false;
+            for (int g = 0; g < next_first; ++g) progress |= step(grp[g], active);
+            if (progress)
+                rc = watch.progressed();
+            else if (!try_work())
+                rc = watch.idled();
+        }
+        return rc;
+    }
+};
+}  // namespace
+
+// Host transcript, default schedule (kernels.hip "Multi-round passes"): a pass hands the host the
+// 2^J sub-block sums of the current table; the host runs J rounds on them (J <= 5 hashes in a row,
+// eight or sixteen sumchecks per IFMA call), derives the 2^J fold weights, and the next pass binds all J
+// variables at once.  Length rules as in run_mle_batch.
+int run_mle_batch_passes(gkr_ctx* ctx, const Fr* d_tables, int n, int batch, gkr_fr* out_coeffs, uint32_t* out_len, gkr_fr* out_r,
+                         const MleTailArgs* tail) {
+    MlePassRun R{ctx, n, batch, tail, out_coeffs, out_len, out_r};
+    const size_t len = (size_t)1 << n;
+    hipStream_t s = R.s = R.late = ctx->stream;
+    gkr::SpinPool* pool = ctx->host_pool();
+    const gkr::Options* o = gkr::current_options();
+    const MleSchedule& sc = R.sc = mle_schedule(n, batch, pool->workers() + 1, tail != nullptr, o ? *o : gkr::default_options());
+    if (int rc = mle_pass_tables(ctx, "mlep", d_tables, len, len >> sc.j_first, batch, R.T)) return rc;
+    if (int rc = mle_arrival_counters(ctx, len, R.T)) return rc;
+    HIP_TRY(ctx, ctx->aux_stream(sc.groups));
+    if (sc.tail_on) HIP_TRY(ctx, ctx->pinned_host("mlep.tail", sizeof(Fr) * ((size_t)batch << kMleTailLog2), reinterpret_cast<void**>(&R.T.h_tail)));
+    if (!gkr::opt(gkr::OPT_no_late_stream) && sc.groups > 1) HIP_TRY(ctx, ctx->late_stream(&R.late));
+    R.dep_last = std::vector<uint32_t>(batch, 0);
+    R.grp = std::vector<PassGroup>(sc.groups);
+    for (int g = 0; g < sc.groups; ++g) {
+        PassGroup& G = R.grp[g];
+        G.index = g;
+        G.b0 = sc.bound[g];
+        G.nb = sc.bound[g + 1] - sc.bound[g];
+        G.m = n;
+        G.j = sc.j_first;
+    }
+    const std::function<bool()> try_work = [&R] { return R.try_work(); };
+    R.clock.a = R.clock.us();
+    gkr::SpinPool::Session session(pool, &try_work);
+    R.launch_next_first();   // (the host's first sums before the device chain's first pass)
+    if (sc.n_dev)
+        if (int rc = R.queue_device_chain()) return rc;
+    while (R.next_first < sc.groups && R.next_first < sc.depth) R.launch_next_first();
+    R.clock.b = R.clock.us();
+    const int rc = R.loop();
+    R.clock.c = R.clock.us();
+    session.close();
+    if (rc) {   // wait for every stream the call used
+        (void)hipStreamSynchronize(s);
+        if (R.late != s) (void)hipStreamSynchronize(R.late);
+        if (R.chain) (void)hipStreamSynchronize(R.chain);
+        ctx->mle_arrivals_zeroed = nullptr;   // (a pass that was given up may have left its counters half way)
+        return rc;
+    }
+    R.clock.d = R.clock.us();
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    if (R.late != s) HIP_TRY(ctx, hipStreamSynchronize(R.late));
+    if (sc.n_dev) {
+        HIP_TRY(ctx, hipStreamSynchronize(R.chain));
+        // (tail == nullptr here: n_out = n, r_off = 0 -- the staging arrays have the caller's layout)
+        memcpy(out_coeffs, R.stage_c, sizeof(gkr_fr) * 2 * (size_t)sc.n_dev * n);
+        memcpy(out_r, R.stage_r, sizeof(gkr_fr) * (size_t)sc.n_dev * n);
+        memcpy(out_len, R.stage_len, sizeof(uint32_t) * (size_t)sc.n_dev * n);
+    }
+    R.clock.e = R.clock.us();
+    if (ctx->pending.size() > 8192) ctx->drain_events();   // otherwise when the profile is read
+    R.clock.report(pool->workers() + 1);
+    return GKR_OK;
+}
+
+// One rank's run of a sumcheck split over ranks.  Everything that can fail locally is set up BEFORE the first exchange; from
+// there on a failure is carried through the remaining exchanges as a flag (rc), so that no rank is left waiting inside a collective.
+namespace {
+struct MleShardRun {
+    gkr_ctx* ctx;
+    const gkr_exchange_dev* exchange;
+    const int n, batch;
+    gkr_fr* out_coeffs;
+    uint32_t* out_len;
+    gkr_fr* out_r;
+    MlePassTables T;   // (rec: device records -- a pass's sums go through the exchange before the host sees them in h_rec)
+    uint32_t* h_fail = nullptr;
+    std::vector<uint32_t> dep_last;
+    gkr::SpinPool* pool = nullptr;
+    int rc = GKR_OK;   // this rank's own failure
+    uint32_t exchanges = 0;
+
+    long long* limbs() const { return reinterpret_cast<long long*>(exchange->d_limbs); }
+    void hook_failed(int arc) {
+        if (arc && !rc) rc = ctx->fail(GKR_ERR_INVALID, "the device sum-over-ranks hook failed (status " + std::to_string(arc) + ")");
+    }
+    bool some_rank_failed() const { return __atomic_load_n(h_fail, __ATOMIC_ACQUIRE) != 0; }
+    void exchange_sums(int J, uint32_t ticket) {
+        hipStream_t s = ctx->stream;
+        Timed t(ctx, "exchange", 0.0);
+        gkr::launch_mle_xwiden(T.rec, (uint32_t)J, (uint32_t)batch, rc ? 1u : 0u, limbs(), s);
+        const int arc = exchange->fn(exchange->user, (size_t)batch * (((size_t)1 << J) + 2) * 8, static_cast<void*>(s));
+        gkr::launch_mle_xnarrow(limbs(), (uint32_t)J, (uint32_t)batch, T.h_rec, ticket, h_fail, s);
+        ++exchanges;
+        hook_failed(arc);
+    }
+    // the 2^m entries every shard has left (rows `stride` apart) -> the tail table of 2^(m + lp) entries, on every rank
+    void gather_tail(const Fr* rest, size_t stride, int m, int lp, int shard, Fr* d_tail) {
+        hipStream_t s = ctx->stream;
+        Timed t(ctx, "exchange", 0.0);
+        gkr::launch_mle_gather_widen(rest, stride, (uint32_t)m, (uint32_t)lp, (uint32_t)shard, rc ? 1u : 0u, (uint32_t)batch, limbs(), s);
+        const int arc = exchange->fn(exchange->user, ((size_t)batch << (m + lp)) * 8 + 8, static_cast<void*>(s));
+        gkr::launch_mle_gather_narrow(limbs(), (uint32_t)(m + lp), (uint32_t)batch, d_tail, h_fail, s);
+        ++exchanges;
+        hook_failed(arc);
+    }
+    // a chunk of sixteen tables: their J rounds on the summed sub-block sums (the same on every rank), and the fold weights
+    void rounds_chunk(int first, int J, int round0) {
+        const int count = batch - first < 16 ? batch - first : 16;
+        uint64_t c0[gkr::kMlePassMaxRounds][16][4], c1[gkr::kMlePassMaxRounds][16][4], r[gkr::kMlePassMaxRounds][16][4];
+        uint32_t ln[gkr::kMlePassMaxRounds][16];
+        (host_ifma_ready() && count >= 3 ? gkr::gkr_ifma_pass : host_pass_scalar)(
+            reinterpret_cast<const uint64_t*>(T.h_rec[first].sums), sizeof(gkr::MleHostRecSub) / 8, count, J, nullptr, c0, c1, r, ln,
+            reinterpret_cast<uint64_t*>(T.h_w + (size_t)first * gkr::kMleMaxSub), 4 * gkr::kMleMaxSub);
+        for (int i = 0; i < count; ++i) {
+            if (round0 == 0) dep_last[first + i] = T.h_rec[first + i].dep;
+            for (int t = 0; t < J; ++t)
+                write_round_output(out_coeffs, out_len, out_r, (size_t)(first + i) * n + round0 + t, c0[t][i], c1[t][i], ln[t][i], r[t][i]);
+        }
+    }
+    void host_rounds(int J, int round0) {
+        std::atomic<int> next{0};
+        const std::function<bool()> work_fn = [&]() -> bool {
+            const int first = next.fetch_add(16, std::memory_order_relaxed);
+            if (first < batch) rounds_chunk(first, J, round0);
+            return first < batch;
+        };
+        gkr::SpinPool::Session session(pool, nullptr);
+        run_pieces(pool, &work_fn, batch > 16);
+    }
+    // one pass (its launches only while this rank is well), its exchange, its rounds
+    void pass(bool pass0, bool from_input, int m_src, int jin, int J, int round0) {
+        const uint32_t ticket = ++ctx->ticket;
+        if (!rc) {
+            MlePassPolicy P;   // (no pass publishes from its last block: arrivals == nullptr; the plan on the pass's own stream)
+            P.row = pass0 ? "mle_sub_sums" : "mle_multifold";
+            if (pass0)
+                queue_pass0(ctx, T, 0, batch, J, ticket, ctx->stream, P);
+            else
+                queue_fold(ctx, T, 0, batch, from_input, m_src, jin, J, ticket, ctx->stream, P);
+            if (hipError_t le = hipGetLastError(); le != hipSuccess) rc = ctx->hip_fail(le, "launch of a sumcheck pass");
+        }
+        exchange_sums(J, ticket);
+        if (!rc) rc = wait_records(ctx, T.h_rec, batch, ticket);
+        if (!rc && some_rank_failed()) rc = ctx->fail(GKR_ERR_HIP, "another rank failed during the sumcheck");
+        if (!rc) host_rounds(J, round0);
+    }
+};
+}  // namespace
+
+}  // namespace gkr_host
+
+extern "C" {
+
+// ---- one plain sumcheck split over ranks, on the multi-round schedule -----------------------------------------------
+// prove_sumcheck (sumcheck.rs:158-214) with the reduce over the hypercube (the rayon reduce of :62) split over P = 2^lp
+// ranks.  Rank p holds, of every table T (2^n entries, variable 1 = most significant index bit), the shard
+//     T_p[h * 2 + x_n] = T[h * 2P + 2p + x_n],   h < 2^(n - lp - 1):
+// the index bits lp .. 1 are the rank, the last variable stays inside every shard.  Rounds bind the leading variable,
+// so every pair (i, i + half) is rank-local while bits of h are bound; the sub-block sums a pass hands the host are
+// linear in the table, so the whole table's 2^J sums are the sums over ranks of the shards' -- ONE all-reduce of
+// 2^J (+ 2 flags) field elements per pass of J <= 5 rounds (n = 20 on 8 ranks: 3 exchanges + the gather, not 20), queued
+// on the library's stream through the caller's gkr_exchange_dev; every rank then runs the same J rounds on the same
+// sums and derives the same weights, no broadcast.  When 2^6 entries per shard are left they are gathered (one more
+// all-reduce, of zero-padded buffers) into a tail table of 2^(6 + lp) entries on which every rank finishes the last
+// rounds redundantly.  "Does T depend on x_n" (the last round's length, sumcheck.rs:206-207) is the OR over ranks of
+// a neighbour compare inside each shard -- exact, no shard is compared across ranks.
+size_t gkr_exchange_limbs_mle(int n, int log2_shards, int batch) {
+    if (n < 2 || log2_shards < 0 || log2_shards > 16 || n - log2_shards < 1 || n - log2_shards > GKR_MAX_MLE_N || batch < 1) return 0;
+    const int nl = n - log2_shards, t = nl < kMleShardTailLog2 ? nl : kMleShardTailLog2;
+    const size_t per_pass = (size_t)batch * (gkr::kMleMaxSub + 2) * 8, gather = ((size_t)batch << (t + log2_shards)) * 8 + 8;
+    return per_pass > gather ? per_pass : gather;
+}
+
+int gkr_sumcheck_mle_sharded_dev(gkr_ctx* ctx, const void* d_shards, int n, int log2_shards, int shard, int batch,
+                                 const gkr_exchange_dev* exchange, gkr_fr* out_coeffs, uint32_t* out_len, gkr_fr* out_r,
+                                 uint32_t* out_exchanges) {
+    if (!ctx) return GKR_ERR_INVALID;
+    if (!d_shards || !exchange || !exchange->fn || !exchange->d_limbs || !out_coeffs || !out_len || !out_r || batch < 1 || batch > 65535)
+        return ctx->fail(GKR_ERR_INVALID, "null pointer or batch out of range [1, 65535]");
+    const int lp = log2_shards, nl = n - lp;
+    if (lp < 0 || lp > 16 || shard < 0 || shard >= (1 << lp)) return ctx->fail(GKR_ERR_INVALID, "shard must be in [0, 2^log2_shards), log2_shards in [0, 16]");
+    if (n < 2 || nl < 1 || nl > GKR_MAX_MLE_N) return ctx->fail(GKR_ERR_INVALID, "n >= 2 and 1 <= n - log2_shards <= GKR_MAX_MLE_N needed");
+    if (ctx->transcript != GKR_TRANSCRIPT_HOST) return ctx->fail(GKR_ERR_INVALID, "a sumcheck split over ranks needs the host transcript");
+    if (exchange->capacity < gkr_exchange_limbs_mle(n, lp, batch)) return ctx->fail(GKR_ERR_INVALID, "the exchange buffer is smaller than gkr_exchange_limbs_mle(n, log2_shards, batch) int64");
+    GKR_ENTER(ctx);
+    hipStream_t s = ctx->stream;
+    const size_t len = (size_t)1 << nl;
+    const int t_stop = nl < kMleShardTailLog2 ? nl : kMleShardTailLog2;   // variables every shard keeps for the gathered tail
+    const int jmax = gkr::opt(gkr::OPT_no_mfma_fold) ? 3 : gkr::kMlePassMaxRounds;
+    auto rounds_for = [&](int m) {
+        int j = mle_pass_rounds(m, nl, jmax);
+        if (m - j < t_stop) j = m - t_stop;
+        return j;
+    };
+    MleShardRun R{ctx, exchange, n, batch, out_coeffs, out_len, out_r};
+    MlePassTables& T = R.T;
+    Fr* d_tail = nullptr;
+    const int j_first = nl > t_stop ? rounds_for(nl) : 0;
+    if (int rc = mle_pass_tables(ctx, "mlex", static_cast<const Fr*>(d_shards), len, j_first ? len >> j_first : 1, batch, T)) return rc;
+    WS(ctx, "mlex.tail", Fr, (size_t)batch << (t_stop + lp), d_tail);
+    WS(ctx, "mlex.drec", gkr::MleHostRecSub, (size_t)batch, T.rec);
+    HIP_TRY(ctx, ctx->pinned_host("mlex.fail", 64, reinterpret_cast<void**>(&R.h_fail)));
+    *R.h_fail = 0;
+    R.dep_last = std::vector<uint32_t>(batch, 0);
+    R.pool = batch >= 32 ? ctx->host_pool() : nullptr;
+    // ---- the rank-local rounds: n - lp - t_stop of them, in passes
+    int m = nl, round0 = 0, jin = 0;
+    while (m - jin > t_stop) {
+        m -= jin;
+        const int J = rounds_for(m);
+        R.pass(jin == 0, round0 == jin, m + jin, jin, J, round0);   // (pass 0 -- sums only -- and the first fold read the input shards)
+        round0 += J;
+        jin = J;
+    }
+    // ---- bind the last pass's variables (2^t_stop entries per shard are left), gather the tail
+    m -= jin;
+    const bool folded = jin && !R.rc;
+    if (folded) {
+        MlePassPolicy P;
+        P.row = "mle_multifold";
+        queue_fold(ctx, T, 0, batch, round0 == jin, m + jin, jin, 1, ++ctx->ticket, s, P);   // (one pass so far: its sums came from the input shards)
+        if (hipError_t le = hipGetLastError(); le != hipSuccess) R.rc = ctx->hip_fail(le, "launch of the last rank-local fold");
+    }
+    R.gather_tail(folded ? T.work : T.input, folded ? T.work_len : len, m, lp, shard, d_tail);
+    if (out_exchanges) *out_exchanges = R.exchanges;
+    {
+        const hipError_t se = hipStreamSynchronize(s);   // the tail is complete, the flag has landed
+        if (se != hipSuccess && !R.rc) R.rc = ctx->hip_fail(se, "hipStreamSynchronize after the gather");
+    }
+    if (!R.rc && R.some_rank_failed()) R.rc = ctx->fail(GKR_ERR_HIP, "another rank failed during the sumcheck");
+    if (R.rc) return R.rc;
+    ctx->drain_events();
+    // ---- the last t_stop + lp rounds on the gathered tail, the same on every rank
+    MleTailArgs tail;
+    tail.n_total = n;
+    tail.round_offset = round0;
+    tail.dep_last = round0 ? R.dep_last.data() : nullptr;   // (no rank-local round: the tail is the whole table, its own neighbour compare decides)
+    return run_mle_batch_passes(ctx, d_tail, m + lp, batch, out_coeffs, out_len, out_r, &tail);
+}
+
+}  // extern "C"

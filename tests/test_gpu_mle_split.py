@@ -57,6 +57,19 @@ def test_split_sumcheck_small_and_edge_tables(nshards):
     del rng
 
 
+@pytest.mark.parametrize("batch", [17, 40])
+@pytest.mark.parametrize("n", [9, 14])
+def test_split_sumcheck_batches_across_hash_chunks(n, batch):
+    """The host rounds of a split sumcheck go out in chunks of sixteen tables: batch 17 is a full chunk and a chunk of one
+    (the scalar pass function), batch 40 two full chunks and a ragged third, shared with the host pool.  The tables at
+    index 16 and at the end do not depend on the last variable, so the last round's length differs inside a chunk."""
+    tables = np.stack([cdense.fill_table(1 << n, 7000 + 13 * n + b) for b in range(batch)])
+    for b in (16, batch - 1):
+        tables[b] = np.repeat(cdense.fill_table(1 << (n - 1), 7500 + 13 * n + b), 2, axis=0)
+    got = parallel.prove_sumcheck_logical_dev(0, tables, n, 2)
+    _check(got, tables, n)
+
+
 def test_split_sumcheck_limits_and_errors():
     with Context(0) as ctx:
         ex = parallel.NoExchange(ctx, parallel.exchange_limbs_mle(10, 0, 1))

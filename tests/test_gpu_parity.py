@@ -122,14 +122,15 @@ def test_mle_extreme_byte_patterns_match_oracle(ctx, n):
                                  {"GKR_NO_FUSED_REDUCE": "1"}, {"GKR_NO_FUSED_REDUCE": "1", "GKR_NO_MFMA_FOLD": "1"},
                                  {"GKR_DEVICE_HASH_PERCENT": "50"}, {"GKR_DEVICE_HASH_PERCENT": "90", "GKR_ROUNDS_PER_PASS": "3"},
                                  {"GKR_NO_LATE_STREAM": "1"}, {"GKR_FOLD_MIN_CHUNK": "64"}, {"GKR_FOLD_MIN_CHUNK": "4096"},
-                                 {"GKR_ITEMS_PER_BLOCK": "256"}, {"GKR_ITEMS_PER_BLOCK": "768"}],
+                                 {"GKR_ITEMS_PER_BLOCK": "256"}, {"GKR_ITEMS_PER_BLOCK": "768"},
+                                 {"GKR_MLE_PER_ROUND": "1"}, {"GKR_MLE_PER_ROUND": "1", "GKR_GROUP_SIZE": "3"}],
                          ids=lambda e: ",".join("%s=%s" % kv for kv in e.items()))
 def test_fold_pass_variants_match_oracle(env):
     """Every schedule of the host-transcript sumcheck gives the same transcript: the v_mad_u64_u32 fold instead
     of the matrix-core one, 1 / 3 / 4 rounds per pass instead of 5, sixteen-lane and scalar host hashing, other
     block counts, many small groups with pass 0 queued one at a time or all at once, part of the batch hashed ON THE DEVICE
-    (MiMC7 on eight lanes per element, the whole chain of passes without the host).  The knobs are read once per process,
-    hence the child interpreter."""
+    (MiMC7 on eight lanes per element, the whole chain of passes without the host), one round per pass with several groups
+    racing for their hashes.  The knobs are read once per process, hence the child interpreter."""
     import os
     import subprocess
     import sys
@@ -139,6 +140,10 @@ def test_fold_pass_variants_match_oracle(env):
         # a share of the batch hashed on the device (kernels_transcript.hip; batches of >= 64): one-block passes only,
         # every kind of pass, a ragged last wave of eight-lane groups, the long first pass
         sizes = ((6, 100), (10, 72), (14, 99), (17, 64), (20, 64))
+    if "GKR_MLE_PER_ROUND" in env:
+        # the per-round host driver with more than one group: (8, 130) is four groups, or 44 asked for and cut to the 32 the
+        # driver allows; n = 14 runs the first-round sums, the streaming fold and the one-block fold
+        sizes = ((8, 130), (14, 20), (17, 3))
     for n, batch in sizes:
         out = subprocess.run([sys.executable, os.path.join(here, "fold_variants_worker.py"), str(n), str(batch)],
                              env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
