@@ -1,8 +1,9 @@
 // Internals shared by the translation units of the C ABI (gkr_capi.hip: contexts, transcript helpers, self-tests, device
 // memory; capi_mle.hip: the plain sumcheck's entry points, per-round schedules and sessions; capi_mle_passes.hip: its multi-round
 // schedule, whole tables and tables split over ranks; capi_layer.hip: the layer sumcheck over gate lists; capi_layer_dense.hip:
-// its dense form; capi_prove.hip: whole proofs): the context, its caches and workspaces, profiling brackets, the host
-// transcript's helpers, the hand-off wait, the plain sumcheck's group hand-off.  Not a public header.
+// its dense form; capi_prove.hip: whole proofs; capi_product.hip: the sumcheck over a product of resident tables): the context,
+// its caches and workspaces, profiling brackets, the host transcript's helpers, the hand-off wait, the plain sumcheck's group
+// hand-off.  Not a public header.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <sched.h>

@@ -241,6 +241,28 @@ void launch_mle_round_hash(const MlePartial* partials, uint32_t nblk, uint32_t r
                            const Fr* cts, Fr* out_coeffs, uint32_t* out_len, Fr* out_r, FixedMul* rtab,
                            uint32_t* dep_last, hipStream_t s);
 
+// ---- sumcheck over a product of `degree` <= kProductMaxDegree resident tables (kernels_product.hip) ----
+// One pass leaves per block degree + 1 exact values of the round polynomial (scaled, see the kernels) and, in round 1, the
+// factors' flags; one wave per sumcheck and round turns them into the round vector, hashes it and publishes r.
+// Launch geometry: mle_blocks_per_table(h or q, batch) blocks per sumcheck, as the plain sumcheck's passes.
+constexpr int kProductMaxDegree = 3;
+struct ProductPartial {
+    Acc<9> s[kProductMaxDegree + 1];
+    uint32_t flags, pad[3];
+};
+// factor f of sumcheck b at tables + (b * degree + f) * table_stride; h = half a table
+void launch_product_first(int degree, const Fr* tables, size_t table_stride, uint32_t h, uint32_t batch, uint32_t nblk,
+                          ProductPartial* partials, hipStream_t s);
+// src: 4q entries per factor, dst: 2q (dst == src with equal strides: in place); rtab[b * r_stride]: r of the round before
+void launch_product_fold_sum(int degree, const Fr* src, size_t src_stride, Fr* dst, size_t dst_stride, uint32_t q, uint32_t batch,
+                             uint32_t nblk, const FixedMul* rtab, uint32_t r_stride, ProductPartial* partials, hipStream_t s);
+// out_coeffs: batch x n rows of degree + 1 slots; out_len, out_r, rtab: batch x n; meta: batch words (written in round 0, read
+// in round n - 1); evals: batch x degree, written in round n - 1 from the factors' two remaining entries at work + (b * degree +
+// f) * work_stride
+void launch_product_round(int degree, const ProductPartial* partials, uint32_t nblk, uint32_t round, uint32_t n, uint32_t batch,
+                          const Fr* cts, const Fr* work, size_t work_stride, Fr* out_coeffs, uint32_t* out_len, Fr* out_r,
+                          FixedMul* rtab, uint32_t* meta, Fr* evals, hipStream_t s);
+
 void launch_layer_eval(uint32_t gates, const uint8_t* gate_type, const uint32_t* left, const uint32_t* right,
                        const Fr* prev, Fr* out, uint32_t batch, uint32_t prev_stride, hipStream_t s, const GateSet* sets = nullptr);
 // words 32-bit words src -> dst (16-byte aligned when words >= 4); either side may be pinned host memory

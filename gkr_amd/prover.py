@@ -345,6 +345,42 @@ class Context:
         C, L, R = self.sumcheck_mle_raw(as_limbs(table), v)
         return [from_limbs(C[j])[2 - int(L[j]):] for j in range(v)], from_limbs(R)
 
+    # -- sumcheck over a product of tables (prove_sumcheck on mult_poly of the tables' extensions; sumcheck.rs:158-214, poly.rs:349-386)
+    def sumcheck_product_batch_device(self, d_tables, n, degree, batch, out=None):
+        """gkr_sumcheck_product_batch_device: `batch` sumchecks over the product of `degree` resident tables of 2^n entries each
+        (factor f of sumcheck b at d_tables + (b * degree + f) * 2^n elements; not modified).  -> (C, L, R, E): C (batch, n,
+        degree + 1, 4) right-aligned round vectors, highest degree first; L (batch, n) lengths; R (batch, n, 4) challenges; E
+        (batch, degree, 4) the factors' values at the challenges.  out: the four arrays of an earlier call to write into."""
+        if out is not None:
+            C, L, R, E = out
+            if C.shape != (batch, n, degree + 1, 4) or L.shape != (batch, n) or R.shape != (batch, n, 4) or E.shape != (batch, degree, 4):
+                raise GkrError(N.GKR_ERR_INVALID, "output arrays do not match (batch, n, degree)")
+        else:
+            C = np.zeros((batch, n, max(degree, 0) + 1, 4), dtype=np.uint64)
+            L = np.zeros((batch, n), dtype=np.uint32)
+            R = np.zeros((batch, n, 4), dtype=np.uint64)
+            E = np.zeros((batch, max(degree, 1), 4), dtype=np.uint64)
+        self._check(N.lib().gkr_sumcheck_product_batch_device(self._h, d_tables, n, degree, batch, _ptr(C), _ptr(L), _ptr(R), _ptr(E)))
+        return C, L, R, E
+
+    def prove_sumcheck_product(self, tables, v):
+        """Sumcheck of sum_x prod_f tables[f](x) over {0,1}^v: tables is a list of 1 .. 3 tables of 2^v values.
+        -> (proof, r, evals): proof[j] the round vector (its used slots, highest degree first, 1 .. len(tables) + 1 of them), r
+        the challenges, evals[f] = tables[f]~(r), the factor's multilinear extension at the challenges.
+        A verifier (verifier.verify_sumcheck_product) ends on proof[-1](r[-1]) == prod evals; that evals are the tables' values
+        is the caller's to establish: verifier.mle_eval(tables[f], r) on the host, or Context.mle_eval_batch_device on resident
+        tables -- the `degree` factors of one sumcheck are a batch of `degree` tables at the same point."""
+        degree = len(tables)
+        limbs = np.concatenate([as_limbs(t) for t in tables], axis=0) if degree else np.zeros((0, 4), dtype=np.uint64)
+        if limbs.shape[0] != degree << v:
+            raise GkrError(N.GKR_ERR_INVALID, "every table must have 2^v values")
+        C = np.zeros((v, degree + 1, 4), dtype=np.uint64)
+        L = np.zeros(v, dtype=np.uint32)
+        R = np.zeros((v, 4), dtype=np.uint64)
+        E = np.zeros((max(degree, 1), 4), dtype=np.uint64)
+        self._check(N.lib().gkr_sumcheck_product(self._h, _ptr(limbs), v, degree, _ptr(C), _ptr(L), _ptr(R), _ptr(E)))
+        return [from_limbs(C[j])[degree + 1 - int(L[j]):] for j in range(v)], from_limbs(R), from_limbs(E[:degree])
+
     # -- the plain sumcheck's verifier (verify_sumcheck, python/sumcheck.py:55-70, plus g_n(r_n) = T(r)) and the evaluation behind it
     def mle_eval_batch_device(self, d_tables, n, batch, points):
         """gkr_mle_eval_batch_device: the multilinear extension of each of `batch` resident tables of 2^n entries at its own point.
@@ -630,3 +666,7 @@ def prove_sumcheck_opt(layer: Layer, k_next, z, W):
 
 def prove_sumcheck(table, v):
     return default_context().prove_sumcheck(table, v)
+
+
+def prove_sumcheck_product(tables, v):
+    return default_context().prove_sumcheck_product(tables, v)

@@ -94,6 +94,30 @@ def verify_sumcheck_table(table: List[int], rounds: List[List[int]], challenges:
     return ok and last == mle_eval(table, [r % P for r in challenges])
 
 
+def verify_sumcheck_product(rounds: List[List[int]], challenges: List[int], evals: List[int], degree: int, claim=None, hashes=None) -> bool:
+    """The verifier of a product sumcheck's transcript (Context.prove_sumcheck_product) on plain integers: every round vector
+    has 1 .. degree + 1 coefficients, python/sumcheck.py:55-70 holds on the claim (the first round vector's own sum when none
+    is given), and g_n(r_n) == prod evals.  That evals[f] is factor f's multilinear extension at the challenges is NOT checked
+    here: mle_eval(table_f, challenges) on the host, or Context.mle_eval_batch_device on resident tables.
+    hashes: multi_hash(rounds[j], 0) for every j, computed by the caller (many transcripts: all their round vectors in one
+    Context.multi_hash_batch call); None: hashed here, one vector at a time."""
+    if len(rounds) < 1 or len(rounds) != len(challenges) or len(evals) != degree:
+        return False
+    if any(not 1 <= len(g) <= degree + 1 for g in rounds) or (hashes is not None and len(hashes) != len(rounds)):
+        return False
+    expected = (eval_univariate(rounds[0], 0) + eval_univariate(rounds[0], 1) if claim is None else claim) % P
+    for j, (g, r) in enumerate(zip(rounds, challenges)):
+        if (eval_univariate(g, 0) + eval_univariate(g, 1)) % P != expected:
+            return False
+        if (multi_hash(g, 0) if hashes is None else hashes[j] % P) != r % P:
+            return False
+        expected = eval_univariate(g, r)
+    prod = 1
+    for e in evals:
+        prod = prod * e % P
+    return expected == prod
+
+
 def verify(proof: Proof, circuit: GKRCircuit) -> bool:
     """python/gkr.py:202-231 on the Rust-shaped proof."""
     L = circuit.depth()

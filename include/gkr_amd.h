@@ -283,6 +283,36 @@ int  gkr_sumcheck_mle(gkr_ctx *ctx, const gkr_fr *table, int n, gkr_fr *out_coef
 int  gkr_sumcheck_mle_batch_device(gkr_ctx *ctx, const void *d_tables, int n, int batch,
                                    gkr_fr *out_coeffs, uint32_t *out_len, gkr_fr *out_r);
 
+/* ---- sumcheck over a product of resident multilinear tables: prove_sumcheck(g, v) with
+ * g = mult_poly(get_multi_ext(T_0), .., get_multi_ext(T_{degree-1})) (sumcheck.rs:158-214, poly.rs:349-386) ----
+ * Inner products sum_x A(x) B(x), zero-checks sum_x eq(x) A(x) B(x), a GKR layer written densely.  degree = 1 is the plain
+ * sumcheck's transcript.  `batch` independent sumchecks over `degree` tables of 2^n canonical values each (variable 1 = most
+ * significant index bit), resident in device memory: factor f of sumcheck b starts at d_tables + (b * degree + f) * 2^n
+ * elements.  Inputs are not modified; the folded halves live in context workspace of batch * degree * 2^(n-1) elements.
+ *   out_coeffs  batch x n rows of degree + 1 slots, right-aligned, highest degree first, unused slots zero
+ *   out_len     batch x n values in 1 .. degree + 1.  Rounds 1 .. n-1: leading zero coefficients dropped, one kept at least
+ *               (add_poly merges by exponent, poly.rs:324-327); round n: 1 + the number of factors that depend on x_n (no
+ *               merge, sumcheck.rs:206-207)
+ *   out_r       batch x n challenges, r_j = multi_hash(round vector j, key 0)
+ *   out_evals   batch x degree values T_f~(r_1 .. r_n) -- the one entry each factor has left after the last fold, which the
+ *               prover has for free -- or NULL.  A verifier's last check is g_n(r_n) = prod_f out_evals[f]; binding the values
+ *               to the tables is one call of the evaluation entry point above on the same resident tables.
+ * A factor that is the zero table makes g the empty term list, on which the reference panics (partial_eval indexes f[0],
+ * poly.rs:236); as the library's OWN choice such a sumcheck returns every round vector as [0] with length 1.
+ * The challenges are hashed on the device in both transcript modes (one launch per round, no host round trip): the result
+ * does not depend on the context's transcript mode.
+ * GKR_ERR_INVALID before a device or the context is touched (plain returns; the context's last error is left as it was): NULL
+ * ctx or pointer (out_evals excepted), batch outside 1 .. 65535, n outside 2 .. GKR_MAX_MLE_N, degree outside
+ * 1 .. GKR_PRODUCT_MAX_DEGREE, batch * degree * 2^n above 2^30 values. */
+#define GKR_PRODUCT_MAX_DEGREE 3
+int  gkr_sumcheck_product_batch_device(gkr_ctx *ctx, const void *d_tables, int n, int degree, int batch,
+                                       gkr_fr *out_coeffs, uint32_t *out_len, gkr_fr *out_r, gkr_fr *out_evals);
+
+/* `degree` tables of 2^n values in host memory, one after the other: upload + the call above with batch 1.
+ * GKR_ERR_NON_CANONICAL for an entry >= r. */
+int  gkr_sumcheck_product(gkr_ctx *ctx, const gkr_fr *tables, int n, int degree,
+                          gkr_fr *out_coeffs, uint32_t *out_len, gkr_fr *out_r, gkr_fr *out_evals);
+
 /* ---- the plain sumcheck's verifier: verify_sumcheck, python/sumcheck.py:55-70, and the relation behind it -------------
  * A transcript of prove_sumcheck proves "sum of the table = claim" only together with g_n(r_n) = T~(r_1 .. r_n), the table's
  * multilinear extension at the challenges: one read of the table (32 * 2^n bytes, where the prover's default schedule moves
