@@ -743,9 +743,12 @@ int run_layer_dense(gkr_ctx* ctx, int batch, int k_i, int k, const uint8_t* d_gt
                     const Fr* d_W, gkr_fr* const* out_coeffs, uint32_t* const* out_len, gkr_fr* const* out_r);
 // ---- defined in capi_verify.hip
 // does a chunk of `rows` round vectors hash on the device (option verify_device_hash_min)?  and THE launcher of the hash kernel:
-// n rows of three right-aligned slots and their lengths, in device memory -> their slots in device memory, on stream s
+// n rows of `slots` (3 or 4) right-aligned slots and their lengths, in device memory -> their slots in device memory, on stream s
 bool verify_device_hash_wanted(size_t rows);
-int verify_hash_rows_device(gkr_ctx* ctx, const uint32_t* d_rows, const uint32_t* d_len, size_t n, gkr::VerifyHashSlot* d_slots, hipStream_t s);
+int verify_hash_rows_device(gkr_ctx* ctx, int slots, const uint32_t* d_rows, const uint32_t* d_len, size_t n, gkr::VerifyHashSlot* d_slots, hipStream_t s);
+// ---- defined in capi_product.hip
+// the shapes gkr_sumcheck_product* and gkr_sumcheck_product_verify* admit (batch itself, 1 .. 65535, is the caller's check)
+bool product_shape_ok(int n, int degree, int batch);
 // ---- defined in capi_prove.hip
 void mobius_msb(std::vector<gkr::h64::F>& c, int k);
 void line_restriction(const std::vector<gkr::h64::F>& vals, const std::vector<gkr::h64::F>& coeffs, int k, const gkr_fr* b, const gkr_fr* c,

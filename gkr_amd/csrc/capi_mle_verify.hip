@@ -1,5 +1,7 @@
-// The plain sumcheck's verifier and the multilinear evaluation behind it: gkr_mle_eval_batch_device,
-// gkr_sumcheck_mle_verify_batch_device, gkr_sumcheck_mle_verify.
+// The plain and the product sumcheck's verifier and the multilinear evaluation behind them: gkr_mle_eval_batch_device,
+// gkr_sumcheck_mle_verify_batch_device, gkr_sumcheck_mle_verify, gkr_sumcheck_product_verify_batch_device,
+// gkr_sumcheck_product_verify.  ONE driver, parametrised by the degree D of the round polynomials: rows of D + 1 slots, D tables
+// per transcript (the plain sumcheck is D = 1), the last relation g_n(r_n) = prod_f T_f(r_1 .. r_n); what follows says T for all D.
 //
 // verify_sumcheck (python/sumcheck.py:55-70) is O(n) per transcript; what makes a transcript of prove_sumcheck checkable is the
 // relation behind it, g_n(r_n) = T(r_1 .. r_n), one pass over the table.  A verifier reads every challenge out of the transcript,
@@ -8,9 +10,10 @@
 //   1. the points (the transcripts' challenges) go up in ONE copy and the evaluation is launched (kernels_mle_eval.hip: a few
 //      set-up launches for the chunk, one streaming read of every table, the second-level sums; one copy back);
 //   2. the chunk's batch x n challenge hashes start: a chunk of at least verify_device_hash_min round vectors sends them to the
-//      device (k_verify_hash through capi_verify.hip's launcher, on the side stream beside the evaluation; the rows are repacked
-//      from the plain sumcheck's two slots to the kernel's three on the way into the staging buffer), a smaller one hashes on
-//      the context's host threads.  Both fill the same slots by the same rule, so verdicts do not depend on where the hashes ran;
+//      device (k_verify_hash through capi_verify.hip's launcher, on the side stream beside the evaluation; rows of two slots are
+//      repacked to the kernel's three on the way into the staging buffer, rows of three and four go as they are), a smaller one
+//      hashes on the context's host threads.  Both fill the same slots by the same rule, so verdicts do not depend on where the
+//      hashes ran;
 //   3. meanwhile the host threads run everything that needs neither: shape, canonical checks, the round sums and the Horner
 //      steps of every transcript (pre_relations);
 //   4. ONE synchronisation, then per transcript the challenge comparisons and the last relation (finish).
@@ -32,10 +35,17 @@ struct HashSlot {
 };
 static_assert(sizeof(HashSlot) == sizeof(gkr::VerifyHashSlot) && offsetof(HashSlot, valid) == offsetof(gkr::VerifyHashSlot, valid),
               "the kernel writes the slots the relations read");
-constexpr size_t kHashRowWords = 24;          // the hash kernel's rows: three right-aligned slots
 constexpr int kRelPiece = 8, kHashPiece = 16; // transcripts / round vectors per piece of host work
+constexpr int kMaxWidth = GKR_PRODUCT_MAX_DEGREE + 1;
+static_assert(kMaxWidth == 4, "the hash kernel has rows of three and of four slots");
 
-// what the host knows about a transcript before the hashes and the device's value are there
+// ONE driver for both verifiers, parametrised by the degree D of the round polynomials: a transcript's rows have D + 1
+// right-aligned slots and it is tied to D resident tables (the plain sumcheck: D = 1, its table; the product: its D factors,
+// next to each other).  The hash kernel's rows have three slots up to D = 2 and four at D = 3.
+inline size_t row_width(int degree) { return (size_t)degree + 1; }
+inline int hash_slots(int degree) { return degree <= 2 ? 3 : 4; }
+
+// what the host knows about a transcript before the hashes and the device's values are there
 struct Pre {
     uint32_t check = 0, round = 0;   // the first failure among checks 1 and 2 (check 0: none)
     uint32_t sum_round = 0;          // the first round whose sum check fails (n: none)
@@ -43,11 +53,12 @@ struct Pre {
     F proved = {{0, 0, 0, 0}};       // g_1(0) + g_1(1)
 };
 
-Pre pre_relations(int n, const gkr_fr* claim, const gkr_fr* coeffs, const uint32_t* len, const gkr_fr* r) {
+Pre pre_relations(int n, int degree, const gkr_fr* claim, const gkr_fr* coeffs, const uint32_t* len, const gkr_fr* r) {
+    const uint32_t W = (uint32_t)row_width(degree);
     Pre p;
     p.sum_round = (uint32_t)n;
     for (int j = 0; j < n; ++j)
-        if (len[j] < 1 || len[j] > 2) {
+        if (len[j] < 1 || len[j] > W) {
             p.check = GKR_VERIFY_SHAPE;
             p.round = (uint32_t)j;
             return p;
@@ -58,7 +69,7 @@ Pre pre_relations(int n, const gkr_fr* claim, const gkr_fr* coeffs, const uint32
     }
     for (int j = 0; j < n; ++j) {
         bool ok = V::canonical(r[j]);
-        for (uint32_t t = 2 - len[j]; t < 2; ++t) ok = ok && V::canonical(coeffs[2 * j + t]);
+        for (uint32_t t = W - len[j]; t < W; ++t) ok = ok && V::canonical(coeffs[W * j + t]);
         if (!ok) {
             p.check = GKR_VERIFY_NON_CANONICAL;
             p.round = (uint32_t)j;
@@ -67,10 +78,9 @@ Pre pre_relations(int n, const gkr_fr* claim, const gkr_fr* coeffs, const uint32
     }
     F running = claim ? V::load(*claim) : F{{0, 0, 0, 0}};
     for (int j = 0; j < n; ++j) {
-        const gkr_fr* g = coeffs + 2 * j + (2 - len[j]);
-        const F c0 = V::load(g[len[j] - 1]);
-        F sum = gkr::h64::add(c0, c0);                                  // g(0) + g(1) = 2 c0 (+ c1)
-        if (len[j] == 2) sum = gkr::h64::add(sum, V::load(g[0]));
+        const gkr_fr* g = coeffs + W * j + (W - len[j]);
+        F sum = V::load(g[len[j] - 1]);                                  // g(0) + g(1) = 2 c_0 + c_1 + .. over the used slots
+        for (uint32_t t = 0; t < len[j]; ++t) sum = gkr::h64::add(sum, V::load(g[t]));
         if (j == 0) p.proved = sum;
         if ((j > 0 || claim) && !V::same(sum, running)) {
             p.sum_round = (uint32_t)j;
@@ -82,27 +92,27 @@ Pre pre_relations(int n, const gkr_fr* claim, const gkr_fr* coeffs, const uint32
     return p;
 }
 
-// the host's rule for a slot -- the kernel's, restated for rows of two slots
-void hash_slot(const gkr_fr* row, uint32_t len, HashSlot* slot) {
+// the host's rule for a slot -- the kernel's, restated for rows of `width` slots
+void hash_slot(const gkr_fr* row, uint32_t width, uint32_t len, HashSlot* slot) {
     slot->valid = 0;
-    if (len < 1 || len > 2) return;
-    F v[2];
+    if (len < 1 || len > width) return;
+    F v[kMaxWidth];
     for (uint32_t t = 0; t < len; ++t) {
-        if (!V::canonical(row[2 - len + t])) return;
-        v[t] = V::load(row[2 - len + t]);
+        if (!V::canonical(row[width - len + t])) return;
+        v[t] = V::load(row[width - len + t]);
     }
     const F h = host_multi_hash(v, (int)len, host_mimc_constants64());
     memcpy(slot->h.l, h.l, 32);
     slot->valid = 1;
 }
 
-// the verdict of one transcript from what the host found, its hash slots and the device's T(r)
-int finish(gkr_ctx* ctx, int n, const Pre& p, const HashSlot* slots, const gkr_fr* r, const Fr& value, int* accept, uint32_t* failed_round,
-           uint32_t* failed_check) {
+// the verdict of one transcript from what the host found, its hash slots and the device's values T_f(r) of its `degree` tables
+int finish(gkr_ctx* ctx, int n, int degree, const Pre& p, const HashSlot* slots, const gkr_fr* r, const Fr* values, int* accept,
+           uint32_t* failed_round, uint32_t* failed_check) {
     uint32_t check = p.check, round = p.round;
     if (!check) {
         for (uint32_t j = 0; j < (uint32_t)n && j < p.sum_round && !check; ++j) {
-            if (!slots[j].valid) return ctx->fail(GKR_ERR_HIP, "gkr_sumcheck_mle_verify: no hash for a well-formed round vector");
+            if (!slots[j].valid) return ctx->fail(GKR_ERR_HIP, "sumcheck verifier: no hash for a well-formed round vector");
             if (memcmp(slots[j].h.l, r[j].l, 32) != 0) {
                 check = GKR_VERIFY_CHALLENGE;
                 round = j;
@@ -112,9 +122,18 @@ int finish(gkr_ctx* ctx, int n, const Pre& p, const HashSlot* slots, const gkr_f
             check = GKR_VERIFY_ROUND_SUM;
             round = p.sum_round;
         }
-        if (!check && memcmp(p.last.l, &value, 32) != 0) {
-            check = GKR_VERIFY_EVALUATION;
-            round = (uint32_t)n;
+        if (!check) {
+            F prod;                                                      // canonical values: a b = mont_mul(to_mont(a), b)
+            memcpy(prod.l, &values[0], 32);
+            for (int f = 1; f < degree; ++f) {
+                F v;
+                memcpy(v.l, &values[f], 32);
+                prod = gkr::h64::mont_mul(gkr::h64::to_mont(prod), v);
+            }
+            if (!V::same(p.last, prod)) {
+                check = GKR_VERIFY_EVALUATION;
+                round = (uint32_t)n;
+            }
         }
     }
     *accept = check == 0 ? 1 : 0;
@@ -136,37 +155,40 @@ int alloc_status(gkr_ctx* ctx, hipError_t e, const char* what) {
         if (_e != hipSuccess) return alloc_status(ctx, _e, slot);                                   \
     } while (0)
 
-// tables of a chunk: what fits verify_workspace_mb (a table's share: its plan, weights, half tables, partials, point, hash rows)
-size_t chunk_tables(int n, int batch, bool hashes) {
+// sumchecks of a chunk: what fits verify_workspace_mb.  A sumcheck's share: per table its plan, weights, half tables, partials,
+// point and value; its n hash rows.  The `degree` tables of a sumcheck are never split over two chunks.
+size_t chunk_tables(int n, int degree, int batch, bool hashes) {
     long long mb = gkr::opt(gkr::OPT_verify_workspace_mb);
     if (mb <= 0) mb = 2048;
-    const size_t one = gkr::mle_eval_ws_bytes((uint32_t)n, 1) + (size_t)n * sizeof(Fr) + sizeof(Fr) +
-                       (hashes ? (size_t)n * (kHashRowWords * sizeof(uint32_t) + sizeof(uint32_t) + sizeof(gkr::VerifyHashSlot)) : 0);
+    const size_t hash_row = (size_t)hash_slots(degree) * 8 * sizeof(uint32_t);
+    const size_t one = (size_t)degree * (gkr::mle_eval_ws_bytes((uint32_t)n, 1) + (size_t)n * sizeof(Fr) + sizeof(Fr)) +
+                       (hashes ? (size_t)n * (hash_row + sizeof(uint32_t) + sizeof(gkr::VerifyHashSlot)) : 0);
     const size_t chunk = ((size_t)mb << 20) / one;
-    return std::max<size_t>(1, std::min<size_t>({chunk, 32768, (size_t)batch}));   // (the table is a grid dimension of the launches)
+    return std::max<size_t>(1, std::min<size_t>({chunk, (size_t)32768 / degree, (size_t)batch}));   // (the table is a grid dimension of the launches)
 }
 
-// the device side of a chunk, queued on the main stream: points up (h_pts: pinned, nb x n), evaluation, values down (h_out: pinned)
-int queue_eval(gkr_ctx* ctx, const Fr* d_tables, int n, uint32_t nb, const Fr* h_pts, Fr* h_out) {
+// the device side of a chunk, queued on the main stream: points up (h_pts: pinned, one per table: nt x n), the evaluation of
+// the chunk's nt = sumchecks x degree tables, values down (h_out: pinned)
+int queue_eval(gkr_ctx* ctx, const Fr* d_tables, int n, uint32_t nt, const Fr* h_pts, Fr* h_out) {
     Fr *d_pts, *d_out;
     void* d_ws;
-    MLEV_WS(ctx, "mlev_pts", (size_t)nb * n * sizeof(Fr), d_pts);
-    MLEV_WS(ctx, "mlev_out", (size_t)nb * sizeof(Fr), d_out);
-    MLEV_WS(ctx, "mlev_ws", gkr::mle_eval_ws_bytes((uint32_t)n, nb), d_ws);
-    HIP_TRY(ctx, hipMemcpyAsync(d_pts, h_pts, (size_t)nb * n * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+    MLEV_WS(ctx, "mlev_pts", (size_t)nt * n * sizeof(Fr), d_pts);
+    MLEV_WS(ctx, "mlev_out", (size_t)nt * sizeof(Fr), d_out);
+    MLEV_WS(ctx, "mlev_ws", gkr::mle_eval_ws_bytes((uint32_t)n, nt), d_ws);
+    HIP_TRY(ctx, hipMemcpyAsync(d_pts, h_pts, (size_t)nt * n * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
     {
-        Timed t(ctx, "mle_eval", (double)nb * 32.0 * (double)((size_t)1 << n));
-        gkr::launch_mle_eval(d_tables, (uint32_t)n, nb, d_pts, d_ws, d_out, ctx->stream);
+        Timed t(ctx, "mle_eval", (double)nt * 32.0 * (double)((size_t)1 << n));
+        gkr::launch_mle_eval(d_tables, (uint32_t)n, nt, d_pts, d_ws, d_out, ctx->stream);
     }
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(h_out, d_out, (size_t)nb * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(h_out, d_out, (size_t)nt * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
     return GKR_OK;
 }
 
-int verify_chunk(gkr_ctx* ctx, const Fr* d_tables, int n, uint32_t nb, const gkr_fr* claims, const gkr_fr* coeffs, const uint32_t* len,
-                 const gkr_fr* r, int* accept, uint32_t* failed_round, uint32_t* failed_check, gkr_fr* out_claims) {
+int verify_chunk(gkr_ctx* ctx, const Fr* d_tables, int n, int degree, uint32_t nb, const gkr_fr* claims, const gkr_fr* coeffs, const uint32_t* len,
+                 const gkr_fr* r, int* accept, uint32_t* failed_round, uint32_t* failed_check, gkr_fr* out_claims, gkr_fr* out_evals) {
     hipStream_t st = ctx->stream;
-    const size_t n_rows = (size_t)nb * n;
+    const size_t n_rows = (size_t)nb * n, W = row_width(degree), nt = (size_t)nb * degree;
     const bool dev_hash = verify_device_hash_wanted(n_rows);
     // ---- the host's share, in pieces: the relations of kRelPiece transcripts, then (host hashing) kHashPiece round vectors
     std::vector<Pre> pre(nb);
@@ -177,12 +199,13 @@ int verify_chunk(gkr_ctx* ctx, const Fr* d_tables, int n, uint32_t nb, const gkr
     const std::function<bool()> host_work = [&] {
         const size_t a = next.fetch_add(1, std::memory_order_relaxed);
         if (a < hash_pieces) {   // (the hashes first: they are the long pieces)
-            for (size_t s = a * kHashPiece; s < std::min(n_rows, (a + 1) * kHashPiece); ++s) hash_slot(coeffs + 2 * s, len[s], &host_slots[s]);
+            for (size_t s = a * kHashPiece; s < std::min(n_rows, (a + 1) * kHashPiece); ++s)
+                hash_slot(coeffs + W * s, (uint32_t)W, len[s], &host_slots[s]);
             return true;
         }
         if (a < hash_pieces + rel_pieces) {
             for (size_t b = (a - hash_pieces) * kRelPiece; b < std::min<size_t>(nb, (a - hash_pieces + 1) * kRelPiece); ++b)
-                pre[b] = pre_relations(n, claims ? claims + b : nullptr, coeffs + 2 * b * n, len + b * n, r + b * n);
+                pre[b] = pre_relations(n, degree, claims ? claims + b : nullptr, coeffs + W * b * n, len + b * n, r + b * n);
             return true;
         }
         return false;
@@ -196,32 +219,39 @@ int verify_chunk(gkr_ctx* ctx, const Fr* d_tables, int n, uint32_t nb, const gkr
     } side;
     // ---- the device's share: hashes on the side stream, the evaluation on the main stream
     Fr *h_pts, *h_out;
-    HIP_TRY(ctx, ctx->pinned_host("mlev_pts", n_rows * sizeof(Fr), reinterpret_cast<void**>(&h_pts)));
-    HIP_TRY(ctx, ctx->pinned_host("mlev_out", (size_t)nb * sizeof(Fr), reinterpret_cast<void**>(&h_out)));
+    HIP_TRY(ctx, ctx->pinned_host("mlev_pts", nt * n * sizeof(Fr), reinterpret_cast<void**>(&h_pts)));
+    HIP_TRY(ctx, ctx->pinned_host("mlev_out", nt * sizeof(Fr), reinterpret_cast<void**>(&h_out)));
     if (dev_hash) {
+        const int hs = hash_slots(degree);
+        const size_t hw = (size_t)hs * 8, lead = ((size_t)hs - W) * 8;   // words of a kernel row; of its slots the transcript's rows lack
         uint32_t *d_hin, *h_hin;
         gkr::VerifyHashSlot *d_hout, *h_hout;
-        MLEV_WS(ctx, "mlev_hash_in", n_rows * (kHashRowWords + 1) * sizeof(uint32_t), d_hin);
+        MLEV_WS(ctx, "mlev_hash_in", n_rows * (hw + 1) * sizeof(uint32_t), d_hin);
         MLEV_WS(ctx, "mlev_hash_out", n_rows * sizeof(gkr::VerifyHashSlot), d_hout);
-        HIP_TRY(ctx, ctx->pinned_host("mlev_hash_in", n_rows * (kHashRowWords + 1) * sizeof(uint32_t), reinterpret_cast<void**>(&h_hin)));
+        HIP_TRY(ctx, ctx->pinned_host("mlev_hash_in", n_rows * (hw + 1) * sizeof(uint32_t), reinterpret_cast<void**>(&h_hin)));
         HIP_TRY(ctx, ctx->pinned_host("mlev_hash_out", n_rows * sizeof(gkr::VerifyHashSlot), reinterpret_cast<void**>(&h_hout)));
-        for (size_t s = 0; s < n_rows; ++s) {   // two slots -> the kernel's three; the leading one is never looked at for len <= 2
-            memset(h_hin + s * kHashRowWords, 0, 32);
-            memcpy(h_hin + s * kHashRowWords + 8, coeffs + 2 * s, 64);
+        if (lead == 0) {
+            memcpy(h_hin, coeffs, n_rows * hw * sizeof(uint32_t));
+        } else {
+            for (size_t s = 0; s < n_rows; ++s) {   // W slots -> the kernel's; the leading ones are never looked at for len <= W
+                memset(h_hin + s * hw, 0, lead * sizeof(uint32_t));
+                memcpy(h_hin + s * hw + lead, coeffs + W * s, W * sizeof(gkr_fr));
+            }
         }
-        memcpy(h_hin + n_rows * kHashRowWords, len, n_rows * sizeof(uint32_t));
+        memcpy(h_hin + n_rows * hw, len, n_rows * sizeof(uint32_t));
         HIP_TRY(ctx, ctx->aux_stream(2));
         HIP_TRY(ctx, hipEventRecord(ctx->aux_events[0], st));             // fork: after whatever the main stream still holds
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux, ctx->aux_events[0], 0));
         side.forked = ctx->aux;
-        HIP_TRY(ctx, hipMemcpyAsync(d_hin, h_hin, n_rows * (kHashRowWords + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->aux));
-        if (const int rc = verify_hash_rows_device(ctx, d_hin, d_hin + n_rows * kHashRowWords, n_rows, d_hout, ctx->aux)) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(d_hin, h_hin, n_rows * (hw + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->aux));
+        if (const int rc = verify_hash_rows_device(ctx, hs, d_hin, d_hin + n_rows * hw, n_rows, d_hout, ctx->aux)) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(h_hout, d_hout, n_rows * sizeof(gkr::VerifyHashSlot), hipMemcpyDeviceToHost, ctx->aux));
         HIP_TRY(ctx, hipEventRecord(ctx->aux_events[1], ctx->aux));
         slots = reinterpret_cast<const HashSlot*>(h_hout);
     }
-    memcpy(h_pts, r, n_rows * sizeof(Fr));
-    if (const int rc = queue_eval(ctx, d_tables, n, nb, h_pts, h_out)) return rc;
+    for (size_t b = 0; b < nb; ++b)   // a sumcheck's point once per table of it
+        for (int f = 0; f < degree; ++f) memcpy(h_pts + (b * degree + f) * n, r + b * n, (size_t)n * sizeof(Fr));
+    if (const int rc = queue_eval(ctx, d_tables, n, (uint32_t)nt, h_pts, h_out)) return rc;
     if (dev_hash) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->aux_events[1], 0));   // join: the main stream's end is the side stream's too
     // ---- the host works while the device streams (waking the pool is worth some tens of hashes or transcripts)
     {
@@ -233,25 +263,31 @@ int verify_chunk(gkr_ctx* ctx, const Fr* d_tables, int n, uint32_t nb, const gkr
     HIP_TRY(ctx, hipStreamSynchronize(st));
     side.forked = nullptr;
     for (uint32_t b = 0; b < nb; ++b) {
-        const int rc = finish(ctx, n, pre[b], slots + (size_t)b * n, r + (size_t)b * n, h_out[b], &accept[b], failed_round ? failed_round + b : nullptr,
-                              failed_check ? failed_check + b : nullptr);
+        const Fr* values = h_out + (size_t)b * degree;
+        const int rc = finish(ctx, n, degree, pre[b], slots + (size_t)b * n, r + (size_t)b * n, values, &accept[b],
+                              failed_round ? failed_round + b : nullptr, failed_check ? failed_check + b : nullptr);
         if (rc) return rc;
+        // the proven sum and the tables' values of a transcript that passed checks 1 and 2; zero otherwise (its point is no point)
         if (out_claims) {
             memset(&out_claims[b], 0, sizeof(gkr_fr));
             if (!pre[b].check) memcpy(out_claims[b].l, pre[b].proved.l, 32);
+        }
+        if (out_evals) {
+            memset(out_evals + (size_t)b * degree, 0, (size_t)degree * sizeof(gkr_fr));
+            if (!pre[b].check) memcpy(out_evals + (size_t)b * degree, values, (size_t)degree * sizeof(gkr_fr));
         }
     }
     return GKR_OK;
 }
 
-int verify_batch(gkr_ctx* ctx, const Fr* d_tables, int n, int batch, const gkr_fr* claims, const gkr_fr* coeffs, const uint32_t* len,
-                 const gkr_fr* r, int* accept, uint32_t* failed_round, uint32_t* failed_check, gkr_fr* out_claims) {
-    const size_t chunk = chunk_tables(n, batch, true);
+int verify_batch(gkr_ctx* ctx, const Fr* d_tables, int n, int degree, int batch, const gkr_fr* claims, const gkr_fr* coeffs, const uint32_t* len,
+                 const gkr_fr* r, int* accept, uint32_t* failed_round, uint32_t* failed_check, gkr_fr* out_claims, gkr_fr* out_evals) {
+    const size_t chunk = chunk_tables(n, degree, batch, true), W = row_width(degree);
     for (size_t b = 0; b < (size_t)batch; b += chunk) {
         const uint32_t nb = (uint32_t)std::min(chunk, (size_t)batch - b);
-        const int rc = verify_chunk(ctx, d_tables + (b << n), n, nb, claims ? claims + b : nullptr, coeffs + 2 * b * n, len + b * n, r + b * n,
-                                    accept + b, failed_round ? failed_round + b : nullptr, failed_check ? failed_check + b : nullptr,
-                                    out_claims ? out_claims + b : nullptr);
+        const int rc = verify_chunk(ctx, d_tables + ((b * degree) << n), n, degree, nb, claims ? claims + b : nullptr, coeffs + W * b * n, len + b * n,
+                                    r + b * n, accept + b, failed_round ? failed_round + b : nullptr, failed_check ? failed_check + b : nullptr,
+                                    out_claims ? out_claims + b : nullptr, out_evals ? out_evals + b * degree : nullptr);
         if (rc) return rc;
     }
     return GKR_OK;
@@ -266,7 +302,7 @@ int gkr_mle_eval_batch_device(gkr_ctx* ctx, const void* d_tables, int n, int bat
     if (!ctx || !d_tables || !points || !out || batch < 1 || n < 1 || n > 30) return GKR_ERR_INVALID;
     if (!all_canonical(points, (size_t)batch * n)) return ctx->fail(GKR_ERR_NON_CANONICAL, "coordinate of a point >= r");
     GKR_ENTER(ctx);
-    const size_t chunk = chunk_tables(n, batch, false);
+    const size_t chunk = chunk_tables(n, 1, batch, false);
     for (size_t b = 0; b < (size_t)batch; b += chunk) {
         const uint32_t nb = (uint32_t)std::min(chunk, (size_t)batch - b);
         Fr *h_pts, *h_out;
@@ -285,7 +321,7 @@ int gkr_sumcheck_mle_verify_batch_device(gkr_ctx* ctx, const void* d_tables, int
                                          gkr_fr* out_claims) {
     if (!ctx || !d_tables || !coeffs || !len || !r || !accept || batch < 1 || n < 2 || n > 30) return GKR_ERR_INVALID;
     GKR_ENTER(ctx);
-    return verify_batch(ctx, static_cast<const Fr*>(d_tables), n, batch, claims, coeffs, len, r, accept, failed_round, failed_check, out_claims);
+    return verify_batch(ctx, static_cast<const Fr*>(d_tables), n, 1, batch, claims, coeffs, len, r, accept, failed_round, failed_check, out_claims, nullptr);
 }
 
 int gkr_sumcheck_mle_verify(gkr_ctx* ctx, const gkr_fr* table, int n, const gkr_fr* claim, const gkr_fr* coeffs, const uint32_t* len,
@@ -299,7 +335,35 @@ int gkr_sumcheck_mle_verify(gkr_ctx* ctx, const gkr_fr* table, int n, const gkr_
         if (e != hipSuccess) return alloc_status(ctx, e, "gkr_sumcheck_mle_verify: the table");
     }
     HIP_TRY(ctx, hipMemcpyAsync(d.p, table, count * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
-    return verify_batch(ctx, d.p, n, 1, claim, coeffs, len, r, accept, failed_round, failed_check, nullptr);
+    return verify_batch(ctx, d.p, n, 1, 1, claim, coeffs, len, r, accept, failed_round, failed_check, nullptr, nullptr);
+}
+
+// ---- the product sumcheck's verifier: the same driver at degree 1 .. GKR_PRODUCT_MAX_DEGREE, argument checks as the prover's
+
+int gkr_sumcheck_product_verify_batch_device(gkr_ctx* ctx, const void* d_tables, int n, int degree, int batch, const gkr_fr* claims,
+                                             const gkr_fr* coeffs, const uint32_t* len, const gkr_fr* r, int* accept, uint32_t* failed_round,
+                                             uint32_t* failed_check, gkr_fr* out_claims, gkr_fr* out_evals) {
+    if (!ctx || !d_tables || !coeffs || !len || !r || !accept || batch < 1 || batch > 65535) return GKR_ERR_INVALID;
+    if (!product_shape_ok(n, degree, batch)) return GKR_ERR_INVALID;
+    GKR_ENTER(ctx);
+    return verify_batch(ctx, static_cast<const Fr*>(d_tables), n, degree, batch, claims, coeffs, len, r, accept, failed_round, failed_check,
+                        out_claims, out_evals);
+}
+
+int gkr_sumcheck_product_verify(gkr_ctx* ctx, const gkr_fr* tables, int n, int degree, const gkr_fr* claim, const gkr_fr* coeffs,
+                                const uint32_t* len, const gkr_fr* r, int* accept, uint32_t* failed_round, uint32_t* failed_check) {
+    if (!ctx || !tables || !coeffs || !len || !r || !accept) return GKR_ERR_INVALID;
+    if (!product_shape_ok(n, degree, 1)) return GKR_ERR_INVALID;
+    const size_t count = (size_t)degree << n;
+    if (!all_canonical(tables, count)) return ctx->fail(GKR_ERR_NON_CANONICAL, "table entry >= r");
+    GKR_ENTER(ctx);
+    DevBuf<Fr> d;
+    {
+        const hipError_t e = d.alloc(count);
+        if (e != hipSuccess) return alloc_status(ctx, e, "gkr_sumcheck_product_verify: the tables");
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(d.p, tables, count * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+    return verify_batch(ctx, d.p, n, degree, 1, claim, coeffs, len, r, accept, failed_round, failed_check, nullptr, nullptr);
 }
 
 }  // extern "C"

@@ -50,9 +50,10 @@ static int run_product_batch(gkr_ctx* ctx, const Fr* d_tables, int n, int degree
     return GKR_OK;
 }
 
-// The shape checks both entry points share, in gkr_sumcheck_mle_batch_device's order (ctx and pointers first, then n).  Plain
-// returns, as gkr_mle_eval_batch_device's: they are decided before the context is looked at.
-static bool product_shape_ok(int n, int degree, int batch) {
+// The shape checks the prover's and the verifier's (capi_mle_verify.hip) entry points share, in gkr_sumcheck_mle_batch_device's
+// order (ctx and pointers first, then n).  Plain returns, as gkr_mle_eval_batch_device's: they are decided before the context
+// is looked at.
+bool product_shape_ok(int n, int degree, int batch) {
     if (n < 2 || n > GKR_MAX_MLE_N) return false;                                       // n must be in [2, 30]
     if (degree < 1 || degree > GKR_PRODUCT_MAX_DEGREE) return false;                    // degree must be in [1, 3]
     return (((unsigned long long)batch * (unsigned long long)degree) << n) <= (1ull << 30);   // batch * degree * 2^n values

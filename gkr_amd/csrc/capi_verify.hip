@@ -122,12 +122,14 @@ bool device_hash_wanted(size_t rows) {
 }
 
 // n rows and their lengths, in device memory -> their slots in device memory, on stream s: THE launcher of both entry points
-int hash_rows_device(gkr_ctx* ctx, const uint32_t* d_rows, const uint32_t* d_len, size_t n, gkr::VerifyHashSlot* d_slots, hipStream_t s) {
+// (slots: 3, this file's rows, or 4, the degree-3 product sumcheck's)
+int hash_rows_device(gkr_ctx* ctx, int slots, const uint32_t* d_rows, const uint32_t* d_len, size_t n, gkr::VerifyHashSlot* d_slots, hipStream_t s) {
+    const size_t row_words = (size_t)slots * 8;
     for (size_t a = 0; a < n; a += kHashLaunchRows) {
         const size_t m = std::min(kHashLaunchRows, n - a);
         {
-            Timed t(ctx, "verify_hash", (double)m * kHashRowBytes, s);
-            gkr::launch_verify_hash(d_rows + a * kHashRowWords, d_len + a, (uint32_t)m, ctx->d_cts, d_slots + a, s);
+            Timed t(ctx, "verify_hash", (double)m * (kHashRowBytes + 32.0 * (slots - 3)), s);
+            gkr::launch_verify_hash(slots, d_rows + a * row_words, d_len + a, (uint32_t)m, ctx->d_cts, d_slots + a, s);
         }
         HIP_TRY(ctx, hipGetLastError());
     }
@@ -269,7 +271,7 @@ int verify_chunk(gkr_ctx* ctx, const gkr_verify_circuit* vc, const Shape& sh, co
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux, ctx->aux_events[0], 0));
         side.forked = ctx->aux;
         HIP_TRY(ctx, hipMemcpyAsync(d_hin, h_hin, n_rows * (kHashRowWords + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->aux));
-        if (const int rc = hash_rows_device(ctx, d_hin, d_hin + n_rows * kHashRowWords, n_rows, d_hout, ctx->aux)) return rc;
+        if (const int rc = hash_rows_device(ctx, 3, d_hin, d_hin + n_rows * kHashRowWords, n_rows, d_hout, ctx->aux)) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(h_hout, d_hout, n_rows * sizeof(gkr::VerifyHashSlot), hipMemcpyDeviceToHost, ctx->aux));
         HIP_TRY(ctx, hipEventRecord(ctx->aux_events[1], ctx->aux));
         slots = reinterpret_cast<const HashSlot*>(h_hout);
@@ -352,11 +354,12 @@ int verify_chunk(gkr_ctx* ctx, const gkr_verify_circuit* vc, const Shape& sh, co
 
 }  // namespace
 
-// the plain sumcheck's verifier (capi_mle_verify.hip) hashes its round vectors through the same threshold and the same launcher
+// the plain and the product sumcheck's verifier (capi_mle_verify.hip) hash their round vectors through the same threshold and the same launcher
 namespace gkr_host {
 bool verify_device_hash_wanted(size_t rows) { return device_hash_wanted(rows); }
-int verify_hash_rows_device(gkr_ctx* ctx, const uint32_t* d_rows, const uint32_t* d_len, size_t n, gkr::VerifyHashSlot* d_slots, hipStream_t s) {
-    return hash_rows_device(ctx, d_rows, d_len, n, d_slots, s);
+int verify_hash_rows_device(gkr_ctx* ctx, int slots, const uint32_t* d_rows, const uint32_t* d_len, size_t n, gkr::VerifyHashSlot* d_slots,
+                            hipStream_t s) {
+    return hash_rows_device(ctx, slots, d_rows, d_len, n, d_slots, s);
 }
 }  // namespace gkr_host
 
@@ -447,7 +450,7 @@ int gkr_mimc7_multi_hash_device(gkr_ctx* ctx, const gkr_fr* rows, const uint32_t
         memcpy(h_in, rows + a * 3, m * kHashRowWords * sizeof(uint32_t));
         memcpy(h_in + m * kHashRowWords, len + a, m * sizeof(uint32_t));
         HIP_TRY(ctx, hipMemcpyAsync(d_in, h_in, m * (kHashRowWords + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-        if (const int rc = hash_rows_device(ctx, d_in, d_in + m * kHashRowWords, m, d_out, ctx->stream)) return rc;
+        if (const int rc = hash_rows_device(ctx, 3, d_in, d_in + m * kHashRowWords, m, d_out, ctx->stream)) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(h_out, d_out, m * sizeof(gkr::VerifyHashSlot), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         for (size_t i = 0; i < m; ++i) {

@@ -410,10 +410,11 @@ struct VerifyHashSlot {
     uint32_t pad;
 };
 static_assert(sizeof(VerifyHashSlot) == 40, "hash slot");
-// out[i] = {multi_hash(row i's trailing len[i] slots, key 0), 1} for n >= 1 rows of 3 right-aligned slots (24 words per row, the
-// layout of gkr_proof_buf.sumcheck_coeffs); {0, 0} when len[i] is outside 1 .. 3 or a used slot holds an element >= r (an
-// unused leading slot is never looked at).  cts: the 91 round constants in Montgomery form.  Eight lanes per row, one launch.
-void launch_verify_hash(const uint32_t* rows, const uint32_t* len, uint32_t n, const Fr* cts, VerifyHashSlot* out, hipStream_t s);
+// out[i] = {multi_hash(row i's trailing len[i] slots, key 0), 1} for n >= 1 rows of `slots` (3 or 4) right-aligned slots (8 * slots
+// words per row; 3: the layout of gkr_proof_buf.sumcheck_coeffs, 4: the degree-3 product sumcheck's rows); {0, 0} when len[i] is
+// outside 1 .. slots or a used slot holds an element >= r (an unused leading slot is never looked at).  cts: the 91 round
+// constants in Montgomery form.  Eight lanes per row, one launch.
+void launch_verify_hash(int slots, const uint32_t* rows, const uint32_t* len, uint32_t n, const Fr* cts, VerifyHashSlot* out, hipStream_t s);
 
 // ---- multilinear evaluation at a point (kernels_mle_eval.hip) ---------------------------------------------------------------------
 // The streaming matrix-core form binds five variables per pass over 2^(n-5) outputs in wave tiles of 64: it applies from

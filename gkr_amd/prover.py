@@ -367,9 +367,8 @@ class Context:
         """Sumcheck of sum_x prod_f tables[f](x) over {0,1}^v: tables is a list of 1 .. 3 tables of 2^v values.
         -> (proof, r, evals): proof[j] the round vector (its used slots, highest degree first, 1 .. len(tables) + 1 of them), r
         the challenges, evals[f] = tables[f]~(r), the factor's multilinear extension at the challenges.
-        A verifier (verifier.verify_sumcheck_product) ends on proof[-1](r[-1]) == prod evals; that evals are the tables' values
-        is the caller's to establish: verifier.mle_eval(tables[f], r) on the host, or Context.mle_eval_batch_device on resident
-        tables -- the `degree` factors of one sumcheck are a batch of `degree` tables at the same point."""
+        Context.verify_sumcheck_product(tables, proof, r) checks the transcript AND that it belongs to these tables (it
+        evaluates them at r on the device); verifier.verify_sumcheck_product is the transcript's part of it on plain integers."""
         degree = len(tables)
         limbs = np.concatenate([as_limbs(t) for t in tables], axis=0) if degree else np.zeros((0, 4), dtype=np.uint64)
         if limbs.shape[0] != degree << v:
@@ -433,6 +432,52 @@ class Context:
         accept, rnd, check = ctypes.c_int(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
         self._check(N.lib().gkr_sumcheck_mle_verify(self._h, _ptr(limbs), ctypes.c_int(n), _ptr(cl) if cl is not None else None, _ptr(C), _ptr(L),
                                                     _ptr(R), ctypes.byref(accept), ctypes.byref(rnd), ctypes.byref(check)))
+        return bool(accept.value), int(rnd.value), int(check.value)
+
+    # -- the product sumcheck's verifier: the same checks on rows of degree + 1 slots, g_n(r_n) = prod_f T_f~(r)
+    def verify_sumcheck_product_batch_device(self, d_tables, n, degree, batch, C, L, R, claims=None):
+        """gkr_sumcheck_product_verify_batch_device on the resident tables and the arrays sumcheck_product_batch_device returned (C
+        (batch, n, degree + 1, 4), L (batch, n), R (batch, n, 4)); claims: (batch, 4) uint64 limbs or None (round 0's sum check
+        is skipped, the proven sums are returned).  -> (accept (batch,) bool, failed_round (batch,) uint32, failed_check (batch,)
+        uint32, claims (batch, 4) uint64, evals (batch, degree, 4) uint64: the tables' values at the challenges as computed here)."""
+        C = np.ascontiguousarray(C, dtype=np.uint64)
+        L = np.ascontiguousarray(L, dtype=np.uint32)
+        R = np.ascontiguousarray(R, dtype=np.uint64)
+        if degree < 1 or C.shape != (batch, n, degree + 1, 4) or L.shape != (batch, n) or R.shape != (batch, n, 4):
+            raise GkrError(N.GKR_ERR_INVALID, "transcript arrays do not match (batch, n, degree)")
+        if claims is not None:
+            claims = np.ascontiguousarray(claims, dtype=np.uint64)
+            if claims.shape != (batch, 4):
+                raise GkrError(N.GKR_ERR_INVALID, "claims of shape (batch, 4) expected")
+        accept = np.zeros(batch, dtype=np.int32)
+        rnd, check = np.zeros(batch, dtype=np.uint32), np.zeros(batch, dtype=np.uint32)
+        out = np.zeros((batch, 4), dtype=np.uint64)
+        evals = np.zeros((batch, degree, 4), dtype=np.uint64)
+        self._check(N.lib().gkr_sumcheck_product_verify_batch_device(
+            self._h, d_tables, n, degree, batch, _ptr(claims) if claims is not None else None, _ptr(C), _ptr(L), _ptr(R),
+            _ptr(accept), _ptr(rnd), _ptr(check), _ptr(out), _ptr(evals)))
+        return accept.astype(bool), rnd, check, out, evals
+
+    def verify_sumcheck_product(self, tables, proof, r, claim=None):
+        """gkr_sumcheck_product_verify on what prove_sumcheck_product returned: tables the 1 .. 3 factors, proof[j] the round
+        vector (1 .. len(tables) + 1 coefficients, highest degree first), r the challenges; claim: the sum the transcript is to
+        prove, or None.  -> (accept, failed_round, failed_check)."""
+        degree, n = len(tables), len(proof)
+        limbs = np.concatenate([as_limbs(t) for t in tables], axis=0) if degree else np.zeros((0, 4), dtype=np.uint64)
+        if n < 1 or degree < 1 or limbs.shape[0] != degree << n or len(r) != n:
+            raise GkrError(N.GKR_ERR_INVALID, "tables of 2^n entries each, n round vectors and n challenges expected")
+        C = np.zeros((n, degree + 1, 4), dtype=np.uint64)
+        L = np.zeros(n, dtype=np.uint32)
+        for j, g in enumerate(proof):
+            if not 1 <= len(g) <= degree + 1:
+                raise GkrError(N.GKR_ERR_INVALID, "a round vector has 1 .. degree + 1 coefficients")
+            L[j] = len(g)
+            C[j, degree + 1 - len(g):] = to_limbs(g)
+        R = to_limbs(r)
+        cl = to_limbs([claim]) if claim is not None else None
+        accept, rnd, check = ctypes.c_int(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+        self._check(N.lib().gkr_sumcheck_product_verify(self._h, _ptr(limbs), n, degree, _ptr(cl) if cl is not None else None, _ptr(C), _ptr(L),
+                                                        _ptr(R), ctypes.byref(accept), ctypes.byref(rnd), ctypes.byref(check)))
         return bool(accept.value), int(rnd.value), int(check.value)
 
     # -- layer sumcheck (prove_sumcheck_opt, sumcheck.rs:36-156)

@@ -98,7 +98,8 @@ def verify_sumcheck_product(rounds: List[List[int]], challenges: List[int], eval
     """The verifier of a product sumcheck's transcript (Context.prove_sumcheck_product) on plain integers: every round vector
     has 1 .. degree + 1 coefficients, python/sumcheck.py:55-70 holds on the claim (the first round vector's own sum when none
     is given), and g_n(r_n) == prod evals.  That evals[f] is factor f's multilinear extension at the challenges is NOT checked
-    here: mle_eval(table_f, challenges) on the host, or Context.mle_eval_batch_device on resident tables.
+    here: Context.verify_sumcheck_product (host tables) and Context.verify_sumcheck_product_batch_device (resident tables) check
+    the transcript against the tables themselves, on the device, and return the values they computed.
     hashes: multi_hash(rounds[j], 0) for every j, computed by the caller (many transcripts: all their round vectors in one
     Context.multi_hash_batch call); None: hashed here, one vector at a time."""
     if len(rounds) < 1 or len(rounds) != len(challenges) or len(evals) != degree:

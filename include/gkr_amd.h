@@ -295,8 +295,8 @@ int  gkr_sumcheck_mle_batch_device(gkr_ctx *ctx, const void *d_tables, int n, in
  *               merge, sumcheck.rs:206-207)
  *   out_r       batch x n challenges, r_j = multi_hash(round vector j, key 0)
  *   out_evals   batch x degree values T_f~(r_1 .. r_n) -- the one entry each factor has left after the last fold, which the
- *               prover has for free -- or NULL.  A verifier's last check is g_n(r_n) = prod_f out_evals[f]; binding the values
- *               to the tables is one call of the evaluation entry point above on the same resident tables.
+ *               prover has for free -- or NULL.  A verifier's last check is g_n(r_n) = prod_f T_f~(r): the verifier below
+ *               (gkr_sumcheck_product_verify_batch_device) evaluates the resident tables itself and returns the values.
  * A factor that is the zero table makes g the empty term list, on which the reference panics (partial_eval indexes f[0],
  * poly.rs:236); as the library's OWN choice such a sumcheck returns every round vector as [0] with length 1.
  * The challenges are hashed on the device in both transcript modes (one launch per round, no host round trip): the result
@@ -312,6 +312,39 @@ int  gkr_sumcheck_product_batch_device(gkr_ctx *ctx, const void *d_tables, int n
  * GKR_ERR_NON_CANONICAL for an entry >= r. */
 int  gkr_sumcheck_product(gkr_ctx *ctx, const gkr_fr *tables, int n, int degree,
                           gkr_fr *out_coeffs, uint32_t *out_len, gkr_fr *out_r, gkr_fr *out_evals);
+
+/* Verifier of gkr_sumcheck_product_batch_device's transcripts: the plain sumcheck's verifier (below; the same driver, the same
+ * options) for round polynomials of degree up to 3, one read of every factor.
+ * d_tables / coeffs / len / r: exactly the arrays and layout of the prover (factor f of sumcheck b at (b * degree + f) * 2^n
+ * elements; batch x n rows of degree + 1 right-aligned slots, highest degree first; len in 1 .. degree + 1; batch x n
+ * challenges).  claims: batch elements or NULL.
+ * accept[batch] required; failed_round / failed_check / out_claims (batch) / out_evals (batch x degree) may be NULL.
+ * Per transcript, in this order, the first failure reported (failed_check: the GKR_VERIFY_* values below):
+ *   1. GKR_VERIFY_SHAPE           some len[j] outside 1 .. degree + 1; failed_round = the first such j
+ *   2. GKR_VERIFY_NON_CANONICAL   a used slot, an r_j or the claim >= r (unused slots are never read); failed_round = the
+ *                                 first such row, 0 for the claim
+ *   3. for j = 0 .. n-1:  GKR_VERIFY_ROUND_SUM  g_j(0) + g_j(1) (= 2 c_0 + c_1 + .. + c_D over the used slots) != the running
+ *      claim;  GKR_VERIFY_CHALLENGE  r_j != multi_hash(used slots of row j, key 0);  the running claim becomes g_j(r_j)
+ *   4. GKR_VERIFY_EVALUATION      g_n(r_n) != prod_f T_f~(r_1 .. r_n); failed_round = n
+ * claims == NULL: round 0's sum check is skipped.  out_claims[b] = g_1(0) + g_1(1), the sum the transcript proves, and
+ * out_evals[b * degree + f] = T_f~(r) as the device computed it, for every transcript that passes checks 1 and 2; zero for the
+ * others (their point is not a point).  A caller that also holds the prover's out_evals compares them itself.  Table entries
+ * are read as integers modulo r.  The library's zero-factor transcripts (every vector [0]) need no special case.
+ * The return value is the status of the CALL, not the verdict.  GKR_ERR_INVALID before a device or the context is touched
+ * (plain returns): NULL ctx or required pointer, and every shape the prover refuses (batch outside 1 .. 65535, n outside
+ * 2 .. GKR_MAX_MLE_N, degree outside 1 .. GKR_PRODUCT_MAX_DEGREE, batch * degree * 2^n above 2^30 values).  Chunks are counted
+ * in sumchecks (the factors of one sumcheck are never split); verdicts depend neither on verify_workspace_mb nor on
+ * verify_device_hash_min. */
+int gkr_sumcheck_product_verify_batch_device(gkr_ctx *ctx, const void *d_tables, int n, int degree, int batch,
+                                             const gkr_fr *claims, const gkr_fr *coeffs, const uint32_t *len, const gkr_fr *r,
+                                             int *accept, uint32_t *failed_round, uint32_t *failed_check,
+                                             gkr_fr *out_claims, gkr_fr *out_evals);
+
+/* `degree` tables in host memory, one after the other: upload + the call above with batch 1.  GKR_ERR_NON_CANONICAL for a
+ * table entry >= r, as gkr_sumcheck_product. */
+int gkr_sumcheck_product_verify(gkr_ctx *ctx, const gkr_fr *tables, int n, int degree, const gkr_fr *claim,
+                                const gkr_fr *coeffs, const uint32_t *len, const gkr_fr *r,
+                                int *accept, uint32_t *failed_round, uint32_t *failed_check);
 
 /* ---- the plain sumcheck's verifier: verify_sumcheck, python/sumcheck.py:55-70, and the relation behind it -------------
  * A transcript of prove_sumcheck proves "sum of the table = claim" only together with g_n(r_n) = T~(r_1 .. r_n), the table's
@@ -645,7 +678,7 @@ enum {
     GKR_VERIFY_R_STAR = 7,         /* r* != multi_hash(last round vector) */
     GKR_VERIFY_NEXT_Z = 8,         /* z[i+1] != b* + r* (c* - b*) */
     GKR_VERIFY_INPUT = 9,          /* q(r*) of the last layer != input_func(z[L]) */
-    GKR_VERIFY_EVALUATION = 10     /* plain sumcheck (gkr_sumcheck_mle_verify*): g_n(r_n) != T~(r_1 .. r_n) */
+    GKR_VERIFY_EVALUATION = 10     /* plain and product sumcheck (gkr_sumcheck_*_verify*): g_n(r_n) != prod_f T_f~(r) */
 };
 int  gkr_verify(const gkr_circuit_desc *circuit, const gkr_proof_buf *proof, int threads, int *accept, uint32_t *failed_layer,
                 uint32_t *failed_check);

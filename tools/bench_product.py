@@ -12,6 +12,12 @@ tables (the evals are the factors' values at the challenges), every later one fo
 calls under the context profile give the per-call kernel times by name (product_first, product_fold_sum, product_round) and the
 share of the round kernel -- the device hash, once per round on the critical path.
 
+The verify leg, same process and tables: gkr_sumcheck_product_verify_batch_device on the transcripts just proved, alternating
+with a bare gkr_mle_eval_batch_device call on the same batch * degree tables at the same points -- the evaluation alone, the
+yardstick of what the verifier's table read should cost.  Per call: host-clock medians and spread, the `mle_eval` (and
+`verify_hash`) entries of the context profile, and the fraction of the box's read ceiling that the tables' batch * degree * 32 *
+2^n bytes reach in the call and in its `mle_eval` entry.  Checked: every transcript accepted, the values equal to the prover's.
+
 Algorithmic counts per sumcheck (h = 2^(n-1)): modular products  h * c  in round 1 and  q * (2 d + c)  in a round that folds
 (q = a quarter of its source tables; c = 3 at degree 2, 8 at degree 3: one per value at degree 2, a Montgomery and a lazy product
 per value at degree 3), about  h * (2 d + 2 c)  in all; bytes  32 * d * 2^n  in round 1 and  6 q * 32  per factor and folding
@@ -57,6 +63,39 @@ def check(ctx, d, n, degree, batch, out):
         if not verify_sumcheck_product(proof, from_limbs(R[b]), from_limbs(E[b]), degree):
             return False
     return bool(np.array_equal(ctx.mle_eval_batch_device(d, n, batch * degree, np.repeat(R, degree, axis=0)), E.reshape(-1, 4)))
+
+
+def verify_leg(ctx, d, n, degree, batch, proved, args, ceil):
+    C, L, R, E = proved
+    tables = batch * degree
+    points = np.ascontiguousarray(np.repeat(R, degree, axis=0))
+    accepted = lambda res: bool(res[0].all()) and bool(np.array_equal(res[4], E))
+    ok = accepted(ctx.verify_sumcheck_product_batch_device(d, n, degree, batch, C, L, R))      # warm-up
+    ok = ok and bool(np.array_equal(ctx.mle_eval_batch_device(d, n, tables, points), E.reshape(-1, 4)))
+    t_verify, t_bare = [], []
+    for _ in range(args.reps):
+        ms, res = timed(lambda: ctx.verify_sumcheck_product_batch_device(d, n, degree, batch, C, L, R))
+        t_verify.append(ms)
+        ok = ok and accepted(res)
+        ms, _ = timed(lambda: ctx.mle_eval_batch_device(d, n, tables, points))
+        t_bare.append(ms)
+    ctx.profile(1)
+    entries = {}
+    for name, call in (("verify", lambda: ctx.verify_sumcheck_product_batch_device(d, n, degree, batch, C, L, R)),
+                       ("bare", lambda: ctx.mle_eval_batch_device(d, n, tables, points))):
+        ctx.profile_reset()
+        for _ in range(args.profile_reps):
+            call()
+        entries[name] = {k: ctx.profile_get(k)["total_ms"] / args.profile_reps for k in ("mle_eval", "verify_hash")}
+    ctx.profile(0)
+    v, b = spread(t_verify), spread(t_bare)
+    floor_ms = tables * 32.0 * (1 << n) / (ceil["read_GBps"] * 1e6)
+    return {"ok": ok, "verify": v, "bare_mle_eval": b, "table_bytes": tables * 32 * (1 << n), "read_floor_ms": floor_ms,
+            "verify_profile_ms_per_call": entries["verify"], "bare_profile_ms_per_call": entries["bare"],
+            "verify_call_fraction_of_read_ceiling": floor_ms / v["median_ms"], "bare_call_fraction_of_read_ceiling": floor_ms / b["median_ms"],
+            "verify_mle_eval_fraction_of_read_ceiling": floor_ms / entries["verify"]["mle_eval"],
+            "bare_mle_eval_fraction_of_read_ceiling": floor_ms / entries["bare"]["mle_eval"],
+            "verify_minus_bare_ms": v["median_ms"] - b["median_ms"], "device_hashes": entries["verify"]["verify_hash"] > 0}
 
 
 def counts(n, degree, batch):
@@ -109,6 +148,8 @@ def main():
                         ctx.sumcheck_product_batch_device(d, n, degree, batch, out=out)
                     kernels = {k: ctx.profile_get(k)["total_ms"] / args.profile_reps for k in ("product_first", "product_fold_sum", "product_round")}
                     ctx.profile(0)
+                    verify = verify_leg(ctx, d, n, degree, batch, first, args, ceil)
+                    ok = ok and verify.pop("ok")
                 finally:
                     ctx.free(d)
                 failed += int(not ok)
@@ -123,6 +164,7 @@ def main():
                        "passes_fraction_of_modmul_ceiling": alu_ms / pass_ms, "passes_fraction_of_read_ceiling": mem_ms / pass_ms,
                        "call_fraction_of_modmul_ceiling": alu_ms / p["median_ms"],
                        "round_kernel_share_of_kernel_time": kernels["product_round"] / (pass_ms + kernels["product_round"])}
+                row["verify"] = verify
                 result["shapes"].append(row)
     result["failed"] = failed
     line = json.dumps(result, sort_keys=True)
