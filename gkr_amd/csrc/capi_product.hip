@@ -7,6 +7,16 @@ static_assert(gkr::kProductMaxDegree == GKR_PRODUCT_MAX_DEGREE, "the kernels' te
 
 namespace gkr_host {
 
+// Blocks per sumcheck of round `round` (0-based): mle_blocks_per_table of the round's items (round 1: half a table; later: a quarter
+// of the source table), never more than round 1's count, which sizes the partials.  Host logic only; gkr_selftest_product_geometry
+// reports it.
+static uint32_t product_round_blocks(int n, int batch, int round) {
+    const size_t len = (size_t)1 << n;
+    const uint32_t max_nblk = gkr::mle_blocks_per_table((uint32_t)(len / 2), (uint32_t)batch);   // (non-increasing in the items)
+    const uint32_t items = (uint32_t)(len >> (round + 1));
+    return std::min(gkr::mle_blocks_per_table(items, (uint32_t)batch), max_nblk);
+}
+
 // Workspace slots are this path's own ("product.*"): a call may follow a plain sumcheck on the same context.
 static int run_product_batch(gkr_ctx* ctx, const Fr* d_tables, int n, int degree, int batch, gkr_fr* out_coeffs, uint32_t* out_len,
                              gkr_fr* out_r, gkr_fr* out_evals) {
@@ -16,7 +26,7 @@ static int run_product_batch(gkr_ctx* ctx, const Fr* d_tables, int n, int degree
     uint32_t *d_len = nullptr, *d_meta = nullptr;
     gkr::FixedMul* d_rtab = nullptr;
     gkr::ProductPartial* partials = nullptr;
-    const uint32_t max_nblk = gkr::mle_blocks_per_table((uint32_t)(len / 2), (uint32_t)batch);   // (non-increasing in the items)
+    const uint32_t max_nblk = product_round_blocks(n, batch, 0);
     WS(ctx, "product.work", Fr, tables * (len / 2), work);
     WS(ctx, "product.partials", gkr::ProductPartial, (size_t)batch * max_nblk, partials);
     WS(ctx, "product.coeffs", Fr, rounds * slots, d_coeffs);
@@ -27,7 +37,7 @@ static int run_product_batch(gkr_ctx* ctx, const Fr* d_tables, int n, int degree
     WS(ctx, "product.evals", Fr, tables, d_evals);
     for (int round = 0; round < n; ++round) {
         const uint32_t items = (uint32_t)(len >> (round + 1));   // round 1: half a table; later: a quarter of the source table
-        const uint32_t nblk = std::min(gkr::mle_blocks_per_table(items, (uint32_t)batch), max_nblk);
+        const uint32_t nblk = product_round_blocks(n, batch, round);
         if (round == 0) {   // round 1: values only
             Timed t(ctx, "product_first", (double)tables * len * 32.0);
             gkr::launch_product_first(degree, d_tables, len, items, (uint32_t)batch, nblk, partials, s);
@@ -84,6 +94,18 @@ int gkr_sumcheck_product(gkr_ctx* ctx, const gkr_fr* tables, int n, int degree, 
     HIP_TRY(ctx, d.alloc(count));
     HIP_TRY(ctx, hipMemcpyAsync(d.p, tables, count * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
     return run_product_batch(ctx, d.p, n, degree, 1, out_coeffs, out_len, out_r, out_evals);
+}
+
+// the launch geometry of run_product_batch (host logic only, the process-default options): per round the blocks per sumcheck and
+// the chunk the pass kernels derive from them.  batch * 1 table of 2^n values must be a shape the prover admits.
+int gkr_selftest_product_geometry(int n, int batch, uint32_t* nblk, uint32_t* chunk) {
+    if (!nblk || !chunk || batch < 1 || batch > 65535 || !product_shape_ok(n, 1, batch)) return GKR_ERR_INVALID;
+    for (int round = 0; round < n; ++round) {
+        const uint32_t items = (uint32_t)(((size_t)1 << n) >> (round + 1)), b = product_round_blocks(n, batch, round);
+        nblk[round] = b;
+        chunk[round] = ((items + b - 1) / b + 255u) & ~255u;
+    }
+    return GKR_OK;
 }
 
 }  // extern "C"

@@ -208,6 +208,11 @@ int  gkr_selftest_dot(const gkr_fr *a, const gkr_fr *b, size_t n, gkr_fr *out);
 /* the pass schedule of a 2^n-point plain sumcheck (host logic): rounds covered by each pass; mfma = 1 default
  * (up to 5 rounds per pass), 0 the v_mad_u64_u32 fold's (up to 3).  *passes = number of passes. */
 int  gkr_selftest_pass_schedule(int n, int mfma, uint32_t *rounds, size_t capacity, size_t *passes);
+/* the launch geometry of gkr_sumcheck_product_batch_device (host logic, the process-default options; the degree does not enter):
+ * nblk[j] = blocks per sumcheck of round j's pass (j = 0 .. n-1; round 0 the value pass, later rounds the fold-and-value pass),
+ * chunk[j] = the entries a block walks, as the kernels derive it: ((items + nblk - 1) / nblk + 255) & ~255 with items = 2^(n-1-j).
+ * GKR_ERR_INVALID: NULL pointer, batch outside 1 .. 65535, n outside 2 .. GKR_MAX_MLE_N, batch * 2^n above 2^30. */
+int  gkr_selftest_product_geometry(int n, int batch, uint32_t *nblk, uint32_t *chunk);
 /* q(t) = W(b + t (c - b)) (reduce_multiple_polynomial, poly.rs:469-500) as gkr_prove computes it on the host: W = 2^k
  * evaluations; out = k + 1 slots right-aligned, highest degree first; *out_len = 1 + largest monomial degree of W */
 int  gkr_selftest_line_restriction(int k, const gkr_fr *W, const gkr_fr *b, const gkr_fr *c, gkr_fr *out, uint32_t *out_len);

@@ -372,6 +372,89 @@ static int sumcheck_mle_on(u64 (*t)[4], int n, ogkr_fr *out_coeffs, uint32_t *ou
     return 0;
 }
 
+/* prove_sumcheck on g = the product of `degree` multilinear tables (tests/product_model.py restates the rules): round j's
+ * polynomial sum_{i<h} prod_f (lo_f + t (hi_f - lo_f)) by EXPANSION -- per index the factors are multiplied out into
+ * degree + 1 coefficients, which are summed coefficient by coefficient.  No evaluation points, no interpolation, no
+ * division; every sum and product is reduced at once.  The working tables are held in Montgomery form, so a product is
+ * one mont_mul; the modular sums are exact, so the result does not depend on the thread count. */
+int ogkr_sumcheck_product(const ogkr_fr *tables, int n, int degree, ogkr_fr *out_coeffs, uint32_t *out_len,
+                          ogkr_fr *out_r, ogkr_fr *out_evals, int threads) {
+    if (n < 2 || n > 40 || degree < 1 || degree > 3) return -1;
+    if (!cts_ready) init_constants();
+    const int nt = set_threads(threads), d = degree;
+    const size_t len = (size_t)1 << n;
+    u64(*t)[4] = malloc((size_t)d * len * 32);
+    if (!t) return -2;
+    /* the structural facts of the input: factors that depend on x_n, and whether a factor is the zero table */
+    int ndep = 0, zero_factor = 0;
+    for (int f = 0; f < d; ++f) {
+        const ogkr_fr *tf = tables + (size_t)f * len;
+        int dep = 0, any = 0;
+#pragma omp parallel for schedule(static) num_threads(nt) reduction(| : dep, any)
+        for (size_t m = 0; m < len / 2; ++m) {
+            dep |= memcmp(tf[2 * m].l, tf[2 * m + 1].l, 32) != 0;
+            any |= (tf[2 * m].l[0] | tf[2 * m].l[1] | tf[2 * m].l[2] | tf[2 * m].l[3] | tf[2 * m + 1].l[0] | tf[2 * m + 1].l[1] |
+                    tf[2 * m + 1].l[2] | tf[2 * m + 1].l[3]) != 0;
+        }
+        ndep += dep;
+        zero_factor |= !any;
+    }
+#pragma omp parallel for schedule(static) num_threads(nt)
+    for (size_t i = 0; i < (size_t)d * len; ++i) to_mont(tables[i].l, t[i]);
+    const ogkr_fr zero = {{0, 0, 0, 0}};
+    for (int j = 0; j < n; ++j) {
+        const size_t h = len >> (j + 1);
+        u64 c[4][4];   /* c[k]: coefficient of t^k, Montgomery form */
+        memset(c, 0, sizeof c);
+#pragma omp parallel num_threads(nt)
+        {
+            u64 local[4][4];
+            memset(local, 0, sizeof local);
+#pragma omp for schedule(static) nowait
+            for (size_t i = 0; i < h; ++i) {
+                u64 poly[4][4], nxt[4][4], diff[4], a[4], b[4];
+                /* factor 0: lo + t (hi - lo) */
+                memcpy(poly[0], t[i], 32);
+                fr_sub(t[i + h], t[i], poly[1]);
+                for (int f = 1; f < d; ++f) {   /* poly (degree f) times (lo + t diff) */
+                    const u64 *lo = t[(size_t)f * len + i];
+                    fr_sub(t[(size_t)f * len + i + h], lo, diff);
+                    mont_mul(poly[0], lo, nxt[0]);
+                    for (int k = 1; k <= f; ++k) {
+                        mont_mul(poly[k], lo, a);
+                        mont_mul(poly[k - 1], diff, b);
+                        fr_add(a, b, nxt[k]);
+                    }
+                    mont_mul(poly[f], diff, nxt[f + 1]);
+                    memcpy(poly, nxt, (size_t)(f + 2) * 32);
+                }
+                for (int k = 0; k <= d; ++k) fr_add(local[k], poly[k], local[k]);
+            }
+#pragma omp critical(ogkr_prod)
+            for (int k = 0; k <= d; ++k) fr_add(c[k], local[k], c[k]);
+        }
+        ogkr_fr *row = out_coeffs + (size_t)j * (d + 1);   /* highest degree first */
+        for (int k = 0; k <= d; ++k) from_mont(c[d - k], row[k].l);
+        int length;
+        if (j < n - 1) {
+            length = d + 1;
+            while (length > 1 && !(row[d + 1 - length].l[0] | row[d + 1 - length].l[1] | row[d + 1 - length].l[2] | row[d + 1 - length].l[3]))
+                --length;
+        } else {
+            length = zero_factor ? 1 : 1 + ndep;
+        }
+        for (int k = 0; k < d + 1 - length; ++k) row[k] = zero;   /* (zero already in the last round, by the length rule's own argument) */
+        out_len[j] = (uint32_t)length;
+        ogkr_multi_hash(row + (d + 1 - length), (size_t)length, &zero, &out_r[j]);
+        u64 rm[4];
+        to_mont(out_r[j].l, rm);
+        for (int f = 0; f < d; ++f) fold_table(t + (size_t)f * len, h, rm, nt);
+    }
+    for (int f = 0; f < d; ++f) from_mont(t[(size_t)f * len], out_evals[f].l);
+    free(t);
+    return 0;
+}
+
 static void eq_table(int k, const ogkr_fr *z, u64 (*e)[4]) {
     /* e[g] = prod_i (bit_i(g) ? z_i : 1 - z_i), variable 1 = most significant bit */
     memcpy(e[0], ONE, 32);

@@ -55,6 +55,14 @@ int ogkr_sumcheck_mle(const ogkr_fr *table, int n, ogkr_fr *out_coeffs, uint32_t
 int ogkr_sumcheck_mle_inplace(ogkr_fr *table, int n, ogkr_fr *out_coeffs, uint32_t *out_len,
                               ogkr_fr *out_r, int threads);
 
+/* prove_sumcheck on the product of `degree` (1 .. 3) multilinear tables of 2^n evaluations each, factor f at
+ * tables + f * 2^n: the C twin of tests/product_model.py (its docstring has the rules), coefficients by multiplying
+ * the factors out per index.  out_coeffs: n rows of degree + 1 slots, right-aligned, highest degree first, unused
+ * slots zero; out_evals: the degree entries left after the last fold.  -1: n < 2 or degree outside 1 .. 3;
+ * -2: no memory. */
+int ogkr_sumcheck_product(const ogkr_fr *tables, int n, int degree, ogkr_fr *out_coeffs, uint32_t *out_len,
+                          ogkr_fr *out_r, ogkr_fr *out_evals, int threads);
+
 /* prove_sumcheck_opt for one layer: gates g = 0..2^k_i-1 of type gate_type[g]
  * (0 add, 1 mult) with operands left[g], right[g] in [0, 2^k_next); z has k_i
  * entries; W has 2^k_next evaluations.  out_coeffs: 2*k_next rows of 3 slots,

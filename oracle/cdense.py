@@ -128,6 +128,26 @@ def sumcheck_mle_inplace_raw(table_limbs, n, threads=0):
     return C, L, R
 
 
+def sumcheck_product_raw(tables_limbs, n, degree, threads=0):
+    """ogkr_sumcheck_product on `degree` tables of 2^n entries, one after the other ((degree * 2^n, 4) or (degree, 2^n, 4))
+    -> (coeffs (n, degree + 1, 4) uint64 right-aligned, lens (n,) uint32, r (n, 4) uint64, evals (degree, 4) uint64):
+    one sumcheck's slice of what the product's gkr_sumcheck_product_batch_device returns."""
+    tables_limbs = np.ascontiguousarray(tables_limbs, dtype=np.uint64)
+    if degree < 1 or tables_limbs.size != (degree << n) * 4:
+        raise ValueError("degree tables of 2^n entries expected")
+    C = np.zeros((n, degree + 1, 4), dtype=np.uint64)
+    L = np.zeros(n, dtype=np.uint32)
+    R = np.zeros((n, 4), dtype=np.uint64)
+    E = np.zeros((degree, 4), dtype=np.uint64)
+    fn = lib().ogkr_sumcheck_product
+    fn.restype = ctypes.c_int
+    rc = fn(_p(tables_limbs), ctypes.c_int(n), ctypes.c_int(degree), _p(C), _p(L), _p(R), _p(E),
+            ctypes.c_int(threads if threads > 0 else usable_threads()))
+    if rc:
+        raise ValueError("ogkr_sumcheck_product rc=%d" % rc)
+    return C, L, R, E
+
+
 def sumcheck_mle(table, n, threads=0):
     C, L, R = sumcheck_mle_raw(to_limbs(table), n, threads)
     proof = [from_limbs(C[j])[2 - int(L[j]):] for j in range(n)]

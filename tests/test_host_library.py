@@ -16,6 +16,7 @@ from gkr_amd import _native as N
 from gkr_amd.field import from_limbs, to_limbs
 from oracle import mimc7
 from oracle.field import P
+from product_shapes import PRODUCT_GEOMETRY, product_geometry
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -395,6 +396,24 @@ def _schedule(L, n, mfma):
     assert L.gkr_selftest_pass_schedule(ctypes.c_int(n), ctypes.c_int(mfma), rounds.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(64),
                                         ctypes.byref(count)) == 0
     return rounds[:count.value]
+
+
+def test_launch_geometry_of_the_product_sumcheck():
+    for (n, batch), want in PRODUCT_GEOMETRY.items():
+        g = product_geometry(n, batch)
+        assert tuple(g[:2]) == want, (n, batch, g[:2])
+        for j, (nblk, chunk) in enumerate(g):
+            items = 1 << (n - 1 - j)
+            assert 1 <= nblk <= g[0][0] and chunk % 256 == 0 and nblk * chunk >= items, (n, batch, j)
+    assert [b for b, _ in product_geometry(20, 4)] == [512, 512, 512, 256, 128, 64, 32, 16, 8, 4, 2] + [1] * 9
+    assert product_geometry(20, 64)[0] == product_geometry(20, 1024)[0] == (512, 1024)   # round 0: any batch >= 4 at n = 20
+    lib = N.lib()
+    out = np.zeros(32, dtype=np.uint32)
+    for n, batch in ((1, 1), (31, 1), (16, 0), (16, 65536), (20, 1025)):
+        assert lib.gkr_selftest_product_geometry(n, batch, _p(out), _p(out)) == N.GKR_ERR_INVALID, (n, batch)
+    assert lib.gkr_selftest_product_geometry(16, 1, None, _p(out)) == N.GKR_ERR_INVALID
+    assert lib.gkr_selftest_product_geometry(16, 1, _p(out), None) == N.GKR_ERR_INVALID
+    assert not out.any()
 
 
 def test_limb_widening_for_the_modular_all_reduce():
