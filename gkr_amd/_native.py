@@ -25,6 +25,10 @@ GKR_ERR_UNSUPPORTED = 7
 GKR_VERIFY_OK, GKR_VERIFY_SHAPE, GKR_VERIFY_NON_CANONICAL = 0, 1, 2
 GKR_VERIFY_ROUND_SUM, GKR_VERIFY_CHALLENGE, GKR_VERIFY_EVALUATION = 4, 5, 10
 
+# limits of the sumcheck over a sum of products (gkr_sumcheck_sop*)
+GKR_SOP_MAX_TABLES = 8
+GKR_SOP_MAX_TERMS = 8
+
 GKR_TRANSCRIPT_DEVICE = 0
 GKR_TRANSCRIPT_HOST = 1
 
@@ -36,6 +40,7 @@ SYMBOLS = [
     "gkr_selftest_mul", "gkr_selftest_wide_sum", "gkr_selftest_fold", "gkr_selftest_dot", "gkr_selftest_hash8", "gkr_selftest_host_pass", "gkr_selftest_host_prod_pass", "gkr_selftest_host_tail", "gkr_selftest_pass_schedule", "gkr_selftest_product_geometry", "gkr_selftest_line_restriction", "gkr_selftest_seg_item", "gkr_devtest_field", "gkr_devtest_lazy", "gkr_devtest_reduce", "gkr_devtest_lanes", "gkr_sumcheck_mle", "gkr_sumcheck_mle_batch_device",
     "gkr_sumcheck_product", "gkr_sumcheck_product_batch_device",
     "gkr_sumcheck_product_verify_batch_device", "gkr_sumcheck_product_verify",
+    "gkr_sumcheck_sop_batch_device", "gkr_sumcheck_sop",
     "gkr_mle_eval_batch_device", "gkr_sumcheck_mle_verify_batch_device", "gkr_sumcheck_mle_verify",
     "gkr_sumcheck_layer", "gkr_sumcheck_layer_sharded", "gkr_sumcheck_layer_device", "gkr_resident_layer_create", "gkr_resident_layer_sumcheck", "gkr_resident_layer_sumcheck_wdev", "gkr_resident_layer_free", "gkr_exchange_limbs", "gkr_resident_layer_sumcheck_dev", "gkr_exchange_limbs_mle", "gkr_sumcheck_mle_sharded_dev", "gkr_exchange_rccl_unique_id", "gkr_exchange_rccl_create", "gkr_exchange_rccl_dev",
     "gkr_exchange_rccl_calls", "gkr_exchange_rccl_destroy", "gkr_exchange_rccl_error", "gkr_fr_widen", "gkr_fr_narrow", "gkr_predicate_tables", "gkr_layer_eval", "gkr_proof_sizes", "gkr_prove", "gkr_prove_batch",
@@ -87,6 +92,11 @@ class R1csInfo(ctypes.Structure):
                 ("n_terms", ctypes.c_size_t)]
 
 
+class SopTerm(ctypes.Structure):
+    """gkr_sop_term: one product of `degree` (1 .. 3) tables, table[j] < n_tables for j < degree."""
+    _fields_ = [("degree", ctypes.c_uint8), ("table", ctypes.c_uint8 * 3)]
+
+
 class ProofSizes(ctypes.Structure):
     _fields_ = [(n, ctypes.c_size_t) for n in ("rounds", "q_slots", "z_values", "d_coeffs", "input_coeffs")]
 
@@ -131,6 +141,11 @@ def lib():
         L.gkr_sumcheck_product_verify_batch_device.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 9
         L.gkr_sumcheck_product_verify.restype = ctypes.c_int
         L.gkr_sumcheck_product_verify.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 7
+        # the sum of products: (ctx, tables, n, n_tables, terms, term_coeffs, n_terms[, batch], out_coeffs, out_len, out_r, out_evals)
+        L.gkr_sumcheck_sop_batch_device.restype = ctypes.c_int
+        L.gkr_sumcheck_sop_batch_device.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 4
+        L.gkr_sumcheck_sop.restype = ctypes.c_int
+        L.gkr_sumcheck_sop.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 4
         L.gkr_selftest_product_geometry.restype = ctypes.c_int
         L.gkr_selftest_product_geometry.argtypes = [ctypes.c_int] * 2 + [ctypes.c_void_p] * 2
         for fn in (L.gkr_r1cs_free, L.gkr_layered_free):

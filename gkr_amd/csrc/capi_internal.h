@@ -1,7 +1,8 @@
 // Internals shared by the translation units of the C ABI (gkr_capi.hip: contexts, transcript helpers, self-tests, device
 // memory; capi_mle.hip: the plain sumcheck's entry points, per-round schedules and sessions; capi_mle_passes.hip: its multi-round
 // schedule, whole tables and tables split over ranks; capi_layer.hip: the layer sumcheck over gate lists; capi_layer_dense.hip:
-// its dense form; capi_prove.hip: whole proofs; capi_product.hip: the sumcheck over a product of resident tables): the context,
+// its dense form; capi_prove.hip: whole proofs; capi_product.hip: the sumcheck over a product of resident tables; capi_sop.hip: over a sum of
+// such products): the context,
 // its caches and workspaces, profiling brackets, the host transcript's helpers, the hand-off wait, the plain sumcheck's group
 // hand-off.  Not a public header.
 #pragma once
@@ -749,6 +750,8 @@ int verify_hash_rows_device(gkr_ctx* ctx, int slots, const uint32_t* d_rows, con
 // ---- defined in capi_product.hip
 // the shapes gkr_sumcheck_product* and gkr_sumcheck_product_verify* admit (batch itself, 1 .. 65535, is the caller's check)
 bool product_shape_ok(int n, int degree, int batch);
+// blocks per sumcheck of round `round` (0-based) of the product passes; the sum-of-products passes (capi_sop.hip) launch the same
+uint32_t product_round_blocks(int n, int batch, int round);
 // ---- defined in capi_prove.hip
 void mobius_msb(std::vector<gkr::h64::F>& c, int k);
 void line_restriction(const std::vector<gkr::h64::F>& vals, const std::vector<gkr::h64::F>& coeffs, int k, const gkr_fr* b, const gkr_fr* c,

@@ -10,7 +10,7 @@ namespace gkr_host {
 // Blocks per sumcheck of round `round` (0-based): mle_blocks_per_table of the round's items (round 1: half a table; later: a quarter
 // of the source table), never more than round 1's count, which sizes the partials.  Host logic only; gkr_selftest_product_geometry
 // reports it.
-static uint32_t product_round_blocks(int n, int batch, int round) {
+uint32_t product_round_blocks(int n, int batch, int round) {
     const size_t len = (size_t)1 << n;
     const uint32_t max_nblk = gkr::mle_blocks_per_table((uint32_t)(len / 2), (uint32_t)batch);   // (non-increasing in the items)
     const uint32_t items = (uint32_t)(len >> (round + 1));

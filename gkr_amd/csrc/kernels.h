@@ -263,6 +263,29 @@ void launch_product_round(int degree, const ProductPartial* partials, uint32_t n
                           const Fr* cts, const Fr* work, size_t work_stride, Fr* out_coeffs, uint32_t* out_len, Fr* out_r,
                           FixedMul* rtab, uint32_t* meta, Fr* evals, hipStream_t s);
 
+// ---- sumcheck over a sum of products of resident tables (kernels_sop.hip): g = sum_k c_k prod_j T_{t(k, j)} ----
+// The term structure travels as kernel arguments (wave-uniform).  A pass folds each of the n_tables tables once and leaves per
+// block and term one ProductPartial (partials: batch x nblk x n_terms); the geometry is the product path's.
+constexpr int kSopMaxTables = 8, kSopMaxTerms = 8;
+struct SopTerms {
+    uint32_t n_tables, n_terms, max_degree;
+    uint32_t term[kSopMaxTerms];   // degree | table 0 << 8 | table 1 << 16 | table 2 << 24
+};
+struct SopCoeffs {
+    Fr c[kSopMaxTerms];            // canonical
+};
+// table m of sumcheck b at tables + (b * n_tables + m) * table_stride; h = half a table
+void launch_sop_first(const SopTerms& ts, const Fr* tables, size_t table_stride, uint32_t h, uint32_t batch, uint32_t nblk,
+                      ProductPartial* partials, hipStream_t s);
+// src: 4q entries per table, dst: 2q (dst == src with equal strides: in place); rtab[b * r_stride]: r of the round before
+void launch_sop_fold_sum(const SopTerms& ts, const Fr* src, size_t src_stride, Fr* dst, size_t dst_stride, uint32_t q, uint32_t batch,
+                         uint32_t nblk, const FixedMul* rtab, uint32_t r_stride, ProductPartial* partials, hipStream_t s);
+// out_coeffs: batch x n rows of max_degree + 1 slots; out_len, out_r, rtab: batch x n; evals: batch x n_tables, written in round
+// n - 1 from the tables' two remaining entries at work + (b * n_tables + m) * work_stride
+void launch_sop_round(const SopTerms& ts, const SopCoeffs& cf, const ProductPartial* partials, uint32_t nblk, uint32_t round, uint32_t n,
+                      uint32_t batch, const Fr* cts, const Fr* work, size_t work_stride, Fr* out_coeffs, uint32_t* out_len, Fr* out_r,
+                      FixedMul* rtab, Fr* evals, hipStream_t s);
+
 void launch_layer_eval(uint32_t gates, const uint8_t* gate_type, const uint32_t* left, const uint32_t* right,
                        const Fr* prev, Fr* out, uint32_t batch, uint32_t prev_stride, hipStream_t s, const GateSet* sets = nullptr);
 // words 32-bit words src -> dst (16-byte aligned when words >= 4); either side may be pinned host memory

@@ -380,6 +380,63 @@ class Context:
         self._check(N.lib().gkr_sumcheck_product(self._h, _ptr(limbs), v, degree, _ptr(C), _ptr(L), _ptr(R), _ptr(E)))
         return [from_limbs(C[j])[degree + 1 - int(L[j]):] for j in range(v)], from_limbs(R), from_limbs(E[:degree])
 
+    # -- sumcheck over a sum of products of tables, g = sum_k c_k prod_j T_t(k,j) (prove_sumcheck on add_poly of scaled mult_poly's)
+    @staticmethod
+    def _sop_terms(terms, n_tables):
+        """[(coeff, (table indices ..)), ..] -> (SopTerm array, (K, 4) coefficient limbs, the largest degree)."""
+        K = len(terms)
+        if not 1 <= K <= N.GKR_SOP_MAX_TERMS:
+            raise GkrError(N.GKR_ERR_INVALID, "1 .. %d terms expected" % N.GKR_SOP_MAX_TERMS)
+        arr = (N.SopTerm * K)()
+        for k, (_, idx) in enumerate(terms):
+            idx = tuple(int(i) for i in idx)
+            if not 1 <= len(idx) <= 3 or any(not 0 <= i < n_tables for i in idx):
+                raise GkrError(N.GKR_ERR_INVALID, "a term is a product of 1 .. 3 tables of the call")
+            arr[k].degree = len(idx)
+            for j, i in enumerate(idx):
+                arr[k].table[j] = i
+        return arr, to_limbs([int(c) % MODULUS for c, _ in terms]), max(t.degree for t in arr)
+
+    def sumcheck_sop_batch_device(self, d_tables, n, n_tables, terms, batch, out=None):
+        """gkr_sumcheck_sop_batch_device: `batch` sumchecks of sum_k c_k prod_j T_t(k,j) over n_tables resident tables of 2^n entries
+        each (table m of sumcheck b at d_tables + (b * n_tables + m) * 2^n elements; not modified).  terms: [(coeff, (table
+        indices ..)), ..], shared by the batch.  -> (C, L, R, E): C (batch, n, D + 1, 4) right-aligned round vectors, highest degree
+        first, D the largest term degree; L (batch, n) lengths; R (batch, n, 4) challenges; E (batch, n_tables, 4) the tables'
+        values at the challenges.  out: the four arrays of an earlier call to write into."""
+        arr, coeffs, D = self._sop_terms(terms, n_tables)
+        if out is not None:
+            C, L, R, E = out
+            if C.shape != (batch, n, D + 1, 4) or L.shape != (batch, n) or R.shape != (batch, n, 4) or E.shape != (batch, n_tables, 4):
+                raise GkrError(N.GKR_ERR_INVALID, "output arrays do not match (batch, n, degree, n_tables)")
+        else:
+            C = np.zeros((batch, n, D + 1, 4), dtype=np.uint64)
+            L = np.zeros((batch, n), dtype=np.uint32)
+            R = np.zeros((batch, n, 4), dtype=np.uint64)
+            E = np.zeros((batch, n_tables, 4), dtype=np.uint64)
+        self._check(N.lib().gkr_sumcheck_sop_batch_device(self._h, d_tables, n, n_tables, ctypes.cast(arr, ctypes.c_void_p), _ptr(coeffs),
+                                                          len(terms), batch, _ptr(C), _ptr(L), _ptr(R), _ptr(E)))
+        return C, L, R, E
+
+    def prove_sumcheck_sop(self, tables, terms, v):
+        """Sumcheck of sum_x sum_k c_k prod_j tables[t(k,j)](x) over {0,1}^v: tables is a list of 1 .. 8 tables of 2^v values,
+        terms [(coeff, (table indices ..)), ..] with 1 .. 3 indices each.  -> (proof, r, evals): proof[j] the round vector (its
+        used slots, highest degree first), r the challenges, evals[m] = tables[m]~(r).  verifier.verify_sumcheck_sop checks the
+        transcript against evals on plain integers."""
+        M = len(tables)
+        if not 1 <= M <= N.GKR_SOP_MAX_TABLES:
+            raise GkrError(N.GKR_ERR_INVALID, "1 .. %d tables expected" % N.GKR_SOP_MAX_TABLES)
+        arr, coeffs, D = self._sop_terms(terms, M)
+        limbs = np.concatenate([as_limbs(t) for t in tables], axis=0)
+        if limbs.shape[0] != M << v:
+            raise GkrError(N.GKR_ERR_INVALID, "every table must have 2^v values")
+        C = np.zeros((v, D + 1, 4), dtype=np.uint64)
+        L = np.zeros(v, dtype=np.uint32)
+        R = np.zeros((v, 4), dtype=np.uint64)
+        E = np.zeros((M, 4), dtype=np.uint64)
+        self._check(N.lib().gkr_sumcheck_sop(self._h, _ptr(limbs), v, M, ctypes.cast(arr, ctypes.c_void_p), _ptr(coeffs), len(terms), _ptr(C),
+                                             _ptr(L), _ptr(R), _ptr(E)))
+        return [from_limbs(C[j])[D + 1 - int(L[j]):] for j in range(v)], from_limbs(R), from_limbs(E)
+
     # -- the plain sumcheck's verifier (verify_sumcheck, python/sumcheck.py:55-70, plus g_n(r_n) = T(r)) and the evaluation behind it
     def mle_eval_batch_device(self, d_tables, n, batch, points):
         """gkr_mle_eval_batch_device: the multilinear extension of each of `batch` resident tables of 2^n entries at its own point.
@@ -715,3 +772,7 @@ def prove_sumcheck(table, v):
 
 def prove_sumcheck_product(tables, v):
     return default_context().prove_sumcheck_product(tables, v)
+
+
+def prove_sumcheck_sop(tables, terms, v):
+    return default_context().prove_sumcheck_sop(tables, terms, v)

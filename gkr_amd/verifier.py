@@ -119,6 +119,33 @@ def verify_sumcheck_product(rounds: List[List[int]], challenges: List[int], eval
     return expected == prod
 
 
+def verify_sumcheck_sop(rounds: List[List[int]], challenges: List[int], evals: List[int], terms, claim=None) -> bool:
+    """The verifier of a sum-of-products sumcheck's transcript (Context.prove_sumcheck_sop) on plain integers.  terms:
+    [(coeff, (table indices ..)), ..] as the prover took them; evals[m] the value of table m at the challenges.  Every round
+    vector has 1 .. D + 1 coefficients (D the largest term degree), python/sumcheck.py:55-70 holds on the claim (the first
+    round vector's own sum when none is given), and g_n(r_n) == sum_k c_k prod_j evals[t(k,j)].  That evals[m] is table m's
+    multilinear extension at the challenges is NOT checked here (mle_eval, or Context.mle_eval_batch_device on resident tables)."""
+    if len(terms) < 1 or any(not 1 <= len(idx) <= 3 or any(not 0 <= i < len(evals) for i in idx) for _, idx in terms):
+        return False
+    degree = max(len(idx) for _, idx in terms)
+    if len(rounds) < 1 or len(rounds) != len(challenges) or any(not 1 <= len(g) <= degree + 1 for g in rounds):
+        return False
+    expected = (eval_univariate(rounds[0], 0) + eval_univariate(rounds[0], 1) if claim is None else claim) % P
+    for g, r in zip(rounds, challenges):
+        if (eval_univariate(g, 0) + eval_univariate(g, 1)) % P != expected:
+            return False
+        if multi_hash(g, 0) != r % P:
+            return False
+        expected = eval_univariate(g, r)
+    total = 0
+    for c, idx in terms:
+        prod = c % P
+        for i in idx:
+            prod = prod * evals[i] % P
+        total = (total + prod) % P
+    return expected == total
+
+
 def verify(proof: Proof, circuit: GKRCircuit) -> bool:
     """python/gkr.py:202-231 on the Rust-shaped proof."""
     L = circuit.depth()

@@ -318,6 +318,47 @@ int  gkr_sumcheck_product_batch_device(gkr_ctx *ctx, const void *d_tables, int n
 int  gkr_sumcheck_product(gkr_ctx *ctx, const gkr_fr *tables, int n, int degree,
                           gkr_fr *out_coeffs, uint32_t *out_len, gkr_fr *out_r, gkr_fr *out_evals);
 
+/* ---- sumcheck over a SUM OF PRODUCTS of resident multilinear tables: prove_sumcheck(g, v) with
+ * g = add_poly over k of c_k * mult_poly(get_multi_ext(T_t(k,0)), ..) (sumcheck.rs:158-214, poly.rs:293-386) ----
+ *   g(x) = sum_{k < n_terms} c_k * prod_{j < d_k} T_{t(k,j)}(x)   over n_tables tables of 2^n canonical values each.
+ * The R1CS zero-check sum_x eq(x) (A(x) B(x) - C(x)): 4 tables, terms {3, {0, 1, 2}} and {2, {0, 3}} with coefficients 1, r - 1.
+ * A GKR layer written densely, add (W_b + W_c) + mult W_b W_c; a random linear combination of inner-product claims.  ONE
+ * transcript for all terms; a table that stands in several terms (or several times in one: squares, cubes) is stored once and
+ * folded once per round.  Table m of sumcheck b starts at d_tables + (b * n_tables + m) * 2^n elements; the term structure and
+ * the coefficients (term_coeffs: n_terms canonical elements, NULL = all 1; zero is allowed) are shared by the batch.  Inputs are
+ * not modified; the folded halves live in context workspace of batch * n_tables * 2^(n-1) elements, under slot names of this
+ * path's own (a plain or product call on the same context is unaffected).  D = the largest term degree of the call.
+ *   out_coeffs  batch x n rows of D + 1 slots, right-aligned, highest degree first, unused slots zero: the sum of the terms'
+ *               round polynomials of the current (folded) tables
+ *   out_len     batch x n values in 1 .. D + 1.  EVERY round, the last included: leading zero coefficients dropped, one kept at
+ *               least.  Rounds 1 .. n-1 this is the reference exactly (add_poly merges by exponent and drops zero sums).  In
+ *               round n the reference's length is 1 + deg_{x_n} g as a polynomial; the two differ only where a non-zero
+ *               coefficient polynomial of g vanishes at the hashed point (r_1 .. r_{n-1}): probability at most 3 (n - 1) / r.
+ *   out_r       batch x n challenges, r_j = multi_hash(used slots of round j, key 0)
+ *   out_evals   batch x n_tables values T_m~(r_1 .. r_n), or NULL.  A verifier's last check is
+ *               g_n(r_n) = sum_k c_k prod_j out_evals[t(k,j)].
+ * g identically zero (terms that cancel, a zero factor in every term) is the empty term list, on which the reference panics;
+ * as the library's OWN choice every round vector is then [0] with length 1, as for the product path's zero factor.  With one
+ * term of coefficient 1 over distinct tables the transcript is gkr_sumcheck_product_batch_device's byte for byte, wherever that
+ * path's structural last-round rule and the value rule above agree (always, up to the probability above).
+ * Hashed on the device in both transcript modes; the result does not depend on the context's transcript mode.
+ * GKR_ERR_INVALID before a device or the context is touched (plain returns): NULL ctx or pointer (term_coeffs and out_evals
+ * excepted), batch outside 1 .. 65535, n outside 2 .. GKR_MAX_MLE_N, n_tables outside 1 .. GKR_SOP_MAX_TABLES, n_terms outside
+ * 1 .. GKR_SOP_MAX_TERMS, a term degree outside 1 .. 3, a table index >= n_tables, a table that no term references,
+ * batch * n_tables * 2^n above 2^30 values.  GKR_ERR_NON_CANONICAL (through the context) for a coefficient >= r. */
+#define GKR_SOP_MAX_TABLES 8
+#define GKR_SOP_MAX_TERMS  8
+typedef struct { uint8_t degree; uint8_t table[3]; } gkr_sop_term;   /* degree 1..3, table[j] < n_tables for j < degree */
+int  gkr_sumcheck_sop_batch_device(gkr_ctx *ctx, const void *d_tables, int n, int n_tables, const gkr_sop_term *terms,
+                                   const gkr_fr *term_coeffs /* n_terms, NULL = all 1 */, int n_terms, int batch,
+                                   gkr_fr *out_coeffs, uint32_t *out_len, gkr_fr *out_r, gkr_fr *out_evals /* batch x n_tables or NULL */);
+
+/* `n_tables` tables of 2^n values in host memory, one after the other: upload + the call above with batch 1.
+ * GKR_ERR_NON_CANONICAL also for a table entry >= r. */
+int  gkr_sumcheck_sop(gkr_ctx *ctx, const gkr_fr *tables /* host, n_tables x 2^n */, int n, int n_tables, const gkr_sop_term *terms,
+                      const gkr_fr *term_coeffs, int n_terms,
+                      gkr_fr *out_coeffs, uint32_t *out_len, gkr_fr *out_r, gkr_fr *out_evals);
+
 /* Verifier of gkr_sumcheck_product_batch_device's transcripts: the plain sumcheck's verifier (below; the same driver, the same
  * options) for round polynomials of degree up to 3, one read of every factor.
  * d_tables / coeffs / len / r: exactly the arrays and layout of the prover (factor f of sumcheck b at (b * degree + f) * 2^n
