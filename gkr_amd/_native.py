@@ -21,7 +21,7 @@ GKR_ERR_NOMEM = 5
 GKR_ERR_DEGENERATE = 6
 GKR_ERR_UNSUPPORTED = 7
 
-# verdicts of the verifiers (failed_check); 10 belongs to the plain and the product sumcheck's verifiers alone
+# verdicts of the verifiers (failed_check); 10 belongs to the plain, the product and the sum-of-products sumcheck's verifiers alone
 GKR_VERIFY_OK, GKR_VERIFY_SHAPE, GKR_VERIFY_NON_CANONICAL = 0, 1, 2
 GKR_VERIFY_ROUND_SUM, GKR_VERIFY_CHALLENGE, GKR_VERIFY_EVALUATION = 4, 5, 10
 
@@ -41,6 +41,7 @@ SYMBOLS = [
     "gkr_sumcheck_product", "gkr_sumcheck_product_batch_device",
     "gkr_sumcheck_product_verify_batch_device", "gkr_sumcheck_product_verify",
     "gkr_sumcheck_sop_batch_device", "gkr_sumcheck_sop",
+    "gkr_sumcheck_sop_verify_batch_device", "gkr_sumcheck_sop_verify",
     "gkr_mle_eval_batch_device", "gkr_sumcheck_mle_verify_batch_device", "gkr_sumcheck_mle_verify",
     "gkr_sumcheck_layer", "gkr_sumcheck_layer_sharded", "gkr_sumcheck_layer_device", "gkr_resident_layer_create", "gkr_resident_layer_sumcheck", "gkr_resident_layer_sumcheck_wdev", "gkr_resident_layer_free", "gkr_exchange_limbs", "gkr_resident_layer_sumcheck_dev", "gkr_exchange_limbs_mle", "gkr_sumcheck_mle_sharded_dev", "gkr_exchange_rccl_unique_id", "gkr_exchange_rccl_create", "gkr_exchange_rccl_dev",
     "gkr_exchange_rccl_calls", "gkr_exchange_rccl_destroy", "gkr_exchange_rccl_error", "gkr_fr_widen", "gkr_fr_narrow", "gkr_predicate_tables", "gkr_layer_eval", "gkr_proof_sizes", "gkr_prove", "gkr_prove_batch",
@@ -146,6 +147,12 @@ def lib():
         L.gkr_sumcheck_sop_batch_device.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 4
         L.gkr_sumcheck_sop.restype = ctypes.c_int
         L.gkr_sumcheck_sop.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 4
+        # its verifier: (ctx, tables, n, n_tables, terms, term_coeffs, n_terms[, batch], claims, coeffs, len, r, accept, failed_round,
+        # failed_check[, out_claims, out_evals])
+        L.gkr_sumcheck_sop_verify_batch_device.restype = ctypes.c_int
+        L.gkr_sumcheck_sop_verify_batch_device.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 9
+        L.gkr_sumcheck_sop_verify.restype = ctypes.c_int
+        L.gkr_sumcheck_sop_verify.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 7
         L.gkr_selftest_product_geometry.restype = ctypes.c_int
         L.gkr_selftest_product_geometry.argtypes = [ctypes.c_int] * 2 + [ctypes.c_void_p] * 2
         for fn in (L.gkr_r1cs_free, L.gkr_layered_free):

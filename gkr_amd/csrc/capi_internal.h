@@ -752,6 +752,11 @@ int verify_hash_rows_device(gkr_ctx* ctx, int slots, const uint32_t* d_rows, con
 bool product_shape_ok(int n, int degree, int batch);
 // blocks per sumcheck of round `round` (0-based) of the product passes; the sum-of-products passes (capi_sop.hip) launch the same
 uint32_t product_round_blocks(int n, int batch, int round);
+// ---- defined in capi_sop.hip
+// the shapes gkr_sumcheck_sop* and gkr_sumcheck_sop_verify* admit, with the term structure in the kernels' form; the term
+// coefficients in the kernels' form (NULL: all one), false: one is >= r
+bool sop_shape(int n, int n_tables, const gkr_sop_term* terms, int n_terms, int batch, gkr::SopTerms* ts);
+bool sop_coeffs(const gkr_fr* term_coeffs, int n_terms, gkr::SopCoeffs* cf);
 // ---- defined in capi_prove.hip
 void mobius_msb(std::vector<gkr::h64::F>& c, int k);
 void line_restriction(const std::vector<gkr::h64::F>& vals, const std::vector<gkr::h64::F>& coeffs, int k, const gkr_fr* b, const gkr_fr* c,

@@ -51,9 +51,9 @@ static int run_sop_batch(gkr_ctx* ctx, const Fr* d_tables, int n, const gkr::Sop
     return GKR_OK;
 }
 
-// The shape checks of both entry points (plain returns: decided before the context is looked at), and the term structure in
-// the kernels' form.  false: GKR_ERR_INVALID.
-static bool sop_shape(int n, int n_tables, const gkr_sop_term* terms, int n_terms, int batch, gkr::SopTerms* ts) {
+// The shape checks of the prover's and the verifier's (capi_mle_verify.hip) entry points (plain returns: decided before the
+// context is looked at), and the term structure in the kernels' form.  false: GKR_ERR_INVALID.
+bool sop_shape(int n, int n_tables, const gkr_sop_term* terms, int n_terms, int batch, gkr::SopTerms* ts) {
     if (batch < 1 || batch > 65535) return false;
     if (n < 2 || n > GKR_MAX_MLE_N) return false;
     if (n_tables < 1 || n_tables > GKR_SOP_MAX_TABLES || n_terms < 1 || n_terms > GKR_SOP_MAX_TERMS) return false;
@@ -80,7 +80,7 @@ static bool sop_shape(int n, int n_tables, const gkr_sop_term* terms, int n_term
 }
 
 // the coefficients in the kernels' form (NULL: all one); false: one is >= r
-static bool sop_coeffs(const gkr_fr* term_coeffs, int n_terms, gkr::SopCoeffs* cf) {
+bool sop_coeffs(const gkr_fr* term_coeffs, int n_terms, gkr::SopCoeffs* cf) {
     memset(cf, 0, sizeof *cf);
     for (int k = 0; k < n_terms; ++k) {
         if (term_coeffs)

@@ -447,10 +447,12 @@ void launch_verify_hash(int slots, const uint32_t* rows, const uint32_t* len, ui
 constexpr uint32_t kMleEvalMfmaValidN = 11, kMleEvalMfmaMinN = 13, kMleEvalSmallMaxN = 24;
 bool mle_eval_uses_mfma(uint32_t n);
 uint32_t mle_eval_blocks(uint32_t n, uint32_t batch);      // blocks per table of the streaming form
-size_t mle_eval_ws_bytes(uint32_t n, uint32_t batch);      // device workspace of one launch_mle_eval
-// out[b] = sum_i eq(points[b * n ..+n), i) tables[(b << n) + i] (canonical) for `batch` tables of 2^n entries, 1 <= n <= 30;
-// points: batch x n canonical elements in device memory, variable 1 = most significant index bit.  ws: mle_eval_ws_bytes().
-void launch_mle_eval(const Fr* tables, uint32_t n, uint32_t batch, const Fr* points, void* ws, Fr* out, hipStream_t s);
+size_t mle_eval_ws_bytes(uint32_t n, uint32_t groups, uint32_t G);   // device workspace of one launch_mle_eval
+// groups x G tables of 2^n entries, 1 <= n <= 30; the G tables of a group share a point (G = 1: every table its own):
+// out[t] = sum_i eq(points[g * n ..+n), i) tables[(t << n) + i] (canonical) for t = g G + m, m < G.  points: groups x n canonical
+// elements in device memory, variable 1 = most significant index bit.  What depends on the point alone is built once per group;
+// every value is bit for bit the one G = 1 gives with the point repeated.  ws: mle_eval_ws_bytes().
+void launch_mle_eval(const Fr* tables, uint32_t n, uint32_t groups, uint32_t G, const Fr* points, void* ws, Fr* out, hipStream_t s);
 
 uint32_t layer_blocks(uint32_t h);
 void launch_layer_round(const Fr* A, const Fr* M, uint32_t h, uint32_t k, uint32_t phase, uint32_t hb, const Fr* Wb,

@@ -24,6 +24,9 @@
 //
 // Set-up per chunk of tables (launch_mle_eval): the leading weights and the two tables E_up, E_63 come from launch_eq_table
 // (its layout is the one needed: proof-major, MSB-first, Montgomery), the plans from launch_mle_fold_plan -- the prover's kernels.
+// Tables come in GROUPS of G that share one point (the M tables of a sumcheck; G = 1: every table its own point): table g G + m
+// is evaluated at point g, and everything that depends on the point alone -- weights, plan, E_up, E_63 -- is built once per
+// group.  The partials, the second-level sums and the values stay per table, and each is computed exactly as at G = 1.
 // Table entries are read as 256-bit integers: any value is taken modulo r (the byte-wise fold and the lazy sums are exact).
 #include "dev_util.h"
 #include "kernels.h"
@@ -39,22 +42,25 @@ constexpr uint32_t kEvalMinChunk = 256;     // one iteration of the block's four
 constexpr uint32_t kEvalFillBlocks = 2048;  // blocks over the batch below which the chunks are made shorter (8 per CU)
 constexpr uint32_t kEvalMaxBlocks = 4096;   // per table
 
-// grid = (nblk, batch), block = 256; chunk = 2^(n-5) / nblk a multiple of 64
-__global__ void __launch_bounds__(256) k_mle_eval_mfma(const Fr* __restrict__ tables, uint32_t n, const MfmaFoldPlan* __restrict__ plans,
+// grid = (nblk, tables), block = 256; chunk = 2^(n-5) / nblk a multiple of 64; plans, e_up, e_63: one per group of G tables
+__global__ void __launch_bounds__(256) k_mle_eval_mfma(const Fr* __restrict__ tables, uint32_t n, uint32_t G, const MfmaFoldPlan* __restrict__ plans,
                                                        const Fr* __restrict__ e_up, const Fr* __restrict__ e_63, Acc<9>* __restrict__ partials) {
     __shared__ Acc<9> smem[4];
     __shared__ __attribute__((aligned(16))) unsigned char digits[32 * 32 * (1 << kMfmaMaxJ)];
     const uint32_t m = n - (uint32_t)kMfmaMaxJ, S = 1u << m;
     const Fr* s = tables + ((size_t)blockIdx.y << n);
-    const Fr* up = e_up + ((size_t)blockIdx.y << (m - 6u));
+    // (the table's group: the same on every lane, and said so -- the quotient of two scalars is computed on the vector unit, and
+    // E_up's entries and the plan are scalar loads only from an address in scalar registers)
+    const uint32_t grp = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.y / G));
+    const Fr* up = e_up + ((size_t)grp << (m - 6u));
     const uint32_t chunk = S / gridDim.x;
     const uint32_t begin = blockIdx.x * chunk;
     Lazy17 sum = lazy_zero();   // sum over this lane's outputs of y * E_up[i >> 6] (E_up Montgomery), unreduced
-    mfma_multifold_stream<kMfmaMaxJ>(s, S, plans + blockIdx.y, begin, begin + chunk, blockIdx.x * 5u + blockIdx.y * 3u, digits,
+    mfma_multifold_stream<kMfmaMaxJ>(s, S, plans + grp, begin, begin + chunk, blockIdx.x * 5u + blockIdx.y * 3u, digits,
                                      [&](uint32_t e0, uint32_t, uint32_t, const Fr& y) { lazy_mac_s(sum, y, load_fr(up + (e0 >> 6))); });
     // (the waves a short chunk leaves idle arrive here with a zero sum)
     Acc<9> acc[1] = {acc_zero<9>()};
-    acc_add_fr(acc[0], mont_mul(lazy_reduce(sum), load_fr(e_63 + (size_t)blockIdx.y * 64u + (threadIdx.x & 63u))));
+    acc_add_fr(acc[0], mont_mul(lazy_reduce(sum), load_fr(e_63 + (size_t)grp * 64u + (threadIdx.x & 63u))));
     block_sum<9, 1>(acc, smem);
     if (threadIdx.x == 0) partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = acc[0];
 }
@@ -72,8 +78,8 @@ __global__ void __launch_bounds__(256) k_mle_eval_reduce(const Acc<9>* __restric
 // One block per table, any n >= 1.  The index splits into (top | mid | low): thread t owns the entries whose low
 // nl = min(n, 8) bits are t; per value of the top bits it sums its 2^nm (nm <= 8) entries against the mid table unreduced, reduces,
 // and adds the result times the top bits' weight to a second unreduced sum; its own low weight comes last, once.
-// grid = (batch), block = 256
-__global__ void __launch_bounds__(256) k_mle_eval_small(const Fr* __restrict__ tables, uint32_t n, const Fr* __restrict__ points,
+// grid = (tables), block = 256; points: one per group of G tables
+__global__ void __launch_bounds__(256) k_mle_eval_small(const Fr* __restrict__ tables, uint32_t n, uint32_t G, const Fr* __restrict__ points,
                                                         Fr* __restrict__ out) {
     __shared__ Fr s_f[2][32];   // Montgomery forms of 1 - r_j and r_j
     __shared__ Fr s_lo[256], s_mid[256];
@@ -82,7 +88,7 @@ __global__ void __launch_bounds__(256) k_mle_eval_small(const Fr* __restrict__ t
     const uint32_t nl = n < 8u ? n : 8u, nm = n - nl < 8u ? n - nl : 8u, nt = n - nl - nm;
     const Fr* t = tables + ((size_t)blockIdx.x << n);
     if (tid < n) {
-        const Fr x = load_fr(points + (size_t)blockIdx.x * n + tid);
+        const Fr x = load_fr(points + (size_t)(blockIdx.x / G) * n + tid);
         Fr one = fr_zero();
         one.l[0] = 1u;
         s_f[1][tid] = to_mont(x);
@@ -120,22 +126,23 @@ struct EvalWs {
     Acc<9>* partials;
     size_t bytes;
 };
-// the streaming form's workspace of a chunk, carved out of one allocation (every part 16-byte aligned)
-EvalWs eval_ws(void* base, uint32_t n, uint32_t batch, uint32_t nblk) {
+// the streaming form's workspace of a chunk, carved out of one allocation (every part 16-byte aligned): what belongs to a point
+// once per group, the partials per table
+EvalWs eval_ws(void* base, uint32_t n, uint32_t groups, uint32_t G, uint32_t nblk) {
     auto up16 = [](size_t x) { return (x + 15u) & ~(size_t)15u; };
     char* p = static_cast<char*>(base);
     EvalWs w;
     size_t off = 0;
     w.plans = reinterpret_cast<MfmaFoldPlan*>(p + off);
-    off += up16((size_t)batch * sizeof(MfmaFoldPlan));
+    off += up16((size_t)groups * sizeof(MfmaFoldPlan));
     w.weights = reinterpret_cast<Fr*>(p + off);
-    off += (size_t)batch * kMleMaxSub * sizeof(Fr);
+    off += (size_t)groups * kMleMaxSub * sizeof(Fr);
     w.e_up = reinterpret_cast<Fr*>(p + off);
-    off += ((size_t)batch << (n - 11u)) * sizeof(Fr);
+    off += ((size_t)groups << (n - 11u)) * sizeof(Fr);
     w.e_63 = reinterpret_cast<Fr*>(p + off);
-    off += (size_t)batch * 64u * sizeof(Fr);
+    off += (size_t)groups * 64u * sizeof(Fr);
     w.partials = reinterpret_cast<Acc<9>*>(p + off);
-    off += up16((size_t)batch * nblk * sizeof(Acc<9>));
+    off += up16((size_t)groups * G * nblk * sizeof(Acc<9>));
     w.bytes = off;
     return w;
 }
@@ -157,23 +164,24 @@ uint32_t mle_eval_blocks(uint32_t n, uint32_t batch) {
     return b > kEvalMaxBlocks ? kEvalMaxBlocks : b;
 }
 
-size_t mle_eval_ws_bytes(uint32_t n, uint32_t batch) {
+size_t mle_eval_ws_bytes(uint32_t n, uint32_t groups, uint32_t G) {
     if (!mle_eval_uses_mfma(n)) return 16;
-    return eval_ws(nullptr, n, batch, mle_eval_blocks(n, batch)).bytes;
+    return eval_ws(nullptr, n, groups, G, mle_eval_blocks(n, groups * G)).bytes;
 }
 
-void launch_mle_eval(const Fr* tables, uint32_t n, uint32_t batch, const Fr* points, void* ws, Fr* out, hipStream_t s) {
+void launch_mle_eval(const Fr* tables, uint32_t n, uint32_t groups, uint32_t G, const Fr* points, void* ws, Fr* out, hipStream_t s) {
+    const uint32_t batch = groups * G;   // tables
     if (!mle_eval_uses_mfma(n)) {
-        hipLaunchKernelGGL(k_mle_eval_small, dim3(batch), dim3(256), 0, s, tables, n, points, out);
+        hipLaunchKernelGGL(k_mle_eval_small, dim3(batch), dim3(256), 0, s, tables, n, G, points, out);
         return;
     }
     const uint32_t nblk = mle_eval_blocks(n, batch);
-    const EvalWs w = eval_ws(ws, n, batch, nblk);
-    launch_eq_table(points, n, 0u, (uint32_t)kMfmaMaxJ, w.weights, true, batch, s);
-    launch_eq_table(points, n, (uint32_t)kMfmaMaxJ, n - 11u, w.e_up, true, batch, s);
-    launch_eq_table(points, n, n - 6u, 6u, w.e_63, true, batch, s);
-    launch_mle_fold_plan(kMfmaMaxJ, w.weights, w.plans, batch, s);
-    hipLaunchKernelGGL(k_mle_eval_mfma, dim3(nblk, batch), dim3(256), 0, s, tables, n, w.plans, w.e_up, w.e_63, w.partials);
+    const EvalWs w = eval_ws(ws, n, groups, G, nblk);
+    launch_eq_table(points, n, 0u, (uint32_t)kMfmaMaxJ, w.weights, true, groups, s);
+    launch_eq_table(points, n, (uint32_t)kMfmaMaxJ, n - 11u, w.e_up, true, groups, s);
+    launch_eq_table(points, n, n - 6u, 6u, w.e_63, true, groups, s);
+    launch_mle_fold_plan(kMfmaMaxJ, w.weights, w.plans, groups, s);
+    hipLaunchKernelGGL(k_mle_eval_mfma, dim3(nblk, batch), dim3(256), 0, s, tables, n, G, w.plans, w.e_up, w.e_63, w.partials);
     hipLaunchKernelGGL(k_mle_eval_reduce, dim3(batch), dim3(256), 0, s, w.partials, nblk, out);
 }
 

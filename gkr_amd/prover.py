@@ -420,8 +420,9 @@ class Context:
     def prove_sumcheck_sop(self, tables, terms, v):
         """Sumcheck of sum_x sum_k c_k prod_j tables[t(k,j)](x) over {0,1}^v: tables is a list of 1 .. 8 tables of 2^v values,
         terms [(coeff, (table indices ..)), ..] with 1 .. 3 indices each.  -> (proof, r, evals): proof[j] the round vector (its
-        used slots, highest degree first), r the challenges, evals[m] = tables[m]~(r).  verifier.verify_sumcheck_sop checks the
-        transcript against evals on plain integers."""
+        used slots, highest degree first), r the challenges, evals[m] = tables[m]~(r).  Context.verify_sumcheck_sop(tables, terms,
+        proof, r) checks the transcript AND that it belongs to these tables (it evaluates them at r on the device);
+        verifier.verify_sumcheck_sop checks the transcript against evals on plain integers."""
         M = len(tables)
         if not 1 <= M <= N.GKR_SOP_MAX_TABLES:
             raise GkrError(N.GKR_ERR_INVALID, "1 .. %d tables expected" % N.GKR_SOP_MAX_TABLES)
@@ -535,6 +536,58 @@ class Context:
         accept, rnd, check = ctypes.c_int(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
         self._check(N.lib().gkr_sumcheck_product_verify(self._h, _ptr(limbs), n, degree, _ptr(cl) if cl is not None else None, _ptr(C), _ptr(L),
                                                         _ptr(R), ctypes.byref(accept), ctypes.byref(rnd), ctypes.byref(check)))
+        return bool(accept.value), int(rnd.value), int(check.value)
+
+    # -- the sum-of-products sumcheck's verifier: the same checks on rows of D + 1 slots, g_n(r_n) = sum_k c_k prod_j T_t(k,j)~(r)
+    def verify_sumcheck_sop_batch_device(self, d_tables, n, n_tables, terms, batch, C, L, R, claims=None):
+        """gkr_sumcheck_sop_verify_batch_device on the resident tables, the terms ([(coeff, (table indices ..)), ..]) and the arrays
+        sumcheck_sop_batch_device returned (C (batch, n, D + 1, 4), D the largest term degree; L (batch, n); R (batch, n, 4));
+        claims: (batch, 4) uint64 limbs or None (round 0's sum check is skipped, the proven sums are returned; a zero-check passes
+        zeros).  -> (accept (batch,) bool, failed_round (batch,) uint32, failed_check (batch,) uint32, claims (batch, 4) uint64,
+        evals (batch, n_tables, 4) uint64: the tables' values at the challenges as computed here)."""
+        arr, coeffs, D = self._sop_terms(terms, n_tables)
+        C = np.ascontiguousarray(C, dtype=np.uint64)
+        L = np.ascontiguousarray(L, dtype=np.uint32)
+        R = np.ascontiguousarray(R, dtype=np.uint64)
+        if n_tables < 1 or C.shape != (batch, n, D + 1, 4) or L.shape != (batch, n) or R.shape != (batch, n, 4):
+            raise GkrError(N.GKR_ERR_INVALID, "transcript arrays do not match (batch, n, the largest term degree)")
+        if claims is not None:
+            claims = np.ascontiguousarray(claims, dtype=np.uint64)
+            if claims.shape != (batch, 4):
+                raise GkrError(N.GKR_ERR_INVALID, "claims of shape (batch, 4) expected")
+        accept = np.zeros(batch, dtype=np.int32)
+        rnd, check = np.zeros(batch, dtype=np.uint32), np.zeros(batch, dtype=np.uint32)
+        out = np.zeros((batch, 4), dtype=np.uint64)
+        evals = np.zeros((batch, n_tables, 4), dtype=np.uint64)
+        self._check(N.lib().gkr_sumcheck_sop_verify_batch_device(
+            self._h, d_tables, n, n_tables, ctypes.cast(arr, ctypes.c_void_p), _ptr(coeffs), len(terms), batch,
+            _ptr(claims) if claims is not None else None, _ptr(C), _ptr(L), _ptr(R), _ptr(accept), _ptr(rnd), _ptr(check), _ptr(out), _ptr(evals)))
+        return accept.astype(bool), rnd, check, out, evals
+
+    def verify_sumcheck_sop(self, tables, terms, proof, r, claim=None):
+        """gkr_sumcheck_sop_verify on what prove_sumcheck_sop returned: tables the 1 .. 8 tables, terms as the prover took them,
+        proof[j] the round vector (1 .. D + 1 coefficients, highest degree first), r the challenges; claim: the sum the transcript
+        is to prove, or None.  -> (accept, failed_round, failed_check)."""
+        M, n = len(tables), len(proof)
+        if not 1 <= M <= N.GKR_SOP_MAX_TABLES:
+            raise GkrError(N.GKR_ERR_INVALID, "1 .. %d tables expected" % N.GKR_SOP_MAX_TABLES)
+        arr, coeffs, D = self._sop_terms(terms, M)
+        limbs = np.concatenate([as_limbs(t) for t in tables], axis=0)
+        if n < 1 or limbs.shape[0] != M << n or len(r) != n:
+            raise GkrError(N.GKR_ERR_INVALID, "tables of 2^n entries each, n round vectors and n challenges expected")
+        C = np.zeros((n, D + 1, 4), dtype=np.uint64)
+        L = np.zeros(n, dtype=np.uint32)
+        for j, g in enumerate(proof):
+            if not 1 <= len(g) <= D + 1:
+                raise GkrError(N.GKR_ERR_INVALID, "a round vector has 1 .. D + 1 coefficients, D the largest term degree")
+            L[j] = len(g)
+            C[j, D + 1 - len(g):] = to_limbs(g)
+        R = to_limbs(r)
+        cl = to_limbs([claim]) if claim is not None else None
+        accept, rnd, check = ctypes.c_int(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+        self._check(N.lib().gkr_sumcheck_sop_verify(self._h, _ptr(limbs), n, M, ctypes.cast(arr, ctypes.c_void_p), _ptr(coeffs), len(terms),
+                                                    _ptr(cl) if cl is not None else None, _ptr(C), _ptr(L), _ptr(R), ctypes.byref(accept),
+                                                    ctypes.byref(rnd), ctypes.byref(check)))
         return bool(accept.value), int(rnd.value), int(check.value)
 
     # -- layer sumcheck (prove_sumcheck_opt, sumcheck.rs:36-156)

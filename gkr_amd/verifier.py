@@ -124,7 +124,9 @@ def verify_sumcheck_sop(rounds: List[List[int]], challenges: List[int], evals: L
     [(coeff, (table indices ..)), ..] as the prover took them; evals[m] the value of table m at the challenges.  Every round
     vector has 1 .. D + 1 coefficients (D the largest term degree), python/sumcheck.py:55-70 holds on the claim (the first
     round vector's own sum when none is given), and g_n(r_n) == sum_k c_k prod_j evals[t(k,j)].  That evals[m] is table m's
-    multilinear extension at the challenges is NOT checked here (mle_eval, or Context.mle_eval_batch_device on resident tables)."""
+    multilinear extension at the challenges is NOT checked here: Context.verify_sumcheck_sop (host tables) and
+    Context.verify_sumcheck_sop_batch_device (resident tables) check the transcript against the tables themselves, on the device,
+    and return the values they computed."""
     if len(terms) < 1 or any(not 1 <= len(idx) <= 3 or any(not 0 <= i < len(evals) for i in idx) for _, idx in terms):
         return False
     degree = max(len(idx) for _, idx in terms)

@@ -392,6 +392,37 @@ int gkr_sumcheck_product_verify(gkr_ctx *ctx, const gkr_fr *tables, int n, int d
                                 const gkr_fr *coeffs, const uint32_t *len, const gkr_fr *r,
                                 int *accept, uint32_t *failed_round, uint32_t *failed_check);
 
+/* Verifier of gkr_sumcheck_sop_batch_device's transcripts: the same driver and options as the product verifier above, with the
+ * caller's term structure; one read of every table, all n_tables tables of a sumcheck evaluated at its one point (the point's
+ * weights are built once per sumcheck).
+ * d_tables / terms / term_coeffs / coeffs / len / r: exactly the arrays and layout of the prover (table m of sumcheck b at
+ * (b * n_tables + m) * 2^n elements; batch x n rows of D + 1 right-aligned slots, D the largest term degree; len in 1 .. D + 1;
+ * batch x n challenges).  claims: batch elements or NULL; a zero-check passes zeros.
+ * accept[batch] required; failed_round / failed_check / out_claims (batch) / out_evals (batch x n_tables) may be NULL.
+ * The checks and their order are the product verifier's 1 .. 3 (SHAPE, NON_CANONICAL, per round ROUND_SUM / CHALLENGE), then
+ *   4. GKR_VERIFY_EVALUATION      g_n(r_n) != sum_k c_k prod_j T_{t(k,j)}~(r_1 .. r_n); failed_round = n
+ * out_claims[b] = g_1(0) + g_1(1) and out_evals[b * n_tables + m] = T_m~(r) as the device computed it, for every transcript that
+ * passes checks 1 and 2; zero for the others.  The library's all-[0] transcripts of an identically zero g need no special case.
+ * A change of a table shows exactly when it moves the sum of the terms: not behind a zero coefficient or cofactor, not in terms
+ * that cancel.  The verifier given other terms or coefficients than the prover's checks the transcript against THOSE.
+ * GKR_ERR_INVALID before a device or the context is touched (plain returns): NULL ctx or required pointer (term_coeffs, claims and
+ * the optional outputs excepted), and every shape the prover refuses (batch outside 1 .. 65535, n outside 2 .. GKR_MAX_MLE_N,
+ * n_tables outside 1 .. GKR_SOP_MAX_TABLES, n_terms outside 1 .. GKR_SOP_MAX_TERMS, a term degree outside 1 .. 3, a table index
+ * >= n_tables, a table that no term references, batch * n_tables * 2^n above 2^30 values).  GKR_ERR_NON_CANONICAL (through the
+ * context) for a coefficient >= r.  Chunks are counted in sumchecks (the tables of one sumcheck are never split); verdicts depend
+ * neither on verify_workspace_mb nor on verify_device_hash_min nor on mle_eval_mfma_min_n. */
+int gkr_sumcheck_sop_verify_batch_device(gkr_ctx *ctx, const void *d_tables, int n, int n_tables, const gkr_sop_term *terms,
+                                         const gkr_fr *term_coeffs /* n_terms, NULL = all 1 */, int n_terms, int batch,
+                                         const gkr_fr *claims /* batch or NULL */, const gkr_fr *coeffs, const uint32_t *len, const gkr_fr *r,
+                                         int *accept, uint32_t *failed_round, uint32_t *failed_check,
+                                         gkr_fr *out_claims /* batch or NULL */, gkr_fr *out_evals /* batch x n_tables or NULL */);
+
+/* `n_tables` tables in host memory, one after the other: upload + the call above with batch 1.  GKR_ERR_NON_CANONICAL also for a
+ * table entry >= r, as gkr_sumcheck_sop. */
+int gkr_sumcheck_sop_verify(gkr_ctx *ctx, const gkr_fr *tables /* host, n_tables x 2^n */, int n, int n_tables, const gkr_sop_term *terms,
+                            const gkr_fr *term_coeffs, int n_terms, const gkr_fr *claim, const gkr_fr *coeffs, const uint32_t *len,
+                            const gkr_fr *r, int *accept, uint32_t *failed_round, uint32_t *failed_check);
+
 /* ---- the plain sumcheck's verifier: verify_sumcheck, python/sumcheck.py:55-70, and the relation behind it -------------
  * A transcript of prove_sumcheck proves "sum of the table = claim" only together with g_n(r_n) = T~(r_1 .. r_n), the table's
  * multilinear extension at the challenges: one read of the table (32 * 2^n bytes, where the prover's default schedule moves
@@ -724,7 +755,8 @@ enum {
     GKR_VERIFY_R_STAR = 7,         /* r* != multi_hash(last round vector) */
     GKR_VERIFY_NEXT_Z = 8,         /* z[i+1] != b* + r* (c* - b*) */
     GKR_VERIFY_INPUT = 9,          /* q(r*) of the last layer != input_func(z[L]) */
-    GKR_VERIFY_EVALUATION = 10     /* plain and product sumcheck (gkr_sumcheck_*_verify*): g_n(r_n) != prod_f T_f~(r) */
+    GKR_VERIFY_EVALUATION = 10     /* plain, product and sum-of-products sumcheck (gkr_sumcheck_*_verify*): g_n(r_n) != the tables'
+                                      values at r combined as the sumcheck combines them: T~(r), prod_f T_f~(r), sum_k c_k prod_j T_t(k,j)~(r) */
 };
 int  gkr_verify(const gkr_circuit_desc *circuit, const gkr_proof_buf *proof, int threads, int *accept, uint32_t *failed_layer,
                 uint32_t *failed_check);

@@ -1,5 +1,5 @@
-"""Sumcheck over a sum of products of resident tables (gkr_sumcheck_sop_batch_device) at n = 20, batch in {1, 64}, three term
-structures:
+"""Sumcheck over a sum of products of resident tables (gkr_sumcheck_sop_batch_device) at n = 20, batch in {1, 64} (--batches),
+three term structures:
 
   * eq (A B - C):  4 tables, terms (0, 1, 2) and -(0, 3) -- the R1CS zero-check;
   * A B + C D:     4 tables, two terms of degree 2;
@@ -12,6 +12,14 @@ output is checked: the first against verify_sumcheck_sop on every sumcheck and a
 tables, every later one for equality with the first.  Then --profile-reps calls under the context profile give the per-call kernel
 times by name (sop_first, sop_fold_sum, sop_round) -- the pass / round split.  For the single term `sop_over_product` is the
 ratio of the medians and `behind_by_iqrs` the difference of the medians in units of the larger of the two interquartile ranges.
+
+The verify leg, same process and tables (after tools/bench_product.py's): gkr_sumcheck_sop_verify_batch_device on the transcripts
+just proved, alternating with a bare gkr_mle_eval_batch_device call on the same batch * n_tables tables with every point repeated
+n_tables times -- the evaluation alone, every table on its own, the yardstick of what the verifier's one read of the tables should
+cost.  Per call: host-clock medians and spread, the `mle_eval` (and `verify_hash`) entries of the context profile, and the
+fraction of the box's read ceiling (gkr_ubench_ceilings, measured in this process) that the tables' batch * n_tables * 32 * 2^n
+bytes reach in the call and in its `mle_eval` entry.  Checked: every transcript accepted, the values equal to the prover's and to
+the bare evaluation's.  What the call costs above the bare evaluation is reported, not gated.
 
 Informational: no threshold.  Prints one JSON line; --out also writes it to a file."""
 
@@ -58,11 +66,48 @@ def check(ctx, d, n, n_tables, terms, batch, out):
     return bool(np.array_equal(ctx.mle_eval_batch_device(d, n, batch * n_tables, np.repeat(R, n_tables, axis=0)), E.reshape(-1, 4)))
 
 
+def verify_leg(ctx, d, n, n_tables, terms, batch, proved, args, ceil):
+    C, L, R, E = proved
+    tables = batch * n_tables
+    points = np.ascontiguousarray(np.repeat(R, n_tables, axis=0))
+    verify = lambda: ctx.verify_sumcheck_sop_batch_device(d, n, n_tables, terms, batch, C, L, R)
+    bare = lambda: ctx.mle_eval_batch_device(d, n, tables, points)
+    accepted = lambda res: bool(res[0].all()) and res[4].tobytes() == E.tobytes()
+    ok = accepted(verify())                                                                    # warm-up
+    ok = ok and bare().tobytes() == E.tobytes()
+    t_verify, t_bare = [], []
+    for _ in range(args.reps):
+        ms, res = timed(verify)
+        t_verify.append(ms)
+        ok = ok and accepted(res)
+        ms, got = timed(bare)
+        t_bare.append(ms)
+        ok = ok and got.tobytes() == E.tobytes()
+    ctx.profile(1)
+    entries = {}
+    for name, call in (("verify", verify), ("bare", bare)):
+        ctx.profile_reset()
+        for _ in range(args.profile_reps):
+            call()
+        entries[name] = {k: ctx.profile_get(k)["total_ms"] / args.profile_reps for k in ("mle_eval", "verify_hash")}
+    ctx.profile(0)
+    v, b = spread(t_verify), spread(t_bare)
+    floor_ms = tables * 32.0 * (1 << n) / (ceil["read_GBps"] * 1e6)
+    return {"ok": ok, "verify": v, "bare_mle_eval": b, "table_bytes": tables * 32 * (1 << n), "read_floor_ms": floor_ms,
+            "verify_profile_ms_per_call": entries["verify"], "bare_profile_ms_per_call": entries["bare"],
+            "verify_call_fraction_of_read_ceiling": floor_ms / v["median_ms"], "bare_call_fraction_of_read_ceiling": floor_ms / b["median_ms"],
+            "verify_mle_eval_fraction_of_read_ceiling": floor_ms / entries["verify"]["mle_eval"],
+            "bare_mle_eval_fraction_of_read_ceiling": floor_ms / entries["bare"]["mle_eval"],
+            "verify_minus_bare_ms": v["median_ms"] - b["median_ms"], "device_hashes": entries["verify"]["verify_hash"] > 0}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--n", type=int, default=20)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--profile-reps", type=int, default=5)
+    ap.add_argument("--batches", default="1,64", help="batch sizes, comma-separated")
+    ap.add_argument("--ceiling-bytes", type=int, default=2 << 30)
     ap.add_argument("--out")
     args = ap.parse_args()
     n = args.n
@@ -71,8 +116,9 @@ def main():
     with Context(0) as ctx:
         result["device"] = ctx.device_name()
         result["cpus"] = len(os.sched_getaffinity(0))
+        ceil = result["ceilings"] = ctx.ceilings(args.ceiling_bytes)
         for name, n_tables, terms in STRUCTURES:
-            for batch in (1, 64):
+            for batch in [int(b) for b in args.batches.split(",")]:
                 tables = batch * n_tables
                 d = ctx.alloc((tables << n) * 32)
                 try:
@@ -104,6 +150,8 @@ def main():
                         kernels.update({k: ctx.profile_get(k)["total_ms"] / args.profile_reps
                                         for k in ("product_first", "product_fold_sum", "product_round")})
                     ctx.profile(0)
+                    verify = verify_leg(ctx, d, n, n_tables, terms, batch, first, args, ceil)
+                    ok = ok and verify.pop("ok")
                 finally:
                     ctx.free(d)
                 failed += int(not ok)
@@ -118,6 +166,7 @@ def main():
                     row["product"] = p
                     row["sop_over_product"] = s["median_ms"] / p["median_ms"]
                     row["behind_by_iqrs"] = (s["median_ms"] - p["median_ms"]) / max(s["iqr_ms"], p["iqr_ms"], 1e-9)
+                row["verify"] = verify
                 result["shapes"].append(row)
     result["failed"] = failed
     line = json.dumps(result, sort_keys=True)
