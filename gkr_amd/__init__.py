@@ -7,11 +7,11 @@ reference's prover interface; it has no CPU fallback.
 
 from .field import MODULUS, from_limbs, to_limbs
 from .prover import (Context, GKRCircuit, GkrError, Layer, Proof, VerifyHandle, default_context, multi_hash, prove,
-                     prove_sumcheck, prove_sumcheck_opt, prove_sumcheck_product, prove_sumcheck_sop)
+                     prove_sumcheck, prove_sumcheck_opt, prove_sumcheck_product, prove_sumcheck_sop, prove_zerocheck)
 
-from .verifier import mle_eval, verify, verify_sumcheck_product, verify_sumcheck_sop, verify_sumcheck_table
+from .verifier import mle_eval, verify, verify_sumcheck_product, verify_sumcheck_sop, verify_sumcheck_table, verify_sumcheck_zerocheck
 from .aggregate import aggregated_input, circom_input, circom_meta
 
 __all__ = ["verify", "mle_eval", "verify_sumcheck_table", "aggregated_input", "circom_input", "circom_meta", "MODULUS", "from_limbs", "to_limbs", "Context", "GKRCircuit", "GkrError", "Layer", "Proof", "VerifyHandle",
            "default_context", "multi_hash", "prove", "prove_sumcheck", "prove_sumcheck_opt", "prove_sumcheck_product", "verify_sumcheck_product",
-           "prove_sumcheck_sop", "verify_sumcheck_sop"]
+           "prove_sumcheck_sop", "verify_sumcheck_sop", "prove_zerocheck", "verify_sumcheck_zerocheck"]

@@ -42,6 +42,7 @@ SYMBOLS = [
     "gkr_sumcheck_product_verify_batch_device", "gkr_sumcheck_product_verify",
     "gkr_sumcheck_sop_batch_device", "gkr_sumcheck_sop",
     "gkr_sumcheck_sop_verify_batch_device", "gkr_sumcheck_sop_verify",
+    "gkr_sumcheck_zerocheck_batch_device", "gkr_sumcheck_zerocheck", "gkr_eq_table_device",
     "gkr_mle_eval_batch_device", "gkr_sumcheck_mle_verify_batch_device", "gkr_sumcheck_mle_verify",
     "gkr_sumcheck_layer", "gkr_sumcheck_layer_sharded", "gkr_sumcheck_layer_device", "gkr_resident_layer_create", "gkr_resident_layer_sumcheck", "gkr_resident_layer_sumcheck_wdev", "gkr_resident_layer_free", "gkr_exchange_limbs", "gkr_resident_layer_sumcheck_dev", "gkr_exchange_limbs_mle", "gkr_sumcheck_mle_sharded_dev", "gkr_exchange_rccl_unique_id", "gkr_exchange_rccl_create", "gkr_exchange_rccl_dev",
     "gkr_exchange_rccl_calls", "gkr_exchange_rccl_destroy", "gkr_exchange_rccl_error", "gkr_fr_widen", "gkr_fr_narrow", "gkr_predicate_tables", "gkr_layer_eval", "gkr_proof_sizes", "gkr_prove", "gkr_prove_batch",
@@ -153,6 +154,14 @@ def lib():
         L.gkr_sumcheck_sop_verify_batch_device.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 9
         L.gkr_sumcheck_sop_verify.restype = ctypes.c_int
         L.gkr_sumcheck_sop_verify.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 7
+        # the zero-check: (ctx, tables, n, n_tables, terms, term_coeffs, n_terms[, batch], z, out_coeffs, out_len, out_r, out_evals, out_eq)
+        L.gkr_sumcheck_zerocheck_batch_device.restype = ctypes.c_int
+        L.gkr_sumcheck_zerocheck_batch_device.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 6
+        L.gkr_sumcheck_zerocheck.restype = ctypes.c_int
+        L.gkr_sumcheck_zerocheck.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 6
+        # the eq-table builder: (ctx, z, n, batch, d_out, stride_elements)
+        L.gkr_eq_table_device.restype = ctypes.c_int
+        L.gkr_eq_table_device.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p, ctypes.c_size_t]
         L.gkr_selftest_product_geometry.restype = ctypes.c_int
         L.gkr_selftest_product_geometry.argtypes = [ctypes.c_int] * 2 + [ctypes.c_void_p] * 2
         for fn in (L.gkr_r1cs_free, L.gkr_layered_free):

@@ -286,6 +286,32 @@ void launch_sop_round(const SopTerms& ts, const SopCoeffs& cf, const ProductPart
                       uint32_t batch, const Fr* cts, const Fr* work, size_t work_stride, Fr* out_coeffs, uint32_t* out_len, Fr* out_r,
                       FixedMul* rtab, Fr* evals, hipStream_t s);
 
+// ---- zero-check sumcheck (kernels_zerocheck.hip): eq(z, .) * sum_k c_k prod_j T_{t(k, j)}, term degrees <= 2, eq never a table ----
+// The weights of the variables still free, w_j(i) = E_hi,j[i >> 8] * E_lo[i & 255], as eq tables of launch_eq_table (Montgomery):
+// hi table m (m variables in front of the last eight) of all sumchecks at hi + batch * (2^m - 1), sumcheck b at + (b << m);
+// lo table k (the last k <= 8 variables) at lo + batch * (2^k - 1).  zc_weight_elements(n, batch) <= batch * (2^(n-8) + 511).
+struct ZcWeights {
+    Fr *hi, *lo;
+    uint32_t batch;
+    const Fr* hi_table(uint32_t m) const { return hi + (size_t)batch * ((1u << m) - 1u); }
+    const Fr* lo_table(uint32_t k) const { return lo + (size_t)batch * ((1u << k) - 1u); }
+};
+size_t zc_weight_elements(uint32_t n, uint32_t batch);
+ZcWeights zc_weights_layout(Fr* base, uint32_t n, uint32_t batch);
+// points: batch x n canonical elements in device (or pinned host) memory
+void launch_zc_weights(const Fr* points, uint32_t n, uint32_t batch, const ZcWeights& w, hipStream_t s);
+// as launch_sop_first / launch_sop_fold_sum; the round has 2^(kh + kl) entries per half table, kl = min(free variables, 8)
+void launch_zc_first(const SopTerms& ts, const Fr* tables, size_t table_stride, uint32_t h, uint32_t batch, uint32_t nblk, const ZcWeights& w,
+                     uint32_t kh, uint32_t kl, ProductPartial* partials, hipStream_t s);
+void launch_zc_fold_sum(const SopTerms& ts, const Fr* src, size_t src_stride, Fr* dst, size_t dst_stride, uint32_t q, uint32_t batch,
+                        uint32_t nblk, const FixedMul* rtab, uint32_t r_stride, const ZcWeights& w, uint32_t kh, uint32_t kl,
+                        ProductPartial* partials, hipStream_t s);
+// out_coeffs: batch x n rows of max_degree + 2 slots; z: batch x n canonical; s_slot: batch elements (s_j, Montgomery); evals
+// (batch x n_tables) and eq_out (batch: eq(z, r)) are written in round n - 1
+void launch_zc_round(const SopTerms& ts, const SopCoeffs& cf, const ProductPartial* partials, uint32_t nblk, uint32_t round, uint32_t n,
+                     uint32_t batch, const Fr* cts, const Fr* z, Fr* s_slot, const Fr* work, size_t work_stride, Fr* out_coeffs,
+                     uint32_t* out_len, Fr* out_r, FixedMul* rtab, Fr* evals, Fr* eq_out, hipStream_t s);
+
 void launch_layer_eval(uint32_t gates, const uint8_t* gate_type, const uint32_t* left, const uint32_t* right,
                        const Fr* prev, Fr* out, uint32_t batch, uint32_t prev_stride, hipStream_t s, const GateSet* sets = nullptr);
 // words 32-bit words src -> dst (16-byte aligned when words >= 4); either side may be pinned host memory

@@ -438,6 +438,76 @@ class Context:
                                              _ptr(L), _ptr(R), _ptr(E)))
         return [from_limbs(C[j])[D + 1 - int(L[j]):] for j in range(v)], from_limbs(R), from_limbs(E)
 
+    # -- the zero-check: sum_x eq(z, x) sum_k c_k prod_j T_t(k,j)(x), term degrees 1 and 2, eq(z, .) never a table
+    @staticmethod
+    def _points(z, batch, n):
+        """z as (batch, n, 4) limbs: such an array, or `batch` lists of n integers (reduced modulo r)."""
+        if isinstance(z, np.ndarray) and z.dtype == np.uint64:
+            pts = np.ascontiguousarray(z)
+        else:
+            pts = to_limbs([int(x) % MODULUS for row in z for x in row]).reshape(-1, n, 4) if len(z) else np.zeros((0, n, 4), dtype=np.uint64)
+        if pts.shape != (batch, n, 4):
+            raise GkrError(N.GKR_ERR_INVALID, "points of shape (batch, n, 4) expected")
+        return pts
+
+    def sumcheck_zerocheck_batch_device(self, d_tables, n, n_tables, terms, batch, z, out=None):
+        """gkr_sumcheck_zerocheck_batch_device: `batch` sumchecks of eq(z_b, .) * sum_k c_k prod_j T_t(k,j) over n_tables resident
+        tables of 2^n entries each (the layout of sumcheck_sop_batch_device; not modified), terms of 1 or 2 tables, z (batch, n, 4)
+        limbs or `batch` lists of n integers.  -> (C, L, R, E, Q): C (batch, n, D + 1, 4) right-aligned round vectors, D = the
+        largest term degree + 1; L (batch, n); R (batch, n, 4); E (batch, n_tables, 4) the tables' values at the challenges;
+        Q (batch, 4) eq(z_b, r_b).  The first four are byte for byte what sumcheck_sop_batch_device returns on the tables
+        {eq(z, .), T_0 ..} with every term prefixed by table 0.  out: the five arrays of an earlier call to write into."""
+        arr, coeffs, d = self._sop_terms(terms, n_tables)
+        if d > 2:
+            raise GkrError(N.GKR_ERR_INVALID, "a zero-check's terms are products of 1 or 2 tables")
+        pts = self._points(z, batch, n)
+        if out is not None:
+            C, L, R, E, Q = out
+            if (C.shape != (batch, n, d + 2, 4) or L.shape != (batch, n) or R.shape != (batch, n, 4) or E.shape != (batch, n_tables, 4)
+                    or Q.shape != (batch, 4)):
+                raise GkrError(N.GKR_ERR_INVALID, "output arrays do not match (batch, n, degree, n_tables)")
+        else:
+            C = np.zeros((batch, n, d + 2, 4), dtype=np.uint64)
+            L = np.zeros((batch, n), dtype=np.uint32)
+            R = np.zeros((batch, n, 4), dtype=np.uint64)
+            E = np.zeros((batch, n_tables, 4), dtype=np.uint64)
+            Q = np.zeros((batch, 4), dtype=np.uint64)
+        self._check(N.lib().gkr_sumcheck_zerocheck_batch_device(self._h, d_tables, n, n_tables, ctypes.cast(arr, ctypes.c_void_p), _ptr(coeffs),
+                                                                len(terms), batch, _ptr(pts), _ptr(C), _ptr(L), _ptr(R), _ptr(E), _ptr(Q)))
+        return C, L, R, E, Q
+
+    def prove_zerocheck(self, tables, terms, z, v):
+        """Sumcheck of sum_x eq(z, x) sum_k c_k prod_j tables[t(k,j)](x) over {0,1}^v: tables is a list of 1 .. 8 tables of 2^v
+        values, terms [(coeff, (table indices ..)), ..] with 1 or 2 indices each, z a point of v integers (0 and 1 allowed).
+        -> (proof, r, evals, eq_r): proof[j] the round vector (its used slots, highest degree first), r the challenges,
+        evals[m] = tables[m]~(r), eq_r = eq(z, r).  verifier.verify_sumcheck_zerocheck checks the transcript on plain integers."""
+        M = len(tables)
+        if not 1 <= M <= N.GKR_SOP_MAX_TABLES:
+            raise GkrError(N.GKR_ERR_INVALID, "1 .. %d tables expected" % N.GKR_SOP_MAX_TABLES)
+        arr, coeffs, d = self._sop_terms(terms, M)
+        if d > 2:
+            raise GkrError(N.GKR_ERR_INVALID, "a zero-check's terms are products of 1 or 2 tables")
+        limbs = np.concatenate([as_limbs(t) for t in tables], axis=0)
+        if limbs.shape[0] != M << v:
+            raise GkrError(N.GKR_ERR_INVALID, "every table must have 2^v values")
+        pts = self._points([z], 1, v)
+        C = np.zeros((v, d + 2, 4), dtype=np.uint64)
+        L = np.zeros(v, dtype=np.uint32)
+        R = np.zeros((v, 4), dtype=np.uint64)
+        E = np.zeros((M, 4), dtype=np.uint64)
+        Q = np.zeros((1, 4), dtype=np.uint64)
+        self._check(N.lib().gkr_sumcheck_zerocheck(self._h, _ptr(limbs), v, M, ctypes.cast(arr, ctypes.c_void_p), _ptr(coeffs), len(terms),
+                                                   _ptr(pts), _ptr(C), _ptr(L), _ptr(R), _ptr(E), _ptr(Q)))
+        return [from_limbs(C[j])[d + 2 - int(L[j]):] for j in range(v)], from_limbs(R), from_limbs(E), from_limbs(Q)[0]
+
+    def eq_table_device(self, z, n, batch, d_out, stride=None):
+        """gkr_eq_table_device: the canonical tables eq(z_b, .) of `batch` points (z: (batch, n, 4) limbs or `batch` lists of n
+        integers; variable 1 = the most significant index bit) written to device memory, table b at d_out + b * stride elements
+        (stride >= 2^n; None: one table after the other).  With stride = n_tables * 2^n the call fills table 0 of every
+        sumcheck of an SOP layout."""
+        pts = self._points(z, batch, n)
+        self._check(N.lib().gkr_eq_table_device(self._h, _ptr(pts), n, batch, d_out, (1 << n) if stride is None else int(stride)))
+
     # -- the plain sumcheck's verifier (verify_sumcheck, python/sumcheck.py:55-70, plus g_n(r_n) = T(r)) and the evaluation behind it
     def mle_eval_batch_device(self, d_tables, n, batch, points):
         """gkr_mle_eval_batch_device: the multilinear extension of each of `batch` resident tables of 2^n entries at its own point.
@@ -829,3 +899,7 @@ def prove_sumcheck_product(tables, v):
 
 def prove_sumcheck_sop(tables, terms, v):
     return default_context().prove_sumcheck_sop(tables, terms, v)
+
+
+def prove_zerocheck(tables, terms, z, v):
+    return default_context().prove_zerocheck(tables, terms, z, v)

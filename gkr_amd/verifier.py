@@ -148,6 +148,38 @@ def verify_sumcheck_sop(rounds: List[List[int]], challenges: List[int], evals: L
     return expected == total
 
 
+def verify_sumcheck_zerocheck(rounds: List[List[int]], challenges: List[int], evals: List[int], terms, z: List[int], claim=None) -> bool:
+    """The verifier of a zero-check's transcript (Context.prove_zerocheck) on plain integers.  terms: [(coeff, (table
+    indices ..)), ..] of 1 or 2 indices each as the prover took them; evals[m] the value of table m at the challenges; z the
+    point of eq(z, .).  Every round vector has 1 .. D + 1 coefficients (D = the largest term degree + 1), python/sumcheck.py:55-70
+    holds on the claim (the first round vector's own sum when none is given; a zero-check passes 0), and
+    g_n(r_n) == eq(z, r) * sum_k c_k prod_j evals[t(k,j)] with eq(z, r) = prod_j (z_j r_j + (1 - z_j)(1 - r_j)), n products.  That
+    evals[m] is table m's multilinear extension at the challenges is NOT checked here (Context.verify_sumcheck_sop_batch_device on
+    the tables and Context.eq_table_device's table checks it on the device)."""
+    if len(terms) < 1 or any(not 1 <= len(idx) <= 2 or any(not 0 <= i < len(evals) for i in idx) for _, idx in terms):
+        return False
+    degree = max(len(idx) for _, idx in terms) + 1
+    if len(rounds) < 1 or len(rounds) != len(challenges) or len(z) != len(rounds) or any(not 1 <= len(g) <= degree + 1 for g in rounds):
+        return False
+    expected = (eval_univariate(rounds[0], 0) + eval_univariate(rounds[0], 1) if claim is None else claim) % P
+    for g, r in zip(rounds, challenges):
+        if (eval_univariate(g, 0) + eval_univariate(g, 1)) % P != expected:
+            return False
+        if multi_hash(g, 0) != r % P:
+            return False
+        expected = eval_univariate(g, r)
+    total = 0
+    for c, idx in terms:
+        prod = c % P
+        for i in idx:
+            prod = prod * evals[i] % P
+        total = (total + prod) % P
+    eq_r = 1
+    for zj, rj in zip(z, challenges):
+        eq_r = eq_r * (zj * rj + (1 - zj) * (1 - rj)) % P
+    return expected == eq_r * total % P
+
+
 def verify(proof: Proof, circuit: GKRCircuit) -> bool:
     """python/gkr.py:202-231 on the Rust-shaped proof."""
     L = circuit.depth()

@@ -359,6 +359,54 @@ int  gkr_sumcheck_sop(gkr_ctx *ctx, const gkr_fr *tables /* host, n_tables x 2^n
                       const gkr_fr *term_coeffs, int n_terms,
                       gkr_fr *out_coeffs, uint32_t *out_len, gkr_fr *out_r, gkr_fr *out_evals);
 
+/* ZERO-CHECK: `batch` sumchecks of  sum_x eq(z, x) g(x),  g = sum_k c_k prod_{f < d_k} T_{t(k,f)}  with term degrees d_k in
+ * {1, 2} -- the R1CS zero-check eq (A B - C), a dense GKR layer, every "this relation holds on the whole cube" claim -- without
+ * eq(z, .) as a table: nothing of 2^n entries is built, uploaded, folded or multiplied in.  Tables, terms and coefficients as
+ * gkr_sumcheck_sop_batch_device takes them; z: batch x n canonical elements in host memory, each sumcheck its own point,
+ * variable 1 = the most significant index bit.  Entries 0 and 1 are ordinary points (nothing divides by z_j or 1 - z_j).
+ * d = the largest term degree, D = d + 1.  Round j = 1 .. n, on the current (folded) tables of 2^(n-j+1) entries, lo_f = T_f[i],
+ * hi_f = T_f[i + 2^(n-j)], i < 2^(n-j):
+ *     w_j(i) = eq((z_{j+1}, .., z_n), i)                              z_{j+1} against i's top bit; w_n = 1
+ *     h_j(X) = sum_i w_j(i) sum_k c_k prod_f (lo_f + X (hi_f - lo_f))                                  degree d
+ *     s_j    = prod_{l < j} (z_l r_l + (1 - z_l)(1 - r_l)),  s_1 = 1
+ *     g_j(X) = s_j ((1 - z_j) + (2 z_j - 1) X) h_j(X)                                                   degree D
+ *   out_coeffs  batch x n rows of D + 1 slots: the coefficients of g_j, right-aligned, highest degree first, unused slots zero
+ *   out_len     batch x n values in 1 .. D + 1; EVERY round: leading zero coefficients dropped, one kept at least
+ *   out_r       batch x n challenges, r_j = multi_hash(used slots of round j, key 0); every table folds once with r_j
+ *   out_evals   batch x n_tables values T_m~(r_1 .. r_n), or NULL
+ *   out_eq      batch values s_{n+1} = eq(z, r), or NULL
+ * A verifier's last check is  g_n(r_n) = out_eq * sum_k c_k prod_f out_evals[t(k,f)];  a zero-check's claim is zero.
+ * g_j is the polynomial gkr_sumcheck_sop_batch_device forms from the n_tables + 1 tables {eq(z, .), T_0 ..} with every term
+ * prefixed by table 0, coefficients are canonical and the length rule goes by value: the two transcripts (coefficients, lengths,
+ * challenges, the tables' values; out_eq = that call's value of table 0) are EQUAL BYTE FOR BYTE, for every input -- g
+ * identically zero (every vector [0]) and boolean z included.  gkr_sumcheck_sop_verify_batch_device on those tables (table 0
+ * from gkr_eq_table_device) therefore verifies this call's transcripts.
+ * Inputs are not modified; the folded halves (batch * n_tables * 2^(n-1) elements) and the weights of the free variables
+ * (2^(n-8) + 511 elements per sumcheck) live in context workspace under slot names of this path's own: a plain, product or SOP
+ * call on the same context is unaffected.
+ * GKR_ERR_INVALID before a device or the context is touched (plain returns): everything gkr_sumcheck_sop_batch_device refuses
+ * (the same table and batch limits), NULL z, and A TERM OF DEGREE 3: inner degree 3 makes g_j a quartic, which needs rows of five
+ * slots and a fifth hash slot.  GKR_ERR_NON_CANONICAL (through the context) for a coefficient or a z entry >= r. */
+int  gkr_sumcheck_zerocheck_batch_device(gkr_ctx *ctx, const void *d_tables, int n, int n_tables, const gkr_sop_term *terms,
+                                         const gkr_fr *term_coeffs /* n_terms, NULL = all 1 */, int n_terms, int batch,
+                                         const gkr_fr *z /* host, batch x n */,
+                                         gkr_fr *out_coeffs, uint32_t *out_len, gkr_fr *out_r,
+                                         gkr_fr *out_evals /* batch x n_tables or NULL */, gkr_fr *out_eq /* batch or NULL */);
+
+/* `n_tables` tables of 2^n values in host memory, one after the other, and one point z of n elements: upload + the call above
+ * with batch 1.  GKR_ERR_NON_CANONICAL also for a table entry >= r. */
+int  gkr_sumcheck_zerocheck(gkr_ctx *ctx, const gkr_fr *tables /* host, n_tables x 2^n */, int n, int n_tables, const gkr_sop_term *terms,
+                            const gkr_fr *term_coeffs, int n_terms, const gkr_fr *z /* n */,
+                            gkr_fr *out_coeffs, uint32_t *out_len, gkr_fr *out_r, gkr_fr *out_evals, gkr_fr *out_eq);
+
+/* The tables eq(z_b, .) of `batch` points, built on the device: d_out[b * stride_elements + i] = prod_j (bit_j(i) ? z_j : 1 - z_j),
+ * canonical, variable 1 = the most significant index bit of i < 2^n.  z: batch x n canonical elements in host memory.  With
+ * stride_elements = n_tables * 2^n the call fills table 0 of every sumcheck's group of an SOP layout in place; elements between
+ * the tables are not touched.  GKR_ERR_INVALID (plain returns): NULL pointer, n outside 1 .. GKR_MAX_MLE_N, batch outside
+ * 1 .. 65535, stride_elements < 2^n.  GKR_ERR_NON_CANONICAL (through the context) for a z entry >= r. */
+int  gkr_eq_table_device(gkr_ctx *ctx, const gkr_fr *z /* host, batch x n */, int n, int batch,
+                         void *d_out, size_t stride_elements /* >= 2^n */);
+
 /* Verifier of gkr_sumcheck_product_batch_device's transcripts: the plain sumcheck's verifier (below; the same driver, the same
  * options) for round polynomials of degree up to 3, one read of every factor.
  * d_tables / coeffs / len / r: exactly the arrays and layout of the prover (factor f of sumcheck b at (b * degree + f) * 2^n
