@@ -25,6 +25,9 @@ GKR_ERR_UNSUPPORTED = 7
 GKR_VERIFY_OK, GKR_VERIFY_SHAPE, GKR_VERIFY_NON_CANONICAL = 0, 1, 2
 GKR_VERIFY_ROUND_SUM, GKR_VERIFY_CHALLENGE, GKR_VERIFY_EVALUATION = 4, 5, 10
 
+# rows of an R1CS matrix with more terms than this get a wave each on the device (GKR_R1CS_LONG_ROW)
+GKR_R1CS_LONG_ROW = 32
+
 # limits of the sumcheck over a sum of products (gkr_sumcheck_sop*)
 GKR_SOP_MAX_TABLES = 8
 GKR_SOP_MAX_TERMS = 8
@@ -50,6 +53,8 @@ SYMBOLS = [
     "gkr_verify_prepare", "gkr_verify_prepared", "gkr_verify_circuit_free", "gkr_verify_device", "gkr_mimc7_multi_hash_device",
     "gkr_circom_meta", "gkr_circom_input_json", "gkr_circom_verifier_source", "gkr_circom_inject",
     "gkr_r1cs_parse", "gkr_r1cs_build", "gkr_r1cs_info", "gkr_r1cs_export", "gkr_r1cs_serialize", "gkr_r1cs_free",
+    "gkr_r1cs_csr_info", "gkr_r1cs_csr_export", "gkr_r1cs_rows_prepare", "gkr_r1cs_rows_info", "gkr_r1cs_rows_free", "gkr_r1cs_rows_device",
+    "gkr_r1cs_zerocheck_batch_device", "gkr_r1cs_zerocheck",
     "gkr_wtns_parse", "gkr_wtns_serialize", "gkr_r1cs_compile", "gkr_layered_count", "gkr_layered_circuit",
     "gkr_layered_input_layer", "gkr_layered_input_values", "gkr_layered_free",
     "gkr_device_alloc", "gkr_device_free", "gkr_device_upload", "gkr_device_download",
@@ -92,6 +97,16 @@ class R1csInfo(ctypes.Structure):
     _fields_ = [("n_wires", ctypes.c_uint32), ("n_pub_out", ctypes.c_uint32), ("n_pub_in", ctypes.c_uint32),
                 ("n_prv_in", ctypes.c_uint32), ("n_labels", ctypes.c_uint64), ("n_constraints", ctypes.c_size_t),
                 ("n_terms", ctypes.c_size_t)]
+
+
+class R1csCsrInfo(ctypes.Structure):
+    """gkr_r1cs_csr_info_t: the CSR form's sizes; tables of 2^n entries."""
+    _fields_ = [("n", ctypes.c_uint32), ("n_wires", ctypes.c_uint32), ("n_constraints", ctypes.c_size_t),
+                ("n_terms", ctypes.c_size_t * 3), ("n_long_rows", ctypes.c_size_t * 3), ("n_pool", ctypes.c_size_t)]
+
+    def as_dict(self):
+        return dict(n=int(self.n), n_wires=int(self.n_wires), n_constraints=int(self.n_constraints), n_terms=[int(x) for x in self.n_terms],
+                    n_long_rows=[int(x) for x in self.n_long_rows], n_pool=int(self.n_pool))
 
 
 class SopTerm(ctypes.Structure):
@@ -162,6 +177,26 @@ def lib():
         # the eq-table builder: (ctx, z, n, batch, d_out, stride_elements)
         L.gkr_eq_table_device.restype = ctypes.c_int
         L.gkr_eq_table_device.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p, ctypes.c_size_t]
+        # the R1CS zero-check: the CSR form (host only), the resident handle, the rows, the zero-check on them
+        L.gkr_r1cs_csr_info.restype = ctypes.c_int
+        L.gkr_r1cs_csr_info.argtypes = [ctypes.c_void_p] * 2
+        L.gkr_r1cs_csr_export.restype = ctypes.c_int
+        L.gkr_r1cs_csr_export.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4
+        L.gkr_r1cs_rows_prepare.restype = ctypes.c_int
+        L.gkr_r1cs_rows_prepare.argtypes = [ctypes.c_void_p] * 3
+        L.gkr_r1cs_rows_info.restype = ctypes.c_int
+        L.gkr_r1cs_rows_info.argtypes = [ctypes.c_void_p] * 2
+        L.gkr_r1cs_rows_free.restype = None
+        L.gkr_r1cs_rows_free.argtypes = [ctypes.c_void_p]
+        # (ctx, rows, d_witness, stride_elements, batch, d_out, out_first_bad)
+        L.gkr_r1cs_rows_device.restype = ctypes.c_int
+        L.gkr_r1cs_rows_device.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_size_t, ctypes.c_int] + [ctypes.c_void_p] * 2
+        # (ctx, rows, d_witness, stride_elements, batch, z, out_coeffs, out_len, out_r, out_evals, out_eq, out_first_bad)
+        L.gkr_r1cs_zerocheck_batch_device.restype = ctypes.c_int
+        L.gkr_r1cs_zerocheck_batch_device.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_size_t, ctypes.c_int] + [ctypes.c_void_p] * 7
+        # (ctx, r1cs, witness, n_witness, z, out_coeffs, out_len, out_r, out_evals, out_eq, out_first_bad)
+        L.gkr_r1cs_zerocheck.restype = ctypes.c_int
+        L.gkr_r1cs_zerocheck.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_size_t] + [ctypes.c_void_p] * 7
         L.gkr_selftest_product_geometry.restype = ctypes.c_int
         L.gkr_selftest_product_geometry.argtypes = [ctypes.c_int] * 2 + [ctypes.c_void_p] * 2
         for fn in (L.gkr_r1cs_free, L.gkr_layered_free):

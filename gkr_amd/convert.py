@@ -93,6 +93,28 @@ class R1cs:
             out.append(tuple(con))
         return out
 
+    def csr_info(self):
+        """gkr_r1cs_csr_info: the sizes of the CSR form the device's row kernels read -- n (tables of 2^n entries), n_wires,
+        n_constraints, n_terms / n_long_rows per matrix (A, B, C), n_pool."""
+        out = N.R1csCsrInfo()
+        _check(N.lib().gkr_r1cs_csr_info(self._h, ctypes.byref(out)), "gkr_r1cs_csr_info")
+        return out.as_dict()
+
+    def csr(self, matrix):
+        """gkr_r1cs_csr_export: matrix 0 / 1 / 2 = A / B / C -> (row_ptr (n_constraints + 1,) uint32, terms (n_terms, 2) uint32 rows
+        of (wire, pool index), long_rows uint32 (the rows with more than GKR_R1CS_LONG_ROW terms, ascending), pool: the distinct
+        coefficients as integers, pool[0] = 1, pool[1] = r - 1, shared by the three matrices)."""
+        if matrix not in (0, 1, 2):
+            raise GkrError(N.GKR_ERR_INVALID, "matrix 0, 1 or 2 expected")
+        inf = self.csr_info()
+        row_ptr = np.zeros(inf["n_constraints"] + 1, dtype=np.uint32)
+        terms = np.zeros((inf["n_terms"][matrix], 2), dtype=np.uint32)
+        long_rows = np.zeros(inf["n_long_rows"][matrix], dtype=np.uint32)
+        pool = np.zeros((inf["n_pool"], 4), dtype=np.uint64)
+        _check(N.lib().gkr_r1cs_csr_export(self._h, matrix, _ptr(row_ptr), _ptr(terms) if len(terms) else None,
+                                           _ptr(long_rows) if len(long_rows) else None, _ptr(pool)), "gkr_r1cs_csr_export")
+        return row_ptr, terms, long_rows, from_limbs(pool)
+
     def serialize(self) -> bytes:
         need = ctypes.c_size_t()
         _check(N.lib().gkr_r1cs_serialize(self._h, None, ctypes.c_size_t(0), ctypes.byref(need)), "gkr_r1cs_serialize")

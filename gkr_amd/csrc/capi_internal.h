@@ -2,7 +2,7 @@
 // memory; capi_mle.hip: the plain sumcheck's entry points, per-round schedules and sessions; capi_mle_passes.hip: its multi-round
 // schedule, whole tables and tables split over ranks; capi_layer.hip: the layer sumcheck over gate lists; capi_layer_dense.hip:
 // its dense form; capi_prove.hip: whole proofs; capi_product.hip: the sumcheck over a product of resident tables; capi_sop.hip: over a sum of
-// such products): the context,
+// such products; capi_zerocheck.hip: the zero-check; capi_r1cs.hip: an R1CS's tables in front of it): the context,
 // its caches and workspaces, profiling brackets, the host transcript's helpers, the hand-off wait, the plain sumcheck's group
 // hand-off.  Not a public header.
 #pragma once
@@ -757,6 +757,11 @@ uint32_t product_round_blocks(int n, int batch, int round);
 // coefficients in the kernels' form (NULL: all one), false: one is >= r
 bool sop_shape(int n, int n_tables, const gkr_sop_term* terms, int n_terms, int batch, gkr::SopTerms* ts);
 bool sop_coeffs(const gkr_fr* term_coeffs, int n_terms, gkr::SopCoeffs* cf);
+// ---- defined in capi_zerocheck.hip
+// `batch` zero-checks eq(z_b, .) * (the terms) on resident tables, the whole of gkr_sumcheck_zerocheck_batch_device behind its
+// argument checks: everything already queued on the context's stream is waited for, the outputs are in the caller's arrays
+int run_zerocheck_batch(gkr_ctx* ctx, const Fr* d_tables, int n, const gkr::SopTerms& ts, const gkr::SopCoeffs& cf, int batch,
+                        const gkr_fr* z, gkr_fr* out_coeffs, uint32_t* out_len, gkr_fr* out_r, gkr_fr* out_evals, gkr_fr* out_eq);
 // ---- defined in capi_prove.hip
 void mobius_msb(std::vector<gkr::h64::F>& c, int k);
 void line_restriction(const std::vector<gkr::h64::F>& vals, const std::vector<gkr::h64::F>& coeffs, int k, const gkr_fr* b, const gkr_fr* c,

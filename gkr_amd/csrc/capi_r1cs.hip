@@ -1,0 +1,192 @@
+// The R1CS zero-check: the CSR form of an R1CS (r1cs.cpp) resident on a context's device, the tables Az, Bz, Cz of a batch of
+// resident witnesses (kernels_r1cs.hip), the row check a * b == c, and the zero-check eq(z, .) (A B - C) on those tables
+// (run_zerocheck_batch, capi_zerocheck.hip).  C ABI: include/gkr_amd.h.
+#include "capi_internal.h"
+
+static_assert(sizeof(gkr_r1cs_term) == sizeof(uint2), "a record is eight bytes: {wire, pool index}");
+static_assert(gkr::kR1csLongRow == GKR_R1CS_LONG_ROW, "the kernels and the host's long-row lists cut at the same length");
+
+struct gkr_r1cs_rows {
+    gkr_ctx* ctx = nullptr;
+    gkr_r1cs_csr_info_t info{};
+    uint32_t* row_ptr[3] = {nullptr, nullptr, nullptr};
+    uint2* terms[3] = {nullptr, nullptr, nullptr};
+    uint32_t* long_rows[3] = {nullptr, nullptr, nullptr};
+    Fr* pool_mont = nullptr;
+    size_t terms_total = 0;
+    void release() {
+        for (int m = 0; m < 3; ++m) {
+            if (row_ptr[m]) (void)hipFree(row_ptr[m]);
+            if (terms[m]) (void)hipFree(terms[m]);
+            if (long_rows[m]) (void)hipFree(long_rows[m]);
+        }
+        if (pool_mont) (void)hipFree(pool_mont);
+    }
+    gkr::R1csCsr csr() const {
+        gkr::R1csCsr c;
+        for (int m = 0; m < 3; ++m) {
+            c.row_ptr[m] = row_ptr[m];
+            c.terms[m] = terms[m];
+            c.long_rows[m] = long_rows[m];
+            c.n_long[m] = (uint32_t)info.n_long_rows[m];
+        }
+        c.pool_mont = pool_mont;
+        c.n_constraints = (uint32_t)info.n_constraints;
+        c.n = info.n;
+        return c;
+    }
+};
+
+namespace gkr_host {
+
+// the argument checks of the two resident entry points (plain returns: decided before the context is looked at)
+static bool r1cs_rows_args(const gkr_ctx* ctx, const gkr_r1cs_rows* rows, const void* d_witness, size_t stride_elements, int batch) {
+    if (!ctx || !rows || !d_witness) return false;
+    if (batch < 1 || batch > 65535) return false;
+    if (rows->ctx != ctx) return false;
+    if (stride_elements < rows->info.n_wires) return false;
+    if ((((unsigned long long)batch * 3ull) << rows->info.n) > (1ull << 30)) return false;   // batch * 3 * 2^n values
+    return true;
+}
+
+template <typename T>
+static hipError_t upload_new(T** d, const T* h, size_t count) {
+    hipError_t rc = hipMalloc(reinterpret_cast<void**>(d), std::max<size_t>(count, 1) * sizeof(T));
+    if (rc == hipSuccess && count) rc = hipMemcpy(*d, h, count * sizeof(T), hipMemcpyHostToDevice);
+    return rc;
+}
+
+static int upload_rows(gkr_ctx* ctx, const gkr_r1cs* r1cs, gkr_r1cs_rows* rows) {
+    const gkr_r1cs_csr_info_t& info = rows->info;
+    std::vector<uint32_t> row_ptr(info.n_constraints + 1), long_rows;
+    std::vector<gkr_r1cs_term> terms;
+    std::vector<gkr_fr> pool(info.n_pool);
+    for (int m = 0; m < 3; ++m) {
+        terms.resize(info.n_terms[m]);
+        long_rows.resize(info.n_long_rows[m]);
+        if (const int rc = gkr_r1cs_csr_export(r1cs, m, row_ptr.data(), terms.data(), long_rows.data(), m == 0 ? pool.data() : nullptr))
+            return ctx->fail(rc, "gkr_r1cs_csr_export");
+        HIP_TRY(ctx, upload_new(&rows->row_ptr[m], row_ptr.data(), row_ptr.size()));
+        HIP_TRY(ctx, upload_new(&rows->terms[m], reinterpret_cast<const uint2*>(terms.data()), terms.size()));
+        HIP_TRY(ctx, upload_new(&rows->long_rows[m], long_rows.data(), long_rows.size()));
+        rows->terms_total += terms.size();
+    }
+    std::vector<Fr> pool_mont(pool.size());
+    for (size_t i = 0; i < pool.size(); ++i) pool_mont[i] = gkr::to_mont(to_dev(pool[i]));   // canonical witness x Montgomery coefficient
+    HIP_TRY(ctx, upload_new(&rows->pool_mont, pool_mont.data(), pool_mont.size()));
+    return GKR_OK;
+}
+
+// The tables of `batch` witnesses into d_out and, with out_first_bad, the row check; everything queued on the context's stream,
+// the caller synchronises.  Workspace slots are this path's own ("r1cs.*").
+static int run_r1cs_rows(gkr_ctx* ctx, const gkr_r1cs_rows* rows, const Fr* d_witness, size_t stride, int batch, Fr* d_out,
+                         uint32_t* out_first_bad) {
+    hipStream_t s = ctx->stream;
+    const double len = (double)((size_t)1 << rows->info.n);
+    {
+        Timed t(ctx, "r1cs_rows", (double)batch * (8.0 * rows->terms_total + 32.0 * rows->terms_total + 32.0 * 3.0 * len));
+        gkr::launch_r1cs_rows(rows->csr(), d_witness, stride, (uint32_t)batch, d_out, s);
+    }
+    if (out_first_bad) {
+        uint32_t* d_bad = nullptr;
+        WS(ctx, "r1cs.first_bad", uint32_t, batch, d_bad);
+        {
+            Timed t(ctx, "r1cs_check", (double)batch * 3.0 * 32.0 * (double)rows->info.n_constraints);
+            HIP_TRY(ctx, gkr::launch_r1cs_check(d_out, rows->info.n, (uint32_t)rows->info.n_constraints, (uint32_t)batch, d_bad, s));
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(out_first_bad, d_bad, (size_t)batch * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return GKR_OK;
+}
+
+// eq(z, .) (A B - C) on the tables of `batch` resident witnesses: terms {2, {0, 1}} coefficient 1 and {1, {2}} coefficient r - 1
+static int run_r1cs_zerocheck(gkr_ctx* ctx, const gkr_r1cs_rows* rows, const Fr* d_witness, size_t stride, int batch, const gkr_fr* z,
+                              gkr_fr* out_coeffs, uint32_t* out_len, gkr_fr* out_r, gkr_fr* out_evals, gkr_fr* out_eq,
+                              uint32_t* out_first_bad) {
+    const int n = (int)rows->info.n;
+    const gkr_sop_term terms[2] = {{2, {0, 1, 0}}, {1, {2, 0, 0}}};
+    gkr_fr coeffs[2] = {{{1, 0, 0, 0}}, {{0, 0, 0, 0}}};
+    memcpy(&coeffs[1], gkr::h64::kMod, 32);
+    coeffs[1].l[0] -= 1;   // r - 1 (r is odd: no borrow)
+    gkr::SopTerms ts;
+    gkr::SopCoeffs cf;
+    if (!sop_shape(n, 3, terms, 2, batch, &ts) || !sop_coeffs(coeffs, 2, &cf)) return ctx->fail(GKR_ERR_INVALID, "R1CS zero-check shape");
+    Fr* d_tables = nullptr;
+    WS(ctx, "r1cs.tables", Fr, ((size_t)batch * 3) << n, d_tables);
+    if (const int rc = run_r1cs_rows(ctx, rows, d_witness, stride, batch, d_tables, out_first_bad)) return rc;
+    return run_zerocheck_batch(ctx, d_tables, n, ts, cf, batch, z, out_coeffs, out_len, out_r, out_evals, out_eq);
+}
+
+}  // namespace gkr_host
+
+// =========================================================================== C ABI
+
+extern "C" {
+
+int gkr_r1cs_rows_prepare(gkr_ctx* ctx, const gkr_r1cs* r1cs, gkr_r1cs_rows** out) {
+    if (!ctx || !r1cs || !out) return GKR_ERR_INVALID;
+    *out = nullptr;
+    std::unique_ptr<gkr_r1cs_rows, void (*)(gkr_r1cs_rows*)> rows(new gkr_r1cs_rows(), gkr_r1cs_rows_free);
+    if (const int rc = gkr_r1cs_csr_info(r1cs, &rows->info)) return rc;
+    rows->ctx = ctx;
+    GKR_ENTER(ctx);
+    if (const int rc = upload_rows(ctx, r1cs, rows.get())) return rc;
+    *out = rows.release();
+    return GKR_OK;
+}
+
+int gkr_r1cs_rows_info(const gkr_r1cs_rows* rows, gkr_r1cs_csr_info_t* out) {
+    if (!rows || !out) return GKR_ERR_INVALID;
+    *out = rows->info;
+    return GKR_OK;
+}
+
+void gkr_r1cs_rows_free(gkr_r1cs_rows* rows) {
+    if (!rows) return;
+    if (rows->ctx) (void)hipSetDevice(rows->ctx->device);
+    rows->release();
+    delete rows;
+}
+
+int gkr_r1cs_rows_device(gkr_ctx* ctx, const gkr_r1cs_rows* rows, const void* d_witness, size_t stride_elements, int batch, void* d_out,
+                         uint32_t* out_first_bad) {
+    if (!r1cs_rows_args(ctx, rows, d_witness, stride_elements, batch) || !d_out) return GKR_ERR_INVALID;
+    GKR_ENTER(ctx);
+    if (const int rc = run_r1cs_rows(ctx, rows, static_cast<const Fr*>(d_witness), stride_elements, batch, static_cast<Fr*>(d_out), out_first_bad))
+        return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->drain_events();
+    return GKR_OK;
+}
+
+int gkr_r1cs_zerocheck_batch_device(gkr_ctx* ctx, const gkr_r1cs_rows* rows, const void* d_witness, size_t stride_elements, int batch,
+                                    const gkr_fr* z, gkr_fr* out_coeffs, uint32_t* out_len, gkr_fr* out_r, gkr_fr* out_evals, gkr_fr* out_eq,
+                                    uint32_t* out_first_bad) {
+    if (!r1cs_rows_args(ctx, rows, d_witness, stride_elements, batch) || !z || !out_coeffs || !out_len || !out_r) return GKR_ERR_INVALID;
+    if (!all_canonical(z, (size_t)batch * rows->info.n)) return ctx->fail(GKR_ERR_NON_CANONICAL, "z entry >= r");
+    GKR_ENTER(ctx);
+    return run_r1cs_zerocheck(ctx, rows, static_cast<const Fr*>(d_witness), stride_elements, batch, z, out_coeffs, out_len, out_r, out_evals,
+                              out_eq, out_first_bad);
+}
+
+int gkr_r1cs_zerocheck(gkr_ctx* ctx, const gkr_r1cs* r1cs, const gkr_fr* witness, size_t n_witness, const gkr_fr* z, gkr_fr* out_coeffs,
+                       uint32_t* out_len, gkr_fr* out_r, gkr_fr* out_evals, gkr_fr* out_eq, uint32_t* out_first_bad) {
+    if (!ctx || !r1cs || !witness || !z || !out_coeffs || !out_len || !out_r) return GKR_ERR_INVALID;
+    gkr_r1cs_csr_info_t info;
+    if (const int rc = gkr_r1cs_csr_info(r1cs, &info)) return rc;
+    if (n_witness < info.n_wires) return GKR_ERR_INVALID;
+    if ((3ull << info.n) > (1ull << 30)) return GKR_ERR_INVALID;   // 3 * 2^n values: the cap of the resident call at batch 1
+    if (!all_canonical(z, (size_t)info.n)) return ctx->fail(GKR_ERR_NON_CANONICAL, "z entry >= r");
+    if (!all_canonical(witness, n_witness)) return ctx->fail(GKR_ERR_NON_CANONICAL, "witness entry >= r");
+    gkr_r1cs_rows* raw = nullptr;
+    if (const int rc = gkr_r1cs_rows_prepare(ctx, r1cs, &raw)) return rc;
+    std::unique_ptr<gkr_r1cs_rows, void (*)(gkr_r1cs_rows*)> rows(raw, gkr_r1cs_rows_free);
+    GKR_ENTER(ctx);
+    DevBuf<Fr> d;
+    HIP_TRY(ctx, d.alloc(info.n_wires));
+    HIP_TRY(ctx, hipMemcpyAsync(d.p, witness, (size_t)info.n_wires * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+    return run_r1cs_zerocheck(ctx, rows.get(), d.p, info.n_wires, 1, z, out_coeffs, out_len, out_r, out_evals, out_eq, out_first_bad);
+}
+
+}  // extern "C"

@@ -8,8 +8,9 @@
 namespace gkr_host {
 
 // Workspace slots are this path's own ("zc.*"): a call may follow or precede a plain, a product or an SOP sumcheck on the same context.
-static int run_zerocheck_batch(gkr_ctx* ctx, const Fr* d_tables, int n, const gkr::SopTerms& ts, const gkr::SopCoeffs& cf, int batch,
-                               const gkr_fr* z, gkr_fr* out_coeffs, uint32_t* out_len, gkr_fr* out_r, gkr_fr* out_evals, gkr_fr* out_eq) {
+// (Also the second half of the R1CS zero-check, capi_r1cs.hip.)
+int run_zerocheck_batch(gkr_ctx* ctx, const Fr* d_tables, int n, const gkr::SopTerms& ts, const gkr::SopCoeffs& cf, int batch,
+                        const gkr_fr* z, gkr_fr* out_coeffs, uint32_t* out_len, gkr_fr* out_r, gkr_fr* out_evals, gkr_fr* out_eq) {
     const size_t len = (size_t)1 << n, rounds = (size_t)batch * n, tables = (size_t)batch * ts.n_tables, slots = (size_t)ts.max_degree + 2;
     hipStream_t s = ctx->stream;
     Fr *work = nullptr, *d_coeffs = nullptr, *d_r = nullptr, *d_evals = nullptr, *d_z = nullptr, *d_s = nullptr, *d_eq = nullptr, *d_w = nullptr;

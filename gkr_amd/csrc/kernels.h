@@ -480,6 +480,25 @@ size_t mle_eval_ws_bytes(uint32_t n, uint32_t groups, uint32_t G);   // device w
 // every value is bit for bit the one G = 1 gives with the point repeated.  ws: mle_eval_ws_bytes().
 void launch_mle_eval(const Fr* tables, uint32_t n, uint32_t groups, uint32_t G, const Fr* points, void* ws, Fr* out, hipStream_t s);
 
+// ---- the R1CS zero-check's tables (kernels_r1cs.hip) -------------------------------------------------------------------------------
+// The three matrices of an R1CS in CSR form, resident: matrix m's n_constraints + 1 row offsets, its records {x: wire, y: pool
+// index}, the ascending list of its rows with more than kR1csLongRow records; the coefficient pool in Montgomery form (entries
+// 0 and 1, one and r - 1, are never read).  Tables of 2^n entries.
+constexpr uint32_t kR1csLongRow = 32;   // (= GKR_R1CS_LONG_ROW: the host's long-row lists are cut at the same length)
+struct R1csCsr {
+    const uint32_t* row_ptr[3];
+    const uint2* terms[3];
+    const uint32_t* long_rows[3];
+    uint32_t n_long[3];
+    const Fr* pool_mont;
+    uint32_t n_constraints, n;
+};
+// out[(b * 3 + m) * 2^n + i] = row i of matrix m times witness b (witness + b * witness_stride elements, canonical), canonical;
+// rows >= n_constraints zero.  One launch over all rows, one more over the long rows where a matrix has any.
+void launch_r1cs_rows(const R1csCsr& csr, const Fr* witness, size_t witness_stride, uint32_t batch, Fr* out, hipStream_t s);
+// first_bad[b] = the lowest row < n_constraints of sumcheck b's tables (a, b, c at (b * 3 + m) * 2^n) with a * b != c, UINT32_MAX if none
+hipError_t launch_r1cs_check(const Fr* tables, uint32_t n, uint32_t n_constraints, uint32_t batch, uint32_t* first_bad, hipStream_t s);
+
 uint32_t layer_blocks(uint32_t h);
 void launch_layer_round(const Fr* A, const Fr* M, uint32_t h, uint32_t k, uint32_t phase, uint32_t hb, const Fr* Wb,
                         const Fr* Wc, uint32_t nblk, LayerPartial* partials, LayerBatch lb, hipStream_t s);

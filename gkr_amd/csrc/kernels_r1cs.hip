@@ -1,0 +1,145 @@
+// CDNA4 (gfx950) kernels of the R1CS zero-check's tables (gkr_r1cs_rows_device): Az, Bz, Cz of a witness as sparse matrix-vector
+// products over BN254 Fr, and the row-wise check a * b == c.
+//
+//   out[(b * 3 + m) * 2^n + i] = sum_t pool[coeff_t] * w_b[wire_t]   over the records of row i of matrix m, canonical;
+//   rows >= n_constraints are zero.
+//
+// The matrices are CSR (r1cs.cpp): 32-bit row offsets, 8-byte records {wire, pool index}, one pool of distinct coefficients in
+// MONTGOMERY form.  A witness entry is canonical; canonical x Montgomery summed unreduced in a Lazy17 and reduced once
+// (lazy_reduce takes a factor 2^-256) is the canonical sum.  Pool entries 0 (one) and 1 (r - 1) take no product: w, or r - w,
+// joins the sum as w * 2^256 (lazy_add_hi), nine additions.
+// Term bounds: a term is a product of two values below r < 2^254, below 2^508, or w * 2^256 < 2^510 (about 5.3 r^2); a row has
+// fewer than 2^32 terms (the offsets are 32 bits wide), so a row's sum stays below 2^542 < 2^544: NO row needs an intermediate
+// reduction of its Lazy17, in either kernel.
+//
+// The witness gather is 32 bytes out of a 128-byte line per term, the pattern of the wide gate passes (DESIGN.md section 3
+// prices it at 3.8x the algorithmic bytes); the records and the row offsets stream.
+// Every element offset (witness, tables) is 64 bits wide; 32-bit values index rows (< 2^30) and records (< 2^32) only.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "kernels.h"
+#include "dev_util.h"
+
+namespace gkr {
+
+namespace {
+
+// matrix m's arrays picked with selects (m is wave-uniform: scalar selects, no indexed copy of the argument struct in memory)
+template <typename T>
+__device__ __forceinline__ T pick3(const T (&a)[3], uint32_t m) {
+    return m == 0 ? a[0] : (m == 1 ? a[1] : a[2]);
+}
+
+// One record's contribution.  The branch is per lane.  In the ISA (hipcc -O3, gfx950) the +-1 side is 78 instructions (the
+// negation, eight selects, the nine-limb carry chain) and the product side about 320 (64 v_mad_u64_u32 with their carries and the
+// 32-byte pool load), behind a common head of 17 (the record and the witness entry).  A branch-free form in the manner of
+// lazy_mac_sel (every term a product, +-1 as pool entries) costs every wave the 320; with the branch a wave whose lanes are all
+// +-1 -- all but a few waves of a circom matrix -- never issues the product, and a mixed wave pays both sides, a quarter over the
+// product alone.  So: the branch.
+__device__ __forceinline__ void r1cs_term(Lazy17& acc, const uint2 rec, const Fr* __restrict__ wit, const Fr* __restrict__ pool_mont) {
+    const Fr w = load_fr(wit + rec.x);
+    if (rec.y < 2u) {
+        const Fr neg = fr_sub(fr_zero(), w);   // r - w; 0 stays 0
+        Fr x;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) x.l[i] = rec.y ? neg.l[i] : w.l[i];
+        lazy_add_hi(acc, x, true);
+    } else {
+        lazy_mac_v(acc, w, load_fr(pool_mont + rec.y));
+    }
+}
+
+}  // namespace
+
+// One thread per row.  Rows with more than kR1csLongRow records are left to k_r1cs_rows_long (a thread-per-row wave runs as
+// long as its longest row); rows past n_constraints store zero.  One lazy_reduce per row (see the term bounds above).
+// grid = (ceil(2^n / 256), 3, batch)
+__global__ void __launch_bounds__(256) k_r1cs_rows_short(const R1csCsr csr, const Fr* __restrict__ witness, size_t witness_stride,
+                                                         Fr* __restrict__ out) {
+    const uint32_t m = blockIdx.y, row = blockIdx.x * 256u + threadIdx.x;
+    const size_t len = (size_t)1 << csr.n;
+    if (row >= len) return;
+    Fr* dst = out + ((size_t)blockIdx.z * 3 + m) * len + row;
+    if (row >= csr.n_constraints) {
+        store_fr(dst, fr_zero());
+        return;
+    }
+    const uint32_t* __restrict__ rp = pick3(csr.row_ptr, m);
+    const uint2* __restrict__ terms = pick3(csr.terms, m);
+    const uint32_t begin = rp[row], end = rp[row + 1];
+    if (end - begin > kR1csLongRow) return;
+    const Fr* wit = witness + (size_t)blockIdx.z * witness_stride;
+    Lazy17 acc = lazy_zero();
+    for (uint32_t t = begin; t < end; ++t) r1cs_term(acc, terms[t], wit, csr.pool_mont);
+    store_fr(dst, lazy_reduce(acc));
+}
+
+// One wave per long row: the lanes stride over the row's records, each with its own Lazy17 and one reduction; the wave totals
+// the 64 canonical values through Acc<9> and shuffles (the block reductions of kernels_product.hip), lane 0 stores.  Launched only
+// where a matrix has long rows; a matrix with fewer of them than the grid is wide leaves its surplus blocks at once.
+// grid = (the largest number of long rows of a matrix, 3, batch), block = 64
+__global__ void __launch_bounds__(64) k_r1cs_rows_long(const R1csCsr csr, const Fr* __restrict__ witness, size_t witness_stride,
+                                                       Fr* __restrict__ out) {
+    const uint32_t m = blockIdx.y;
+    if (blockIdx.x >= pick3(csr.n_long, m)) return;   // (block-uniform: before any shuffle)
+    const uint32_t* __restrict__ rp = pick3(csr.row_ptr, m);
+    const uint2* __restrict__ terms = pick3(csr.terms, m);
+    const uint32_t row = pick3(csr.long_rows, m)[blockIdx.x];
+    const uint32_t begin = rp[row], end = rp[row + 1];
+    const Fr* wit = witness + (size_t)blockIdx.z * witness_stride;
+    Lazy17 acc = lazy_zero();
+    for (uint64_t t = (uint64_t)begin + threadIdx.x; t < end; t += 64u) r1cs_term(acc, terms[t], wit, csr.pool_mont);   // (64 bits: begin + 63 may pass 2^32)
+    Acc<9> sum = acc_zero<9>();
+    acc_add_fr(sum, lazy_reduce(acc));
+    sum = wave_sum(sum);
+    if (threadIdx.x == 0) store_fr(out + (((size_t)blockIdx.z * 3 + m) << csr.n) + row, acc_reduce(sum));
+}
+
+// a * b == c at every row below n_constraints of every witness's three tables; first_bad[b] = the lowest row where it fails
+// (preset to UINT32_MAX by the launcher).  The block's minimum by wave shuffle and LDS, ONE atomicMin per block that found one.
+// grid = (ceil(n_constraints / 256), batch)
+__global__ void __launch_bounds__(256) k_r1cs_check(const Fr* __restrict__ tables, uint32_t n, uint32_t n_constraints,
+                                                    uint32_t* __restrict__ first_bad) {
+    __shared__ uint32_t s_min[4];
+    const uint32_t row = blockIdx.x * 256u + threadIdx.x;
+    const size_t len = (size_t)1 << n;
+    const Fr* t = tables + (size_t)blockIdx.y * 3 * len;
+    uint32_t bad = 0xFFFFFFFFu;
+    if (row < n_constraints) {
+        const Fr a = load_fr(t + row), b = load_fr(t + len + row), c = load_fr(t + 2 * len + row);
+        if (!fr_eq(mont_mul(to_mont(a), b), c)) bad = row;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const uint32_t o = __shfl_down(bad, off, 64);
+        bad = o < bad ? o : bad;
+    }
+    if ((threadIdx.x & 63u) == 0) s_min[threadIdx.x >> 6] = bad;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w) bad = s_min[w] < bad ? s_min[w] : bad;
+        if (bad != 0xFFFFFFFFu) atomicMin(first_bad + blockIdx.y, bad);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// launchers
+// ---------------------------------------------------------------------------
+
+void launch_r1cs_rows(const R1csCsr& csr, const Fr* witness, size_t witness_stride, uint32_t batch, Fr* out, hipStream_t s) {
+    const uint32_t blocks = (uint32_t)((((size_t)1 << csr.n) + 255) / 256);
+    hipLaunchKernelGGL(k_r1cs_rows_short, dim3(blocks, 3, batch), dim3(256), 0, s, csr, witness, witness_stride, out);
+    const uint32_t max_long = std::max(csr.n_long[0], std::max(csr.n_long[1], csr.n_long[2]));
+    if (max_long) hipLaunchKernelGGL(k_r1cs_rows_long, dim3(max_long, 3, batch), dim3(64), 0, s, csr, witness, witness_stride, out);
+}
+
+hipError_t launch_r1cs_check(const Fr* tables, uint32_t n, uint32_t n_constraints, uint32_t batch, uint32_t* first_bad, hipStream_t s) {
+    const hipError_t rc = hipMemsetAsync(first_bad, 0xFF, (size_t)batch * sizeof(uint32_t), s);
+    if (rc != hipSuccess) return rc;
+    hipLaunchKernelGGL(k_r1cs_check, dim3((n_constraints + 255u) / 256u, batch), dim3(256), 0, s, tables, n, n_constraints, first_bad);
+    return hipSuccess;
+}
+
+}  // namespace gkr

@@ -801,3 +801,104 @@ int gkr_layered_input_values(const gkr_layered* L, uint32_t index, const gkr_fr*
 void gkr_layered_free(gkr_layered* L) { delete L; }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------- the matrices in CSR form
+// What the device's row kernels (kernels_r1cs.hip) read: per matrix the row offsets and 8-byte records {wire, pool index}, one
+// pool of distinct coefficients for the three matrices.  circom's matrices are almost all +-1: a record is 8 bytes instead of
+// 36, and pool entries 0 (one) and 1 (r - 1) need no product on the device.
+namespace {
+
+constexpr uint32_t kR1csLongRow = GKR_R1CS_LONG_ROW;
+
+// One walk over the constraints in the pool's order of first appearance (constraint, then A, B, C, then the file's order);
+// `term(matrix, row, wire, pool index)` for every kept term, `row_end(matrix, row, kept terms)` after every row.
+struct CoeffPool {
+    std::map<std::array<uint64_t, 4>, uint32_t> index;
+    std::vector<gkr_fr> values;
+    CoeffPool() {
+        add(fr_one());
+        add(fr_neg(fr_one()));
+    }
+    uint32_t add(const gkr_fr& c) {
+        const std::array<uint64_t, 4> key = {c.l[0], c.l[1], c.l[2], c.l[3]};
+        const auto it = index.find(key);
+        if (it != index.end()) return it->second;
+        const uint32_t id = (uint32_t)values.size();
+        index.emplace(key, id);
+        values.push_back(c);
+        return id;
+    }
+};
+
+template <typename TermFn, typename RowFn>
+void csr_walk(const gkr_r1cs& r, CoeffPool& pool, TermFn term, RowFn row_end) {
+    const gkr_fr one = fr_one(), minus_one = fr_neg(one);
+    for (size_t i = 0; i < r.constraints.size(); ++i)
+        for (int m = 0; m < 3; ++m) {
+            size_t kept = 0;
+            for (const Term& t : r.constraints[i][m]) {
+                if (fr_is_zero(t.coeff)) continue;
+                const uint32_t c = fr_eq(t.coeff, one) ? 0u : (fr_eq(t.coeff, minus_one) ? 1u : pool.add(t.coeff));
+                term(m, i, t.wire, c);
+                ++kept;
+            }
+            row_end(m, i, kept);
+        }
+}
+
+int csr_shape(const gkr_r1cs* r, uint32_t* n_out) {
+    if (!r || r->constraints.empty() || r->n_wires == 0) return GKR_ERR_INVALID;
+    uint32_t n = 2;
+    while (n < 64 && ((size_t)1 << n) < r->constraints.size()) ++n;
+    if (n > GKR_MAX_MLE_N) return GKR_ERR_INVALID;
+    *n_out = n;
+    return GKR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gkr_r1cs_csr_info(const gkr_r1cs* r, gkr_r1cs_csr_info_t* out) {
+    uint32_t n = 0;
+    if (!out) return GKR_ERR_INVALID;
+    if (const int rc = csr_shape(r, &n)) return rc;
+    memset(out, 0, sizeof *out);
+    out->n = n;
+    out->n_wires = r->n_wires;
+    out->n_constraints = r->constraints.size();
+    CoeffPool pool;
+    csr_walk(*r, pool, [&](int m, size_t, uint32_t, uint32_t) { out->n_terms[m] += 1; },
+             [&](int m, size_t, size_t kept) { out->n_long_rows[m] += kept > kR1csLongRow ? 1 : 0; });
+    out->n_pool = pool.values.size();
+    for (int m = 0; m < 3; ++m)
+        if (out->n_terms[m] > 0xFFFFFFFFull) return GKR_ERR_UNSUPPORTED;   // row_ptr is 32 bits wide
+    return GKR_OK;
+}
+
+int gkr_r1cs_csr_export(const gkr_r1cs* r, int matrix, uint32_t* row_ptr, gkr_r1cs_term* terms, uint32_t* long_rows, gkr_fr* pool_out) {
+    if (matrix < 0 || matrix > 2) return GKR_ERR_INVALID;
+    uint32_t n = 0;
+    if (const int rc = csr_shape(r, &n)) return rc;
+    CoeffPool pool;
+    size_t pos = 0, n_long = 0;
+    if (row_ptr) row_ptr[0] = 0;
+    csr_walk(*r, pool,
+             [&](int m, size_t, uint32_t wire, uint32_t c) {
+                 if (m != matrix) return;
+                 if (terms) terms[pos] = gkr_r1cs_term{wire, c};
+                 ++pos;
+             },
+             [&](int m, size_t row, size_t kept) {
+                 if (m != matrix) return;
+                 if (row_ptr) row_ptr[row + 1] = (uint32_t)pos;
+                 if (kept > kR1csLongRow) {
+                     if (long_rows) long_rows[n_long] = (uint32_t)row;
+                     ++n_long;
+                 }
+             });
+    if (pool_out) memcpy(pool_out, pool.values.data(), pool.values.size() * sizeof(gkr_fr));
+    return pos > 0xFFFFFFFFull ? GKR_ERR_UNSUPPORTED : GKR_OK;   // (the info call, where the sizes come from, has refused it already)
+}
+
+}  // extern "C"

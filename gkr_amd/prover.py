@@ -189,6 +189,41 @@ class VerifyHandle:
             pass
 
 
+class R1csRows:
+    """An R1CS's matrices in CSR form on a context's device (gkr_r1cs_rows_prepare): made once per R1CS by Context.r1cs_rows, taken
+    by Context.r1cs_rows_device / r1cs_zerocheck_batch_device for witness after witness.  Close it before its context."""
+
+    def __init__(self, ctx, handle):
+        self._ctx = ctx
+        self._h = handle
+
+    def info(self):
+        """The CSR form's sizes: n (tables of 2^n entries), n_wires, n_constraints, n_terms / n_long_rows per matrix, n_pool."""
+        out = N.R1csCsrInfo()
+        rc = N.lib().gkr_r1cs_rows_info(self._h, ctypes.byref(out))
+        if rc:
+            raise GkrError(rc, "gkr_r1cs_rows_info")
+        return out.as_dict()
+
+    def close(self):
+        if self._h:
+            N.lib().gkr_r1cs_rows_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            if self._ctx is not None and self._ctx._h:
+                self.close()
+        except Exception:
+            pass
+
+
 class Context:
     """One GPU context (one HIP stream).  Not thread-safe; use one per thread."""
 
@@ -507,6 +542,62 @@ class Context:
         sumcheck of an SOP layout."""
         pts = self._points(z, batch, n)
         self._check(N.lib().gkr_eq_table_device(self._h, _ptr(pts), n, batch, d_out, (1 << n) if stride is None else int(stride)))
+
+    # -- the R1CS zero-check: Az, Bz, Cz of resident witnesses built on the device, then eq(z, .) (A B - C)
+    def r1cs_rows(self, r1cs) -> R1csRows:
+        """gkr_r1cs_rows_prepare: the CSR form of `r1cs` (convert.R1cs) resident on this context's device."""
+        h = ctypes.c_void_p()
+        self._check(N.lib().gkr_r1cs_rows_prepare(self._h, r1cs._h, ctypes.byref(h)))
+        return R1csRows(self, h)
+
+    def r1cs_rows_device(self, rows, d_witness, batch, d_out, stride=None, check=True):
+        """gkr_r1cs_rows_device: the tables Az, Bz, Cz of `batch` resident witnesses (witness b: n_wires canonical elements at
+        d_witness + b * stride elements; None: n_wires) into d_out, table m of witness b at (b * 3 + m) * 2^n elements, rows past
+        n_constraints zero.  -> first_bad (batch,) uint32: the lowest constraint with a * b != c or 0xFFFFFFFF; None without check."""
+        inf = rows.info()
+        bad = np.zeros(max(int(batch), 0), dtype=np.uint32) if check else None
+        self._check(N.lib().gkr_r1cs_rows_device(self._h, rows._h, d_witness, inf["n_wires"] if stride is None else int(stride), batch, d_out,
+                                                 _ptr(bad) if check else None))
+        return bad
+
+    def r1cs_zerocheck_batch_device(self, rows, d_witness, batch, z, stride=None):
+        """gkr_r1cs_zerocheck_batch_device: the tables of `batch` resident witnesses (as r1cs_rows_device lays them out, in context
+        workspace), then the zero-check eq(z_b, .) (A B - C) with verifier.R1CS_ZEROCHECK_TERMS.  z: (batch, n, 4) limbs or `batch`
+        lists of n integers.  -> (C, L, R, E, Q, first_bad): the first five are sumcheck_zerocheck_batch_device's on those tables
+        (C (batch, n, 4, 4)), first_bad as r1cs_rows_device returns it.  An unsatisfied witness is not an error: its claim
+        g_1(0) + g_1(1) is non-zero."""
+        inf = rows.info()
+        n = inf["n"]
+        pts = self._points(z, batch, n)
+        C = np.zeros((batch, n, 4, 4), dtype=np.uint64)
+        L = np.zeros((batch, n), dtype=np.uint32)
+        R = np.zeros((batch, n, 4), dtype=np.uint64)
+        E = np.zeros((batch, 3, 4), dtype=np.uint64)
+        Q = np.zeros((batch, 4), dtype=np.uint64)
+        bad = np.zeros(batch, dtype=np.uint32)
+        self._check(N.lib().gkr_r1cs_zerocheck_batch_device(self._h, rows._h, d_witness, inf["n_wires"] if stride is None else int(stride), batch,
+                                                            _ptr(pts), _ptr(C), _ptr(L), _ptr(R), _ptr(E), _ptr(Q), _ptr(bad)))
+        return C, L, R, E, Q, bad
+
+    def prove_r1cs_zerocheck(self, r1cs, witness, z):
+        """gkr_r1cs_zerocheck: the zero-check of one host witness (a list of at least n_wires integers) of `r1cs` at the point z of
+        n = r1cs.csr_info()["n"] integers (or (1, n, 4) limbs; the witness may be (count, 4) limbs too).  -> (proof, r, evals, eq_r, first_bad): proof[j] the round vector (its used slots, highest
+        degree first), r the challenges, evals = [Az~(r), Bz~(r), Cz~(r)], eq_r = eq(z, r), first_bad the lowest constraint the
+        witness breaks or None.  verifier.verify_sumcheck_zerocheck(proof, r, evals, R1CS_ZEROCHECK_TERMS, z, 0) accepts a satisfied
+        witness's transcript; the claims on evals are left to the caller."""
+        n = r1cs.csr_info()["n"]
+        wl = as_limbs(witness)
+        pts = self._points(z if isinstance(z, np.ndarray) else [z], 1, n)      # (limbs: a (1, n, 4) array, passed as it is)
+        C = np.zeros((n, 4, 4), dtype=np.uint64)
+        L = np.zeros(n, dtype=np.uint32)
+        R = np.zeros((n, 4), dtype=np.uint64)
+        E = np.zeros((3, 4), dtype=np.uint64)
+        Q = np.zeros((1, 4), dtype=np.uint64)
+        bad = np.zeros(1, dtype=np.uint32)
+        self._check(N.lib().gkr_r1cs_zerocheck(self._h, r1cs._h, _ptr(wl), wl.shape[0], _ptr(pts), _ptr(C), _ptr(L), _ptr(R), _ptr(E), _ptr(Q),
+                                               _ptr(bad)))
+        return ([from_limbs(C[j])[4 - int(L[j]):] for j in range(n)], from_limbs(R), from_limbs(E), from_limbs(Q)[0],
+                None if int(bad[0]) == 0xFFFFFFFF else int(bad[0]))
 
     # -- the plain sumcheck's verifier (verify_sumcheck, python/sumcheck.py:55-70, plus g_n(r_n) = T(r)) and the evaluation behind it
     def mle_eval_batch_device(self, d_tables, n, batch, points):
@@ -903,3 +994,7 @@ def prove_sumcheck_sop(tables, terms, v):
 
 def prove_zerocheck(tables, terms, z, v):
     return default_context().prove_zerocheck(tables, terms, z, v)
+
+
+def prove_r1cs_zerocheck(r1cs, witness, z):
+    return default_context().prove_r1cs_zerocheck(r1cs, witness, z)

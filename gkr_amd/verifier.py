@@ -148,6 +148,10 @@ def verify_sumcheck_sop(rounds: List[List[int]], challenges: List[int], evals: L
     return expected == total
 
 
+# the R1CS zero-check eq(z, .) (Az * Bz - Cz) over the tables [Az, Bz, Cz] (Context.prove_r1cs_zerocheck): verify_sumcheck_zerocheck's terms
+R1CS_ZEROCHECK_TERMS = [(1, (0, 1)), (P - 1, (2,))]
+
+
 def verify_sumcheck_zerocheck(rounds: List[List[int]], challenges: List[int], evals: List[int], terms, z: List[int], claim=None) -> bool:
     """The verifier of a zero-check's transcript (Context.prove_zerocheck) on plain integers.  terms: [(coeff, (table
     indices ..)), ..] of 1 or 2 indices each as the prover took them; evals[m] the value of table m at the challenges; z the

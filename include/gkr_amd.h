@@ -925,6 +925,68 @@ int  gkr_layered_input_values(const gkr_layered *layered, uint32_t index, const 
                               gkr_fr *out_values);
 void gkr_layered_free(gkr_layered *layered);
 
+/* ---- R1CS zero-check: Az, Bz, Cz built on the device, then eq (A B - C) ---------------------------------
+ * A witness w satisfies an R1CS iff  sum_x eq(z, x) (Az(x) Bz(x) - Cz(x)) = 0  for a random z, with Az(i) = <A_i, w> the value
+ * of constraint i's first linear combination (Bz, Cz alike) and zero for i >= n_constraints.  The three tables are sparse
+ * matrix-vector products; they are computed on the device from the witness and handed to the zero-check above.
+ *
+ * Host side (no device, no context): the matrices A, B, C = matrix 0, 1, 2 in CSR form.  row_ptr: n_constraints + 1 offsets into
+ * the matrix's term records; a record is {wire, coeff}, coeff an index into ONE pool of distinct canonical coefficients shared by
+ * the three matrices: pool[0] = 1 and pool[1] = r - 1 always, the other values in order of first appearance (constraint by
+ * constraint, A before B before C, a row's terms in the file's order).  A term with coefficient 0 is dropped; a wire that
+ * appears twice in a row stays as two terms; an empty combination is an empty row.  long_rows: the ascending indices of the rows
+ * with more than GKR_R1CS_LONG_ROW terms (the device gives those a wave each instead of a thread).
+ * n = max(2, ceil(log2(n_constraints))): the tables have 2^n entries.
+ * GKR_ERR_INVALID: NULL r1cs or out, n_constraints == 0, n > GKR_MAX_MLE_N, n_wires == 0, a matrix outside 0 .. 2.
+ * GKR_ERR_UNSUPPORTED: more than 2^32 - 1 terms in one matrix. */
+#define GKR_R1CS_LONG_ROW 32
+typedef struct { uint32_t wire, coeff; } gkr_r1cs_term;
+typedef struct {
+    uint32_t n, n_wires;
+    size_t n_constraints, n_terms[3], n_long_rows[3], n_pool;   /* n_terms: without the dropped ones */
+} gkr_r1cs_csr_info_t;
+int  gkr_r1cs_csr_info(const gkr_r1cs *r1cs, gkr_r1cs_csr_info_t *out);
+/* any output pointer may be NULL; sizes from the info call (row_ptr n_constraints + 1, terms n_terms[matrix], long_rows
+ * n_long_rows[matrix], pool n_pool) */
+int  gkr_r1cs_csr_export(const gkr_r1cs *r1cs, int matrix, uint32_t *row_ptr, gkr_r1cs_term *terms, uint32_t *long_rows,
+                         gkr_fr *pool);
+
+/* The CSR form resident on ONE context's device (row offsets, records, long-row lists, the pool in Montgomery form): made once
+ * per R1CS, used for witness after witness.  Free it before its context is destroyed.  GKR_ERR_INVALID (plain return) for a NULL
+ * pointer and whatever the info call refuses. */
+typedef struct gkr_r1cs_rows gkr_r1cs_rows;
+int  gkr_r1cs_rows_prepare(gkr_ctx *ctx, const gkr_r1cs *r1cs, gkr_r1cs_rows **out);
+int  gkr_r1cs_rows_info(const gkr_r1cs_rows *rows, gkr_r1cs_csr_info_t *out);
+void gkr_r1cs_rows_free(gkr_r1cs_rows *rows);
+
+/* d_out[(b * 3 + m) * 2^n + i] = sum_t pool[coeff_t] * w_b[wire_t] over row i of matrix m, canonical; rows >= n_constraints are
+ * zero: batch x 3 tables of 2^n values, the n_tables = 3 layout of the zero-check.  Witness b: the n_wires canonical elements at
+ * d_witness + b * stride_elements (canonical by precondition, as every resident table is); not modified.
+ * out_first_bad: batch values, the lowest constraint index with a * b != c, or UINT32_MAX; NULL = no check pass.
+ * GKR_ERR_INVALID (plain returns, before a device is touched): NULL ctx, rows, d_witness or d_out; batch outside 1 .. 65535;
+ * stride_elements < n_wires; batch * 3 * 2^n above 2^30; rows prepared on another context. */
+int  gkr_r1cs_rows_device(gkr_ctx *ctx, const gkr_r1cs_rows *rows, const void *d_witness, size_t stride_elements, int batch,
+                          void *d_out, uint32_t *out_first_bad);
+
+/* The rows into context workspace (slots of this path's own: a plain, product, SOP or zero-check call on the same context is
+ * unaffected), then the zero-check with terms {2, {0, 1}} coefficient 1 and {1, {2}} coefficient r - 1: the outputs of the
+ * zero-check's batch call with n_tables = 3 (rows of 4 slots), byte for byte what that call returns on the tables the call above
+ * writes.  An unsatisfied witness is NOT an error: its transcript has a non-zero claim g_1(0) + g_1(1), and out_first_bad says
+ * where.  The verifier is left with claims on the three tables' values at r (out_evals); reducing those to the witness is a
+ * sumcheck over the columns and not part of this call.
+ * GKR_ERR_INVALID as above, and for NULL z, out_coeffs, out_len or out_r; GKR_ERR_NON_CANONICAL (through the context) for a z
+ * entry >= r. */
+int  gkr_r1cs_zerocheck_batch_device(gkr_ctx *ctx, const gkr_r1cs_rows *rows, const void *d_witness, size_t stride_elements, int batch,
+                                     const gkr_fr *z /* host, batch x n */, gkr_fr *out_coeffs, uint32_t *out_len, gkr_fr *out_r,
+                                     gkr_fr *out_evals /* batch x 3 or NULL */, gkr_fr *out_eq /* batch or NULL */,
+                                     uint32_t *out_first_bad /* batch or NULL */);
+
+/* A host witness of n_witness >= n_wires values: prepare + upload + the call above with batch 1 + free.  GKR_ERR_INVALID also for
+ * n_witness < n_wires and for 3 * 2^n above 2^30; GKR_ERR_NON_CANONICAL also for a witness entry >= r. */
+int  gkr_r1cs_zerocheck(gkr_ctx *ctx, const gkr_r1cs *r1cs, const gkr_fr *witness, size_t n_witness, const gkr_fr *z /* n */,
+                        gkr_fr *out_coeffs, uint32_t *out_len, gkr_fr *out_r, gkr_fr *out_evals, gkr_fr *out_eq,
+                        uint32_t *out_first_bad);
+
 /* ---- step-wise sessions: one sumcheck split across GPUs -------------------
  * The reference reduces each round's per-assignment polynomials with a rayon
  * map-reduce (sumcheck.rs:50-63,65-78,97-124); across GPUs that reduce is one
