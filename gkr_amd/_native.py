@@ -27,6 +27,9 @@ GKR_VERIFY_ROUND_SUM, GKR_VERIFY_CHALLENGE, GKR_VERIFY_EVALUATION = 4, 5, 10
 
 # rows of an R1CS matrix with more terms than this get a wave each on the device (GKR_R1CS_LONG_ROW)
 GKR_R1CS_LONG_ROW = 32
+# columns with more records than this are cut into segments of at most GKR_R1CS_COL_SEGMENT records, a wave each (GKR_R1CS_LONG_COL)
+GKR_R1CS_LONG_COL = 32
+GKR_R1CS_COL_SEGMENT = 2048
 
 # limits of the sumcheck over a sum of products (gkr_sumcheck_sop*)
 GKR_SOP_MAX_TABLES = 8
@@ -55,6 +58,8 @@ SYMBOLS = [
     "gkr_r1cs_parse", "gkr_r1cs_build", "gkr_r1cs_info", "gkr_r1cs_export", "gkr_r1cs_serialize", "gkr_r1cs_free",
     "gkr_r1cs_csr_info", "gkr_r1cs_csr_export", "gkr_r1cs_rows_prepare", "gkr_r1cs_rows_info", "gkr_r1cs_rows_free", "gkr_r1cs_rows_device",
     "gkr_r1cs_zerocheck_batch_device", "gkr_r1cs_zerocheck",
+    "gkr_r1cs_csc_info", "gkr_r1cs_csc_export", "gkr_r1cs_cols_prepare", "gkr_r1cs_cols_prepare_segment", "gkr_r1cs_cols_info", "gkr_r1cs_cols_free",
+    "gkr_r1cs_cols_device", "gkr_r1cs_inner_batch_device", "gkr_r1cs_inner",
     "gkr_wtns_parse", "gkr_wtns_serialize", "gkr_r1cs_compile", "gkr_layered_count", "gkr_layered_circuit",
     "gkr_layered_input_layer", "gkr_layered_input_values", "gkr_layered_free",
     "gkr_device_alloc", "gkr_device_free", "gkr_device_upload", "gkr_device_download",
@@ -107,6 +112,16 @@ class R1csCsrInfo(ctypes.Structure):
     def as_dict(self):
         return dict(n=int(self.n), n_wires=int(self.n_wires), n_constraints=int(self.n_constraints), n_terms=[int(x) for x in self.n_terms],
                     n_long_rows=[int(x) for x in self.n_long_rows], n_pool=int(self.n_pool))
+
+
+class R1csCscInfo(ctypes.Structure):
+    """gkr_r1cs_csc_info_t: the column-major form's sizes; eq tables of 2^n_x entries, T and the padded witness of 2^n_y."""
+    _fields_ = [("n_x", ctypes.c_uint32), ("n_y", ctypes.c_uint32), ("n_wires", ctypes.c_uint32), ("n_constraints", ctypes.c_size_t),
+                ("n_terms", ctypes.c_size_t * 3), ("n_long_cols", ctypes.c_size_t * 3), ("n_pool", ctypes.c_size_t)]
+
+    def as_dict(self):
+        return dict(n_x=int(self.n_x), n_y=int(self.n_y), n_wires=int(self.n_wires), n_constraints=int(self.n_constraints),
+                    n_terms=[int(x) for x in self.n_terms], n_long_cols=[int(x) for x in self.n_long_cols], n_pool=int(self.n_pool))
 
 
 class SopTerm(ctypes.Structure):
@@ -197,6 +212,28 @@ def lib():
         # (ctx, r1cs, witness, n_witness, z, out_coeffs, out_len, out_r, out_evals, out_eq, out_first_bad)
         L.gkr_r1cs_zerocheck.restype = ctypes.c_int
         L.gkr_r1cs_zerocheck.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_size_t] + [ctypes.c_void_p] * 7
+        # the R1CS inner sumcheck: the column-major form (host only), the resident handle, the table T, the sumcheck over (T, w)
+        L.gkr_r1cs_csc_info.restype = ctypes.c_int
+        L.gkr_r1cs_csc_info.argtypes = [ctypes.c_void_p] * 2
+        L.gkr_r1cs_csc_export.restype = ctypes.c_int
+        L.gkr_r1cs_csc_export.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4
+        L.gkr_r1cs_cols_prepare.restype = ctypes.c_int
+        L.gkr_r1cs_cols_prepare.argtypes = [ctypes.c_void_p] * 3
+        L.gkr_r1cs_cols_prepare_segment.restype = ctypes.c_int
+        L.gkr_r1cs_cols_prepare_segment.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_uint32, ctypes.c_void_p]
+        L.gkr_r1cs_cols_info.restype = ctypes.c_int
+        L.gkr_r1cs_cols_info.argtypes = [ctypes.c_void_p] * 2
+        L.gkr_r1cs_cols_free.restype = None
+        L.gkr_r1cs_cols_free.argtypes = [ctypes.c_void_p]
+        # (ctx, cols, x, rho, batch, d_out, out_stride_elements)
+        L.gkr_r1cs_cols_device.restype = ctypes.c_int
+        L.gkr_r1cs_cols_device.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t]
+        # (ctx, cols, d_witness, stride_elements, batch, x, rho, out_coeffs, out_len, out_r, out_evals)
+        L.gkr_r1cs_inner_batch_device.restype = ctypes.c_int
+        L.gkr_r1cs_inner_batch_device.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_size_t, ctypes.c_int] + [ctypes.c_void_p] * 6
+        # (ctx, r1cs, witness, n_witness, x, rho, out_coeffs, out_len, out_r, out_evals)
+        L.gkr_r1cs_inner.restype = ctypes.c_int
+        L.gkr_r1cs_inner.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_size_t] + [ctypes.c_void_p] * 6
         L.gkr_selftest_product_geometry.restype = ctypes.c_int
         L.gkr_selftest_product_geometry.argtypes = [ctypes.c_int] * 2 + [ctypes.c_void_p] * 2
         for fn in (L.gkr_r1cs_free, L.gkr_layered_free):

@@ -115,6 +115,29 @@ class R1cs:
                                            _ptr(long_rows) if len(long_rows) else None, _ptr(pool)), "gkr_r1cs_csr_export")
         return row_ptr, terms, long_rows, from_limbs(pool)
 
+    def csc_info(self):
+        """gkr_r1cs_csc_info: the sizes of the column-major form the inner sumcheck's kernels read -- n_x (eq tables of 2^n_x
+        entries; the CSR form's n), n_y (T and the padded witness have 2^n_y entries), n_wires, n_constraints, n_terms /
+        n_long_cols per matrix (A, B, C), n_pool."""
+        out = N.R1csCscInfo()
+        _check(N.lib().gkr_r1cs_csc_info(self._h, ctypes.byref(out)), "gkr_r1cs_csc_info")
+        return out.as_dict()
+
+    def csc(self, matrix):
+        """gkr_r1cs_csc_export: matrix 0 / 1 / 2 = A / B / C -> (col_ptr (n_wires + 1,) uint32, terms (n_terms, 2) uint32 rows of
+        (ROW, pool index), a column's records in ascending row order and within a row in the CSR order, long_cols uint32 (the
+        columns with more than GKR_R1CS_LONG_COL records, ascending), pool: the CSR form's pool)."""
+        if matrix not in (0, 1, 2):
+            raise GkrError(N.GKR_ERR_INVALID, "matrix 0, 1 or 2 expected")
+        inf = self.csc_info()
+        col_ptr = np.zeros(inf["n_wires"] + 1, dtype=np.uint32)
+        terms = np.zeros((inf["n_terms"][matrix], 2), dtype=np.uint32)
+        long_cols = np.zeros(inf["n_long_cols"][matrix], dtype=np.uint32)
+        pool = np.zeros((inf["n_pool"], 4), dtype=np.uint64)
+        _check(N.lib().gkr_r1cs_csc_export(self._h, matrix, _ptr(col_ptr), _ptr(terms) if len(terms) else None,
+                                           _ptr(long_cols) if len(long_cols) else None, _ptr(pool)), "gkr_r1cs_csc_export")
+        return col_ptr, terms, long_cols, from_limbs(pool)
+
     def serialize(self) -> bytes:
         need = ctypes.c_size_t()
         _check(N.lib().gkr_r1cs_serialize(self._h, None, ctypes.c_size_t(0), ctypes.byref(need)), "gkr_r1cs_serialize")

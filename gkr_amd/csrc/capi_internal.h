@@ -752,6 +752,11 @@ int verify_hash_rows_device(gkr_ctx* ctx, int slots, const uint32_t* d_rows, con
 bool product_shape_ok(int n, int degree, int batch);
 // blocks per sumcheck of round `round` (0-based) of the product passes; the sum-of-products passes (capi_sop.hip) launch the same
 uint32_t product_round_blocks(int n, int batch, int round);
+// `batch` product sumchecks on resident tables, the whole of gkr_sumcheck_product_batch_device behind its argument checks (the
+// R1CS inner sumcheck runs it on the tables it builds): everything already queued on the context's stream is waited for, the
+// outputs are in the caller's arrays
+int run_product_batch(gkr_ctx* ctx, const Fr* d_tables, int n, int degree, int batch, gkr_fr* out_coeffs, uint32_t* out_len, gkr_fr* out_r,
+                      gkr_fr* out_evals);
 // ---- defined in capi_sop.hip
 // the shapes gkr_sumcheck_sop* and gkr_sumcheck_sop_verify* admit, with the term structure in the kernels' form; the term
 // coefficients in the kernels' form (NULL: all one), false: one is >= r

@@ -18,7 +18,7 @@ uint32_t product_round_blocks(int n, int batch, int round) {
 }
 
 // Workspace slots are this path's own ("product.*"): a call may follow a plain sumcheck on the same context.
-static int run_product_batch(gkr_ctx* ctx, const Fr* d_tables, int n, int degree, int batch, gkr_fr* out_coeffs, uint32_t* out_len,
+int run_product_batch(gkr_ctx* ctx, const Fr* d_tables, int n, int degree, int batch, gkr_fr* out_coeffs, uint32_t* out_len,
                              gkr_fr* out_r, gkr_fr* out_evals) {
     const size_t len = (size_t)1 << n, rounds = (size_t)batch * n, tables = (size_t)batch * degree, slots = (size_t)degree + 1;
     hipStream_t s = ctx->stream;

@@ -1,6 +1,8 @@
 // The R1CS zero-check: the CSR form of an R1CS (r1cs.cpp) resident on a context's device, the tables Az, Bz, Cz of a batch of
 // resident witnesses (kernels_r1cs.hip), the row check a * b == c, and the zero-check eq(z, .) (A B - C) on those tables
-// (run_zerocheck_batch, capi_zerocheck.hip).  C ABI: include/gkr_amd.h.
+// (run_zerocheck_batch, capi_zerocheck.hip).  And the inner sumcheck that reduces the zero-check's three claims to the witness: the
+// column-major form resident, the table T(y) = sum_m rho_m sum_i M_m[i][y] eq(x, i), the product path at degree 2 on (T, w)
+// (run_product_batch, capi_product.hip).  C ABI: include/gkr_amd.h.
 #include "capi_internal.h"
 
 static_assert(sizeof(gkr_r1cs_term) == sizeof(uint2), "a record is eight bytes: {wire, pool index}");
@@ -33,6 +35,49 @@ struct gkr_r1cs_rows {
         c.pool_mont = pool_mont;
         c.n_constraints = (uint32_t)info.n_constraints;
         c.n = info.n;
+        return c;
+    }
+};
+
+static_assert(gkr::kR1csLongCol == GKR_R1CS_LONG_COL, "the kernels and the host's long-column lists cut at the same length");
+static_assert(gkr::kR1csColSegment == GKR_R1CS_COL_SEGMENT, "the header names the kernels' segment length");
+
+// The column-major form (r1cs.cpp) resident on a context's device, for the inner sumcheck's table (kernels_r1cs.hip).
+struct gkr_r1cs_cols {
+    gkr_ctx* ctx = nullptr;
+    gkr_r1cs_csc_info_t info{};
+    uint32_t* col_ptr[3] = {nullptr, nullptr, nullptr};
+    uint2* terms[3] = {nullptr, nullptr, nullptr};
+    uint32_t* long_cols[3] = {nullptr, nullptr, nullptr};
+    uint4* segs = nullptr;
+    uint32_t *comb_cols = nullptr, *comb_ptr = nullptr;
+    Fr* pool_mont = nullptr;
+    size_t terms_total = 0, n_segs = 0, n_comb = 0;
+    void release() {
+        for (int m = 0; m < 3; ++m) {
+            if (col_ptr[m]) (void)hipFree(col_ptr[m]);
+            if (terms[m]) (void)hipFree(terms[m]);
+            if (long_cols[m]) (void)hipFree(long_cols[m]);
+        }
+        if (segs) (void)hipFree(segs);
+        if (comb_cols) (void)hipFree(comb_cols);
+        if (comb_ptr) (void)hipFree(comb_ptr);
+        if (pool_mont) (void)hipFree(pool_mont);
+    }
+    gkr::R1csCsc csc() const {
+        gkr::R1csCsc c;
+        for (int m = 0; m < 3; ++m) {
+            c.col_ptr[m] = col_ptr[m];
+            c.terms[m] = terms[m];
+        }
+        c.pool_mont = pool_mont;
+        c.segs = segs;
+        c.comb_cols = comb_cols;
+        c.comb_ptr = comb_ptr;
+        c.n_segs = (uint32_t)n_segs;
+        c.n_comb = (uint32_t)n_comb;
+        c.n_wires = info.n_wires;
+        c.n_y = info.n_y;
         return c;
     }
 };
@@ -118,11 +163,187 @@ static int run_r1cs_zerocheck(gkr_ctx* ctx, const gkr_r1cs_rows* rows, const Fr*
     return run_zerocheck_batch(ctx, d_tables, n, ts, cf, batch, z, out_coeffs, out_len, out_r, out_evals, out_eq);
 }
 
+// ---- the inner sumcheck: the column-major form, the table T, the product path on (T, w)
+
+// the argument checks of the two resident entry points of the columns (plain returns: decided before the context is looked at)
+static bool r1cs_cols_args(const gkr_ctx* ctx, const gkr_r1cs_cols* cols, const gkr_fr* x, const gkr_fr* rho, int batch) {
+    if (!ctx || !cols || !x || !rho) return false;
+    if (batch < 1 || batch > 65535) return false;
+    if (cols->ctx != ctx) return false;
+    if (cols->info.n_y > 29 || (((unsigned long long)batch * 2ull) << cols->info.n_y) > (1ull << 30)) return false;   // batch * 2 * 2^n_y values
+    if (((unsigned long long)batch << cols->info.n_x) > (1ull << 30)) return false;                                   // batch * 2^n_x values
+    return true;
+}
+
+// The records go up as the host exports them; the long columns of the three matrices are cut into segments of at most `segment`
+// records (0: one segment per long column and matrix), listed column by column so that one column's partials are neighbours.
+static int upload_cols(gkr_ctx* ctx, const gkr_r1cs* r1cs, uint32_t segment, gkr_r1cs_cols* cols) {
+    const gkr_r1cs_csc_info_t& info = cols->info;
+    std::vector<uint32_t> col_ptr((size_t)info.n_wires + 1), long_cols;
+    std::vector<gkr_r1cs_term> terms;
+    std::vector<gkr_fr> pool(info.n_pool);
+    std::vector<uint4> segs;
+    for (int m = 0; m < 3; ++m) {
+        terms.resize(info.n_terms[m]);
+        long_cols.resize(info.n_long_cols[m]);
+        if (const int rc = gkr_r1cs_csc_export(r1cs, m, col_ptr.data(), terms.data(), long_cols.data(), m == 0 ? pool.data() : nullptr))
+            return ctx->fail(rc, "gkr_r1cs_csc_export");
+        HIP_TRY(ctx, upload_new(&cols->col_ptr[m], col_ptr.data(), col_ptr.size()));
+        HIP_TRY(ctx, upload_new(&cols->terms[m], reinterpret_cast<const uint2*>(terms.data()), terms.size()));
+        HIP_TRY(ctx, upload_new(&cols->long_cols[m], long_cols.data(), long_cols.size()));
+        cols->terms_total += terms.size();
+        for (const uint32_t col : long_cols) {
+            const uint64_t end = col_ptr[(size_t)col + 1], step = segment ? segment : end - col_ptr[col];
+            for (uint64_t at = col_ptr[col]; at < end; at += step)
+                segs.push_back(make_uint4(col, (uint32_t)m, (uint32_t)at, (uint32_t)std::min(at + step, end)));
+        }
+    }
+    if (segs.size() > 0x7FFFFFFFull) return ctx->fail(GKR_ERR_UNSUPPORTED, "more than 2^31 - 1 segments of long columns");
+    std::stable_sort(segs.begin(), segs.end(), [](const uint4& a, const uint4& b) { return a.x < b.x; });
+    std::vector<uint32_t> comb_cols, comb_ptr;
+    for (size_t i = 0; i < segs.size(); ++i)
+        if (i == 0 || segs[i].x != segs[i - 1].x) {
+            comb_cols.push_back(segs[i].x);
+            comb_ptr.push_back((uint32_t)i);
+        }
+    comb_ptr.push_back((uint32_t)segs.size());
+    cols->n_segs = segs.size();
+    cols->n_comb = comb_cols.size();
+    HIP_TRY(ctx, upload_new(&cols->segs, segs.data(), segs.size()));
+    HIP_TRY(ctx, upload_new(&cols->comb_cols, comb_cols.data(), comb_cols.size()));
+    HIP_TRY(ctx, upload_new(&cols->comb_ptr, comb_ptr.data(), comb_ptr.size()));
+    std::vector<Fr> pool_mont(pool.size());
+    for (size_t i = 0; i < pool.size(); ++i) pool_mont[i] = gkr::to_mont(to_dev(pool[i]));   // canonical eq entry x Montgomery coefficient
+    HIP_TRY(ctx, upload_new(&cols->pool_mont, pool_mont.data(), pool_mont.size()));
+    return GKR_OK;
+}
+
+static int prepare_cols(gkr_ctx* ctx, const gkr_r1cs* r1cs, uint32_t segment, gkr_r1cs_cols** out) {
+    if (!ctx || !r1cs || !out) return GKR_ERR_INVALID;
+    *out = nullptr;
+    if (segment != 0 && segment < 64) return GKR_ERR_INVALID;   // a segment is a wave's work
+    std::unique_ptr<gkr_r1cs_cols, void (*)(gkr_r1cs_cols*)> cols(new gkr_r1cs_cols(), gkr_r1cs_cols_free);
+    if (const int rc = gkr_r1cs_csc_info(r1cs, &cols->info)) return rc;
+    cols->ctx = ctx;
+    GKR_ENTER(ctx);
+    if (const int rc = upload_cols(ctx, r1cs, segment, cols.get())) return rc;
+    *out = cols.release();
+    return GKR_OK;
+}
+
+// The tables T_b of `batch` sumchecks into d_out (table b at b * out_stride elements); everything queued on the context's stream,
+// the caller synchronises -- `stage` holds the points and the weights until then.  Workspace slots are this path's own
+// ("r1cs.cols.*").  x and rho are canonical (the caller's check).
+static int run_r1cs_cols(gkr_ctx* ctx, const gkr_r1cs_cols* cols, const gkr_fr* x, const gkr_fr* rho, int batch, Fr* d_out, size_t out_stride,
+                         std::vector<Fr>& stage) {
+    hipStream_t s = ctx->stream;
+    const uint32_t n_x = cols->info.n_x;
+    const size_t n_pts = (size_t)batch * n_x, n_rho = (size_t)batch * 3;
+    stage.resize(n_pts + n_rho);
+    for (size_t i = 0; i < n_pts; ++i) stage[i] = to_dev(x[i]);
+    for (size_t i = 0; i < n_rho; ++i) stage[n_pts + i] = gkr::to_mont(to_dev(rho[i]));   // canonical column sum x Montgomery rho
+    Fr *d_stage = nullptr, *d_eq = nullptr, *d_part = nullptr;
+    WS(ctx, "r1cs.cols.points", Fr, stage.size(), d_stage);
+    WS(ctx, "r1cs.cols.eq", Fr, (size_t)batch << n_x, d_eq);
+    WS(ctx, "r1cs.cols.partials", Fr, std::max<size_t>((size_t)batch * cols->n_segs, 1), d_part);
+    HIP_TRY(ctx, hipMemcpyAsync(d_stage, stage.data(), stage.size() * sizeof(Fr), hipMemcpyHostToDevice, s));
+    {
+        Timed t(ctx, "r1cs_cols_eq", (double)batch * 32.0 * (double)((size_t)1 << n_x));
+        gkr::launch_eq_table(d_stage, n_x, 0u, n_x, d_eq, false, (uint32_t)batch, s);
+    }
+    {
+        const double len = (double)((size_t)1 << cols->info.n_y);
+        Timed t(ctx, "r1cs_cols", (double)batch * (8.0 * cols->terms_total + 32.0 * cols->terms_total + 32.0 * len));
+        gkr::launch_r1cs_cols(cols->csc(), d_eq, n_x, d_stage + n_pts, (uint32_t)batch, d_part, d_out, out_stride, s);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return GKR_OK;
+}
+
+// {T_b, w_b zero-padded} in the product path's layout, then that path at degree 2 (which synchronises)
+static int run_r1cs_inner(gkr_ctx* ctx, const gkr_r1cs_cols* cols, const Fr* d_witness, size_t stride, int batch, const gkr_fr* x,
+                          const gkr_fr* rho, gkr_fr* out_coeffs, uint32_t* out_len, gkr_fr* out_r, gkr_fr* out_evals) {
+    const int n_y = (int)cols->info.n_y;
+    const size_t len = (size_t)1 << n_y;
+    Fr* d_tables = nullptr;
+    WS(ctx, "r1cs.cols.tables", Fr, ((size_t)batch * 2) << n_y, d_tables);
+    std::vector<Fr> stage;
+    if (const int rc = run_r1cs_cols(ctx, cols, x, rho, batch, d_tables, 2 * len, stage)) return rc;
+    gkr::launch_r1cs_pad_witness(d_witness, stride, cols->info.n_wires, cols->info.n_y, (uint32_t)batch, d_tables + len, 2 * len, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    return run_product_batch(ctx, d_tables, n_y, 2, batch, out_coeffs, out_len, out_r, out_evals);
+}
+
 }  // namespace gkr_host
 
 // =========================================================================== C ABI
 
 extern "C" {
+
+int gkr_r1cs_cols_prepare(gkr_ctx* ctx, const gkr_r1cs* r1cs, gkr_r1cs_cols** out) {
+    return prepare_cols(ctx, r1cs, GKR_R1CS_COL_SEGMENT, out);
+}
+
+int gkr_r1cs_cols_prepare_segment(gkr_ctx* ctx, const gkr_r1cs* r1cs, uint32_t segment, gkr_r1cs_cols** out) {
+    return prepare_cols(ctx, r1cs, segment, out);
+}
+
+int gkr_r1cs_cols_info(const gkr_r1cs_cols* cols, gkr_r1cs_csc_info_t* out) {
+    if (!cols || !out) return GKR_ERR_INVALID;
+    *out = cols->info;
+    return GKR_OK;
+}
+
+void gkr_r1cs_cols_free(gkr_r1cs_cols* cols) {
+    if (!cols) return;
+    if (cols->ctx) (void)hipSetDevice(cols->ctx->device);
+    cols->release();
+    delete cols;
+}
+
+int gkr_r1cs_cols_device(gkr_ctx* ctx, const gkr_r1cs_cols* cols, const gkr_fr* x, const gkr_fr* rho, int batch, void* d_out,
+                         size_t out_stride_elements) {
+    if (!r1cs_cols_args(ctx, cols, x, rho, batch) || !d_out) return GKR_ERR_INVALID;
+    if (out_stride_elements < ((size_t)1 << cols->info.n_y)) return GKR_ERR_INVALID;
+    if (!all_canonical(x, (size_t)batch * cols->info.n_x)) return ctx->fail(GKR_ERR_NON_CANONICAL, "x entry >= r");
+    if (!all_canonical(rho, (size_t)batch * 3)) return ctx->fail(GKR_ERR_NON_CANONICAL, "rho entry >= r");
+    GKR_ENTER(ctx);
+    std::vector<Fr> stage;
+    if (const int rc = run_r1cs_cols(ctx, cols, x, rho, batch, static_cast<Fr*>(d_out), out_stride_elements, stage)) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->drain_events();
+    return GKR_OK;
+}
+
+int gkr_r1cs_inner_batch_device(gkr_ctx* ctx, const gkr_r1cs_cols* cols, const void* d_witness, size_t stride_elements, int batch,
+                                const gkr_fr* x, const gkr_fr* rho, gkr_fr* out_coeffs, uint32_t* out_len, gkr_fr* out_r, gkr_fr* out_evals) {
+    if (!r1cs_cols_args(ctx, cols, x, rho, batch) || !d_witness || !out_coeffs || !out_len || !out_r) return GKR_ERR_INVALID;
+    if (stride_elements < cols->info.n_wires) return GKR_ERR_INVALID;
+    if (!all_canonical(x, (size_t)batch * cols->info.n_x)) return ctx->fail(GKR_ERR_NON_CANONICAL, "x entry >= r");
+    if (!all_canonical(rho, (size_t)batch * 3)) return ctx->fail(GKR_ERR_NON_CANONICAL, "rho entry >= r");
+    GKR_ENTER(ctx);
+    return run_r1cs_inner(ctx, cols, static_cast<const Fr*>(d_witness), stride_elements, batch, x, rho, out_coeffs, out_len, out_r, out_evals);
+}
+
+int gkr_r1cs_inner(gkr_ctx* ctx, const gkr_r1cs* r1cs, const gkr_fr* witness, size_t n_witness, const gkr_fr* x, const gkr_fr* rho,
+                   gkr_fr* out_coeffs, uint32_t* out_len, gkr_fr* out_r, gkr_fr* out_evals) {
+    if (!ctx || !r1cs || !witness || !x || !rho || !out_coeffs || !out_len || !out_r) return GKR_ERR_INVALID;
+    gkr_r1cs_csc_info_t info;
+    if (const int rc = gkr_r1cs_csc_info(r1cs, &info)) return rc;
+    if (n_witness < info.n_wires) return GKR_ERR_INVALID;
+    if (info.n_y > 29 || (2ull << info.n_y) > (1ull << 30) || (1ull << info.n_x) > (1ull << 30)) return GKR_ERR_INVALID;   // the caps of the resident call at batch 1
+    if (!all_canonical(x, (size_t)info.n_x)) return ctx->fail(GKR_ERR_NON_CANONICAL, "x entry >= r");
+    if (!all_canonical(rho, 3)) return ctx->fail(GKR_ERR_NON_CANONICAL, "rho entry >= r");
+    if (!all_canonical(witness, n_witness)) return ctx->fail(GKR_ERR_NON_CANONICAL, "witness entry >= r");
+    gkr_r1cs_cols* raw = nullptr;
+    if (const int rc = gkr_r1cs_cols_prepare(ctx, r1cs, &raw)) return rc;
+    std::unique_ptr<gkr_r1cs_cols, void (*)(gkr_r1cs_cols*)> cols(raw, gkr_r1cs_cols_free);
+    GKR_ENTER(ctx);
+    DevBuf<Fr> d;
+    HIP_TRY(ctx, d.alloc(info.n_wires));
+    HIP_TRY(ctx, hipMemcpyAsync(d.p, witness, (size_t)info.n_wires * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+    return run_r1cs_inner(ctx, cols.get(), d.p, info.n_wires, 1, x, rho, out_coeffs, out_len, out_r, out_evals);
+}
 
 int gkr_r1cs_rows_prepare(gkr_ctx* ctx, const gkr_r1cs* r1cs, gkr_r1cs_rows** out) {
     if (!ctx || !r1cs || !out) return GKR_ERR_INVALID;

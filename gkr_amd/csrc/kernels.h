@@ -499,6 +499,33 @@ void launch_r1cs_rows(const R1csCsr& csr, const Fr* witness, size_t witness_stri
 // first_bad[b] = the lowest row < n_constraints of sumcheck b's tables (a, b, c at (b * 3 + m) * 2^n) with a * b != c, UINT32_MAX if none
 hipError_t launch_r1cs_check(const Fr* tables, uint32_t n, uint32_t n_constraints, uint32_t batch, uint32_t* first_bad, hipStream_t s);
 
+// ---- the R1CS inner sumcheck's table (kernels_r1cs.hip) ----------------------------------------------------------------------------
+// The three matrices in column-major form, resident: matrix m's n_wires + 1 column offsets and its records {x: row, y: pool
+// index}; the pool in Montgomery form.  A column of more than kR1csLongCol records of a matrix is cut into segments of at most
+// kR1csColSegment records (the host's lists): segs[s] = {x: column, y: matrix, z: first record, w: one past the last}, sorted by
+// column, so that the segments of one column -- of all three matrices -- are neighbours; comb_cols[k] is the k-th column that has
+// any, comb_ptr[k] .. comb_ptr[k + 1] its segments.  Tables of 2^n_y entries.
+constexpr uint32_t kR1csLongCol = 32;        // (= GKR_R1CS_LONG_COL)
+constexpr uint32_t kR1csColSegment = 2048;   // (= GKR_R1CS_COL_SEGMENT)
+struct R1csCsc {
+    const uint32_t* col_ptr[3];
+    const uint2* terms[3];
+    const Fr* pool_mont;
+    const uint4* segs;
+    const uint32_t* comb_cols;
+    const uint32_t* comb_ptr;
+    uint32_t n_segs, n_comb, n_wires, n_y;
+};
+// out[b * out_stride + y] = sum_m rho_{b,m} sum_{records (i, c) of column y of matrix m} pool[c] * eq[b << n_x | i], canonical, for
+// y < 2^n_y; zero for y >= n_wires.  eq: batch canonical tables of 2^n_x entries; rho_mont: batch x 3, Montgomery; partials:
+// batch * n_segs elements of scratch (unused without segments).  Three launches in stream order: a thread per column, a wave per
+// segment, a wave per column that has segments.
+void launch_r1cs_cols(const R1csCsc& csc, const Fr* eq, uint32_t n_x, const Fr* rho_mont, uint32_t batch, Fr* partials, Fr* out,
+                      size_t out_stride, hipStream_t s);
+// dst[b * dst_stride + y] = y < n_wires ? witness[b * witness_stride + y] : 0 for y < 2^n_y (the witness as a factor of the product path)
+void launch_r1cs_pad_witness(const Fr* witness, size_t witness_stride, uint32_t n_wires, uint32_t n_y, uint32_t batch, Fr* dst,
+                             size_t dst_stride, hipStream_t s);
+
 uint32_t layer_blocks(uint32_t h);
 void launch_layer_round(const Fr* A, const Fr* M, uint32_t h, uint32_t k, uint32_t phase, uint32_t hb, const Fr* Wb,
                         const Fr* Wc, uint32_t nblk, LayerPartial* partials, LayerBatch lb, hipStream_t s);

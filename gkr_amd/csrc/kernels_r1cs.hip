@@ -1,5 +1,6 @@
 // CDNA4 (gfx950) kernels of the R1CS zero-check's tables (gkr_r1cs_rows_device): Az, Bz, Cz of a witness as sparse matrix-vector
-// products over BN254 Fr, and the row-wise check a * b == c.
+// products over BN254 Fr, and the row-wise check a * b == c; and of the R1CS inner sumcheck's table (gkr_r1cs_cols_device): the
+// same records gathered by COLUMN against the eq table of a point (the second half of this file).
 //
 //   out[(b * 3 + m) * 2^n + i] = sum_t pool[coeff_t] * w_b[wire_t]   over the records of row i of matrix m, canonical;
 //   rows >= n_constraints are zero.
@@ -125,6 +126,97 @@ __global__ void __launch_bounds__(256) k_r1cs_check(const Fr* __restrict__ table
 }
 
 // ---------------------------------------------------------------------------
+// the inner sumcheck's table: T(y) = sum_m rho_m sum_{records (i, c) of column y of matrix m} pool[c] * eq(x, i)
+// ---------------------------------------------------------------------------
+// The same records gathered the other way: the vector is the canonical eq table of the sumcheck's point, a record's first field
+// the ROW, and r1cs_term's arithmetic and term bounds carry over unchanged (a column has fewer than 2^32 records: the offsets are
+// 32 bits wide).  Column lengths are heavy-tailed where row lengths are not -- wire 0, the constant, may stand in every
+// constraint -- so a long column is cut into SEGMENTS (the host's list) and a wave takes a segment, not a column.
+//
+// The rho scaling: ONE eq table per sumcheck, one Lazy17 and one lazy_reduce per (column, matrix), then one Montgomery product
+// with rho_m (Montgomery form) on the canonical sum and a modular addition.  The other form -- three eq tables pre-scaled by
+// rho_m, one accumulator and one reduce per column -- has no product and one reduce per column.  In the ISA (hipcc -O3, gfx950)
+// lazy_reduce is about 1400 instructions (192 v_mad_u64_u32) and the product with its addition about 650 (128): a column with
+// records in k of the three matrices pays k x 2050 here against 1400 there.  But that form builds, stores and gathers three
+// tables of 2^n_x entries where this one has one: three times the eq pass and three times the footprint of the 32-byte gather,
+// the access DESIGN.md section 3 prices highest.  An empty (column, matrix) skips its reduce and product here, and a wire of a
+// circom system stands in one or two of the three matrices.  So: one table, a product per matrix.  (The other form is not
+// measured.)
+
+// One thread per column, the three matrices in turn (m is not unrolled: one copy of r1cs_term's two sides).  A matrix in which
+// the column has more than kR1csLongCol records is left to the segment waves; the thread stores the sum of the others -- zero if
+// there is none -- which k_r1cs_cols_combine completes.  Columns past n_wires store zero.
+// grid = (ceil(2^n_y / 256), batch)
+__global__ void __launch_bounds__(256) k_r1cs_cols_short(const R1csCsc csc, const Fr* __restrict__ eq, uint32_t n_x,
+                                                         const Fr* __restrict__ rho_mont, Fr* __restrict__ out, size_t out_stride) {
+    const size_t y = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (y >= ((size_t)1 << csc.n_y)) return;
+    Fr* dst = out + (size_t)blockIdx.y * out_stride + y;
+    if (y >= csc.n_wires) {
+        store_fr(dst, fr_zero());
+        return;
+    }
+    const Fr* e = eq + ((size_t)blockIdx.y << n_x);
+    const Fr* rho = rho_mont + (size_t)blockIdx.y * 3;
+    Fr total = fr_zero();
+#pragma unroll 1
+    for (uint32_t m = 0; m < 3; ++m) {
+        const uint32_t* __restrict__ cp = pick3(csc.col_ptr, m);
+        const uint2* __restrict__ terms = pick3(csc.terms, m);
+        const uint32_t begin = cp[y], end = cp[y + 1];
+        if (begin == end || end - begin > kR1csLongCol) continue;
+        Lazy17 acc = lazy_zero();
+        for (uint32_t t = begin; t < end; ++t) r1cs_term(acc, terms[t], e, csc.pool_mont);
+        total = fr_add(total, mont_mul(lazy_reduce(acc), load_fr(rho + m)));
+    }
+    store_fr(dst, total);
+}
+
+// One wave per segment of a long column: the lanes stride over the segment's records, each with its own Lazy17 and one
+// reduction; the wave totals the 64 canonical values through Acc<9> and shuffles, lane 0 scales the total by the matrix's rho
+// and stores the canonical partial.  No atomics: every segment has a slot of its own.
+// grid = (n_segs, batch), block = 64
+__global__ void __launch_bounds__(64) k_r1cs_cols_long(const R1csCsc csc, const Fr* __restrict__ eq, uint32_t n_x,
+                                                       const Fr* __restrict__ rho_mont, Fr* __restrict__ partials) {
+    const uint4 sg = csc.segs[blockIdx.x];   // {column, matrix, first record, one past the last}: block-uniform
+    const uint2* __restrict__ terms = pick3(csc.terms, sg.y);
+    const Fr* e = eq + ((size_t)blockIdx.y << n_x);
+    Lazy17 acc = lazy_zero();
+    for (uint64_t t = (uint64_t)sg.z + threadIdx.x; t < sg.w; t += 64u) r1cs_term(acc, terms[t], e, csc.pool_mont);   // (64 bits: first + 63 may pass 2^32)
+    Acc<9> sum = acc_zero<9>();
+    acc_add_fr(sum, lazy_reduce(acc));
+    sum = wave_sum(sum);
+    if (threadIdx.x == 0)
+        store_fr(partials + (size_t)blockIdx.y * csc.n_segs + blockIdx.x, mont_mul(acc_reduce(sum), load_fr(rho_mont + (size_t)blockIdx.y * 3 + sg.y)));
+}
+
+// One wave per column that has segments: the partials of its segments, of all three matrices, added to what the short pass
+// stored.  Stream order puts this launch behind both.
+// grid = (n_comb, batch), block = 64
+__global__ void __launch_bounds__(64) k_r1cs_cols_combine(const R1csCsc csc, const Fr* __restrict__ partials, Fr* __restrict__ out,
+                                                          size_t out_stride) {
+    const uint32_t col = csc.comb_cols[blockIdx.x], p0 = csc.comb_ptr[blockIdx.x], p1 = csc.comb_ptr[blockIdx.x + 1];
+    const Fr* part = partials + (size_t)blockIdx.y * csc.n_segs;
+    Acc<9> sum = acc_zero<9>();
+    for (uint64_t p = (uint64_t)p0 + threadIdx.x; p < p1; p += 64u) acc_add_fr(sum, load_fr(part + p));
+    sum = wave_sum(sum);
+    if (threadIdx.x == 0) {
+        Fr* dst = out + (size_t)blockIdx.y * out_stride + col;
+        acc_add_fr(sum, load_fr(dst));
+        store_fr(dst, acc_reduce(sum));
+    }
+}
+
+// the witness as the product path's second factor: copied, zero behind n_wires
+// grid = (ceil(2^n_y / 256), batch)
+__global__ void __launch_bounds__(256) k_r1cs_pad_witness(const Fr* __restrict__ witness, size_t witness_stride, uint32_t n_wires, uint32_t n_y,
+                                                          Fr* __restrict__ dst, size_t dst_stride) {
+    const size_t y = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (y >= ((size_t)1 << n_y)) return;
+    store_fr(dst + (size_t)blockIdx.y * dst_stride + y, y < n_wires ? load_fr(witness + (size_t)blockIdx.y * witness_stride + y) : fr_zero());
+}
+
+// ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
 
@@ -140,6 +232,21 @@ hipError_t launch_r1cs_check(const Fr* tables, uint32_t n, uint32_t n_constraint
     if (rc != hipSuccess) return rc;
     hipLaunchKernelGGL(k_r1cs_check, dim3((n_constraints + 255u) / 256u, batch), dim3(256), 0, s, tables, n, n_constraints, first_bad);
     return hipSuccess;
+}
+
+void launch_r1cs_cols(const R1csCsc& csc, const Fr* eq, uint32_t n_x, const Fr* rho_mont, uint32_t batch, Fr* partials, Fr* out,
+                      size_t out_stride, hipStream_t s) {
+    const uint32_t blocks = (uint32_t)((((size_t)1 << csc.n_y) + 255) / 256);
+    hipLaunchKernelGGL(k_r1cs_cols_short, dim3(blocks, batch), dim3(256), 0, s, csc, eq, n_x, rho_mont, out, out_stride);
+    if (!csc.n_segs) return;
+    hipLaunchKernelGGL(k_r1cs_cols_long, dim3(csc.n_segs, batch), dim3(64), 0, s, csc, eq, n_x, rho_mont, partials);
+    hipLaunchKernelGGL(k_r1cs_cols_combine, dim3(csc.n_comb, batch), dim3(64), 0, s, csc, partials, out, out_stride);
+}
+
+void launch_r1cs_pad_witness(const Fr* witness, size_t witness_stride, uint32_t n_wires, uint32_t n_y, uint32_t batch, Fr* dst,
+                             size_t dst_stride, hipStream_t s) {
+    const uint32_t blocks = (uint32_t)((((size_t)1 << n_y) + 255) / 256);
+    hipLaunchKernelGGL(k_r1cs_pad_witness, dim3(blocks, batch), dim3(256), 0, s, witness, witness_stride, n_wires, n_y, dst, dst_stride);
 }
 
 }  // namespace gkr

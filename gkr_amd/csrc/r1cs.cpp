@@ -902,3 +902,74 @@ int gkr_r1cs_csr_export(const gkr_r1cs* r, int matrix, uint32_t* row_ptr, gkr_r1
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------- the matrices in column-major form
+// What the device's column kernels (kernels_r1cs.hip, gkr_r1cs_cols_device) read: per matrix the column offsets (one column per
+// wire) and the SAME 8-byte records with the ROW in the first field, the pool of the CSR form entry for entry.  A stable counting
+// sort of the CSR records by wire: a column's records are in ascending row order, within a row in the CSR order.
+namespace {
+
+constexpr uint32_t kR1csLongCol = GKR_R1CS_LONG_COL;
+
+uint32_t csc_log2_wires(uint32_t n_wires) {
+    uint32_t n = 2;
+    while (n < 32 && ((uint64_t)1 << n) < n_wires) ++n;
+    return n;
+}
+
+// the records of column `wire` of matrix `matrix`, counted: col_ptr[w + 1] - col_ptr[w]; UNSUPPORTED as the CSR info call's
+int csc_col_ptr(const gkr_r1cs& r, int matrix, std::vector<uint32_t>& col_ptr, size_t* n_pool) {
+    std::vector<uint64_t> count((size_t)r.n_wires + 1, 0);
+    CoeffPool pool;
+    csr_walk(r, pool, [&](int m, size_t, uint32_t wire, uint32_t) { count[(size_t)wire + 1] += m == matrix ? 1 : 0; }, [](int, size_t, size_t) {});
+    for (size_t w = 0; w < r.n_wires; ++w) count[w + 1] += count[w];
+    if (count[r.n_wires] > 0xFFFFFFFFull) return GKR_ERR_UNSUPPORTED;   // col_ptr is 32 bits wide
+    col_ptr.assign(count.begin(), count.end());
+    if (n_pool) *n_pool = pool.values.size();
+    return GKR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gkr_r1cs_csc_info(const gkr_r1cs* r, gkr_r1cs_csc_info_t* out) {
+    uint32_t n = 0;
+    if (!out) return GKR_ERR_INVALID;
+    if (const int rc = csr_shape(r, &n)) return rc;
+    memset(out, 0, sizeof *out);
+    out->n_x = n;
+    out->n_y = csc_log2_wires(r->n_wires);
+    out->n_wires = r->n_wires;
+    out->n_constraints = r->constraints.size();
+    std::vector<uint32_t> col_ptr;
+    for (int m = 0; m < 3; ++m) {
+        if (const int rc = csc_col_ptr(*r, m, col_ptr, &out->n_pool)) return rc;
+        out->n_terms[m] = col_ptr[r->n_wires];
+        for (size_t w = 0; w < r->n_wires; ++w) out->n_long_cols[m] += col_ptr[w + 1] - col_ptr[w] > kR1csLongCol ? 1 : 0;
+    }
+    return GKR_OK;
+}
+
+int gkr_r1cs_csc_export(const gkr_r1cs* r, int matrix, uint32_t* col_ptr_out, gkr_r1cs_term* terms, uint32_t* long_cols, gkr_fr* pool_out) {
+    if (matrix < 0 || matrix > 2) return GKR_ERR_INVALID;
+    uint32_t n = 0;
+    if (const int rc = csr_shape(r, &n)) return rc;
+    std::vector<uint32_t> col_ptr;
+    if (const int rc = csc_col_ptr(*r, matrix, col_ptr, nullptr)) return rc;
+    if (col_ptr_out) memcpy(col_ptr_out, col_ptr.data(), col_ptr.size() * sizeof(uint32_t));
+    if (long_cols)
+        for (size_t w = 0, n_long = 0; w < r->n_wires; ++w)
+            if (col_ptr[w + 1] - col_ptr[w] > kR1csLongCol) long_cols[n_long++] = (uint32_t)w;
+    CoeffPool pool;
+    std::vector<uint32_t> next(col_ptr.begin(), col_ptr.end() - 1);   // the walk visits the rows in ascending order: a stable sort
+    csr_walk(*r, pool,
+             [&](int m, size_t row, uint32_t wire, uint32_t c) {
+                 if (m == matrix && terms) terms[next[wire]++] = gkr_r1cs_term{(uint32_t)row, c};
+             },
+             [](int, size_t, size_t) {});
+    if (pool_out) memcpy(pool_out, pool.values.data(), pool.values.size() * sizeof(gkr_fr));
+    return GKR_OK;
+}
+
+}  // extern "C"

@@ -224,6 +224,42 @@ class R1csRows:
             pass
 
 
+class R1csCols:
+    """An R1CS's matrices in column-major form on a context's device (gkr_r1cs_cols_prepare): made once per R1CS by
+    Context.r1cs_cols, taken by Context.r1cs_cols_device / r1cs_inner_batch_device for call after call.  Close it before its
+    context."""
+
+    def __init__(self, ctx, handle):
+        self._ctx = ctx
+        self._h = handle
+
+    def info(self):
+        """The column-major form's sizes: n_x, n_y, n_wires, n_constraints, n_terms / n_long_cols per matrix, n_pool."""
+        out = N.R1csCscInfo()
+        rc = N.lib().gkr_r1cs_cols_info(self._h, ctypes.byref(out))
+        if rc:
+            raise GkrError(rc, "gkr_r1cs_cols_info")
+        return out.as_dict()
+
+    def close(self):
+        if self._h:
+            N.lib().gkr_r1cs_cols_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            if self._ctx is not None and self._ctx._h:
+                self.close()
+        except Exception:
+            pass
+
+
 class Context:
     """One GPU context (one HIP stream).  Not thread-safe; use one per thread."""
 
@@ -598,6 +634,72 @@ class Context:
                                                _ptr(bad)))
         return ([from_limbs(C[j])[4 - int(L[j]):] for j in range(n)], from_limbs(R), from_limbs(E), from_limbs(Q)[0],
                 None if int(bad[0]) == 0xFFFFFFFF else int(bad[0]))
+
+    # -- the R1CS inner sumcheck: the zero-check's claims on Az, Bz, Cz at r_x reduced to one claim on the witness
+    def r1cs_cols(self, r1cs, segment=None) -> R1csCols:
+        """gkr_r1cs_cols_prepare: the column-major form of `r1cs` (convert.R1cs) resident on this context's device.  segment: long
+        columns cut into segments of at most this many records instead of GKR_R1CS_COL_SEGMENT (0: no cut;
+        gkr_r1cs_cols_prepare_segment, for measurements -- results do not depend on it)."""
+        h = ctypes.c_void_p()
+        if segment is None:
+            self._check(N.lib().gkr_r1cs_cols_prepare(self._h, r1cs._h, ctypes.byref(h)))
+        else:
+            self._check(N.lib().gkr_r1cs_cols_prepare_segment(self._h, r1cs._h, int(segment), ctypes.byref(h)))
+        return R1csCols(self, h)
+
+    @staticmethod
+    def _rho(rho, batch):
+        """rho as (batch, 3, 4) limbs: such an array, or `batch` triples of integers (reduced modulo r)."""
+        if isinstance(rho, np.ndarray) and rho.dtype == np.uint64:
+            out = np.ascontiguousarray(rho)
+        else:
+            out = to_limbs([int(v) % MODULUS for row in rho for v in row]).reshape(-1, 3, 4) if len(rho) else np.zeros((0, 3, 4), dtype=np.uint64)
+        if out.shape != (batch, 3, 4):
+            raise GkrError(N.GKR_ERR_INVALID, "weights of shape (batch, 3, 4) expected")
+        return out
+
+    def r1cs_cols_device(self, cols, x, rho, batch, d_out, stride=None):
+        """gkr_r1cs_cols_device: the tables T_b(y) = sum_m rho_{b,m} sum_i M_m[i][y] eq(x_b, i) of `batch` sumchecks into d_out,
+        table b at d_out + b * stride elements (None: 2^n_y), zero for y >= n_wires.  x: (batch, n_x, 4) limbs or `batch` lists of
+        n_x integers; rho: (batch, 3, 4) limbs or `batch` triples."""
+        inf = cols.info()
+        pts = self._points(x, batch, inf["n_x"])
+        self._check(N.lib().gkr_r1cs_cols_device(self._h, cols._h, _ptr(pts), _ptr(self._rho(rho, batch)), batch, d_out,
+                                                 (1 << inf["n_y"]) if stride is None else int(stride)))
+
+    def r1cs_inner_batch_device(self, cols, d_witness, batch, x, rho, stride=None):
+        """gkr_r1cs_inner_batch_device: the tables {T_b, w_b zero-padded to 2^n_y} of `batch` resident witnesses (witness b: n_wires
+        canonical elements at d_witness + b * stride elements; None: n_wires) in context workspace, then the product sumcheck at
+        degree 2 on them.  -> (C, L, R, E): sumcheck_product_batch_device's on those tables -- C (batch, n_y, 3, 4), L (batch, n_y),
+        R (batch, n_y, 4), E (batch, 2, 4) = T_b~(r_y), w_b~(r_y)."""
+        inf = cols.info()
+        n_y = inf["n_y"]
+        pts = self._points(x, batch, inf["n_x"])
+        C = np.zeros((batch, n_y, 3, 4), dtype=np.uint64)
+        L = np.zeros((batch, n_y), dtype=np.uint32)
+        R = np.zeros((batch, n_y, 4), dtype=np.uint64)
+        E = np.zeros((batch, 2, 4), dtype=np.uint64)
+        self._check(N.lib().gkr_r1cs_inner_batch_device(self._h, cols._h, d_witness, inf["n_wires"] if stride is None else int(stride), batch,
+                                                        _ptr(pts), _ptr(self._rho(rho, batch)), _ptr(C), _ptr(L), _ptr(R), _ptr(E)))
+        return C, L, R, E
+
+    def prove_r1cs_inner(self, r1cs, witness, x, rho):
+        """gkr_r1cs_inner: the inner sumcheck of one host witness (at least n_wires integers, or (count, 4) limbs) of `r1cs` at the
+        point x of n_x = r1cs.csc_info()["n_x"] integers -- the zero-check's challenges -- with the weights rho = (rho_A, rho_B,
+        rho_C).  -> (proof, r, evals): proof[j] the round vector (its used slots, highest degree first), r the n_y challenges,
+        evals = [T~(r), w~(r)].  verifier.verify_r1cs_inner(r1cs.constraints(), x, rho, claims_abc, proof, r, evals) checks it
+        against the zero-check's claims and the public matrices and returns the claim left on the witness."""
+        inf = r1cs.csc_info()
+        n_y = inf["n_y"]
+        wl = as_limbs(witness)
+        pts = self._points(x if isinstance(x, np.ndarray) else [x], 1, inf["n_x"])
+        rh = self._rho(rho if isinstance(rho, np.ndarray) else [rho], 1)
+        C = np.zeros((n_y, 3, 4), dtype=np.uint64)
+        L = np.zeros(n_y, dtype=np.uint32)
+        R = np.zeros((n_y, 4), dtype=np.uint64)
+        E = np.zeros((2, 4), dtype=np.uint64)
+        self._check(N.lib().gkr_r1cs_inner(self._h, r1cs._h, _ptr(wl), wl.shape[0], _ptr(pts), _ptr(rh), _ptr(C), _ptr(L), _ptr(R), _ptr(E)))
+        return [from_limbs(C[j])[3 - int(L[j]):] for j in range(n_y)], from_limbs(R), from_limbs(E)
 
     # -- the plain sumcheck's verifier (verify_sumcheck, python/sumcheck.py:55-70, plus g_n(r_n) = T(r)) and the evaluation behind it
     def mle_eval_batch_device(self, d_tables, n, batch, points):
@@ -998,3 +1100,7 @@ def prove_zerocheck(tables, terms, z, v):
 
 def prove_r1cs_zerocheck(r1cs, witness, z):
     return default_context().prove_r1cs_zerocheck(r1cs, witness, z)
+
+
+def prove_r1cs_inner(r1cs, witness, x, rho):
+    return default_context().prove_r1cs_inner(r1cs, witness, x, rho)

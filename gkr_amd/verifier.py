@@ -184,6 +184,54 @@ def verify_sumcheck_zerocheck(rounds: List[List[int]], challenges: List[int], ev
     return expected == eq_r * total % P
 
 
+def _eq_table(point: List[int]) -> List[int]:
+    """[eq(point, i) for i < 2^n], variable 1 = most significant index bit."""
+    t = [1]
+    for x in point:
+        x %= P
+        t = [v * f % P for v in t for f in ((1 - x) % P, x)]
+    return t
+
+
+def r1cs_matrix_evals(constraints, rx: List[int], ry: List[int]) -> List[int]:
+    """[A~, B~, C~](rx, ry) of an R1CS given as R1cs.constraints(): the multilinear extensions of the three matrices, rows indexed by
+    rx (len(rx) variables, 2^len(rx) >= the constraints) and columns -- wires -- by ry, variable 1 = most significant index bit:
+    M~(rx, ry) = sum over the terms (coefficient c, wire y) of constraint i of c eq(rx, i) eq(ry, y).  One pass over the non-zeros."""
+    if len(constraints) > 1 << len(rx) or any(w >> len(ry) for con in constraints for lc in con for _, w in lc):
+        raise ValueError("more constraints than 2^len(rx) or a wire past 2^len(ry)")
+    ex, ey = _eq_table(rx), _eq_table(ry)
+    out = [0, 0, 0]
+    for i, con in enumerate(constraints):
+        for m in range(3):
+            s = 0
+            for c, w in con[m]:
+                s += c * ey[w]
+            out[m] = (out[m] + ex[i] * (s % P)) % P
+    return out
+
+
+def verify_r1cs_inner(constraints, rx: List[int], rho: List[int], claims_abc: List[int], rounds: List[List[int]], challenges: List[int],
+                      evals: List[int]):
+    """The verifier of the R1CS inner sumcheck (Context.prove_r1cs_inner) on plain integers.  claims_abc = [Az~(rx), Bz~(rx),
+    Cz~(rx)], the zero-check's evals at its challenges rx; rho the three weights; evals = [T~(ry), w~(ry)] with ry = challenges.
+    The degree-2 checks of verify_sumcheck_product with claim = sum_m rho_m claims_abc[m], then
+    evals[0] == sum_m rho_m M_m~(rx, ry) from the public matrices (r1cs_matrix_evals).  -> the claim left on the witness,
+    (ry, evals[1]): w~(ry) == evals[1] is one evaluation of the (committed) witness and NOT checked here; None on a rejection."""
+    if len(rho) != 3 or len(claims_abc) != 3 or len(evals) != 2:
+        return None
+    claim = sum(r * v for r, v in zip(rho, claims_abc)) % P
+    if not verify_sumcheck_product(rounds, challenges, evals, 2, claim):
+        return None
+    ry = [r % P for r in challenges]
+    try:
+        mats = r1cs_matrix_evals(constraints, rx, ry)
+    except ValueError:
+        return None
+    if evals[0] % P != sum(r * v for r, v in zip(rho, mats)) % P:
+        return None
+    return ry, evals[1] % P
+
+
 def verify(proof: Proof, circuit: GKRCircuit) -> bool:
     """python/gkr.py:202-231 on the Rust-shaped proof."""
     L = circuit.depth()

@@ -972,8 +972,8 @@ int  gkr_r1cs_rows_device(gkr_ctx *ctx, const gkr_r1cs_rows *rows, const void *d
  * unaffected), then the zero-check with terms {2, {0, 1}} coefficient 1 and {1, {2}} coefficient r - 1: the outputs of the
  * zero-check's batch call with n_tables = 3 (rows of 4 slots), byte for byte what that call returns on the tables the call above
  * writes.  An unsatisfied witness is NOT an error: its transcript has a non-zero claim g_1(0) + g_1(1), and out_first_bad says
- * where.  The verifier is left with claims on the three tables' values at r (out_evals); reducing those to the witness is a
- * sumcheck over the columns and not part of this call.
+ * where.  The verifier is left with claims on the three tables' values at r (out_evals); reducing those to the witness is the
+ * inner sumcheck below (gkr_r1cs_inner_batch_device), a call of its own.
  * GKR_ERR_INVALID as above, and for NULL z, out_coeffs, out_len or out_r; GKR_ERR_NON_CANONICAL (through the context) for a z
  * entry >= r. */
 int  gkr_r1cs_zerocheck_batch_device(gkr_ctx *ctx, const gkr_r1cs_rows *rows, const void *d_witness, size_t stride_elements, int batch,
@@ -986,6 +986,76 @@ int  gkr_r1cs_zerocheck_batch_device(gkr_ctx *ctx, const gkr_r1cs_rows *rows, co
 int  gkr_r1cs_zerocheck(gkr_ctx *ctx, const gkr_r1cs *r1cs, const gkr_fr *witness, size_t n_witness, const gkr_fr *z /* n */,
                         gkr_fr *out_coeffs, uint32_t *out_len, gkr_fr *out_r, gkr_fr *out_evals, gkr_fr *out_eq,
                         uint32_t *out_first_bad);
+
+/* ---- R1CS inner sumcheck: the claims on Az, Bz, Cz at r_x reduced to ONE claim on the witness ------------------
+ * The zero-check above leaves v_A = Az~(r_x), v_B = Bz~(r_x), v_C = Cz~(r_x) (its out_evals at its out_r).  For any
+ * rho = (rho_A, rho_B, rho_C) and EVERY witness, satisfied or not,
+ *     rho_A v_A + rho_B v_B + rho_C v_C = sum_y T(y) w(y),    T(y) = sum_m rho_m sum_i M_m[i][y] eq(r_x, i),
+ * with M_0, M_1, M_2 = A, B, C, w the witness zero-padded to 2^n_y entries and n_y = max(2, ceil(log2 n_wires)): the second
+ * sumcheck of a Spartan-style argument.  T is a transposed sparse matrix-vector product, built on the device; the sumcheck is the
+ * product path's at degree 2 over (T, w).  It leaves w~(r_y) -- one evaluation of the witness, gkr_mle_eval_batch_device -- and
+ * T~(r_y) = sum_m rho_m M_m~(r_x, r_y), a sum over the non-zeros of the public matrices (gkr_amd/verifier.py, on integers).
+ * The points x and the weights rho are the CALLER's, as z is in the zero-check: nothing derives Fiat-Shamir challenges across
+ * calls.
+ *
+ * Host side (no device, no context): the matrices in COLUMN-major form, one column per wire.  col_ptr: n_wires + 1 offsets into
+ * the matrix's records; a record is the CSR form's gkr_r1cs_term with the ROW (the constraint index) in its first field (`wire`)
+ * and the same pool index: the pool is the CSR form's entry for entry, the same terms are dropped (coefficient 0), a wire that
+ * appears twice in a row gives two records with the same row.  A column's records are in ascending row order, within a row in the
+ * CSR order (a stable counting sort of the CSR records by wire).  long_cols: the ascending indices of the columns with more than
+ * GKR_R1CS_LONG_COL records.  n_x = the CSR form's n.  Refusals: the CSR info call's, GKR_ERR_UNSUPPORTED included. */
+#define GKR_R1CS_LONG_COL 32
+typedef struct {
+    uint32_t n_x, n_y, n_wires;
+    size_t n_constraints, n_terms[3], n_long_cols[3], n_pool;
+} gkr_r1cs_csc_info_t;
+int  gkr_r1cs_csc_info(const gkr_r1cs *r1cs, gkr_r1cs_csc_info_t *out);
+/* any output pointer may be NULL; sizes from the info call (col_ptr n_wires + 1, terms n_terms[matrix], long_cols
+ * n_long_cols[matrix], pool n_pool) */
+int  gkr_r1cs_csc_export(const gkr_r1cs *r1cs, int matrix, uint32_t *col_ptr, gkr_r1cs_term *terms, uint32_t *long_cols,
+                         gkr_fr *pool);
+
+/* The column-major form resident on ONE context's device (column offsets, records, long-column lists, the segments the long
+ * columns are cut into, the pool in Montgomery form): made once per R1CS and context, a type of its own beside the rows handle: a
+ * caller that never runs the inner sumcheck never pays for it.  Free it before its context is destroyed.  GKR_ERR_INVALID
+ * (plain return) for a NULL pointer and whatever the info call refuses.
+ * gkr_r1cs_cols_prepare_segment: the same with long columns cut into segments of at most `segment` records instead of
+ * GKR_R1CS_COL_SEGMENT (0: no cut, a wave per long column); results do not depend on it.  For measurements. */
+#define GKR_R1CS_COL_SEGMENT 2048
+typedef struct gkr_r1cs_cols gkr_r1cs_cols;
+int  gkr_r1cs_cols_prepare(gkr_ctx *ctx, const gkr_r1cs *r1cs, gkr_r1cs_cols **out);
+int  gkr_r1cs_cols_prepare_segment(gkr_ctx *ctx, const gkr_r1cs *r1cs, uint32_t segment, gkr_r1cs_cols **out);
+int  gkr_r1cs_cols_info(const gkr_r1cs_cols *cols, gkr_r1cs_csc_info_t *out);
+void gkr_r1cs_cols_free(gkr_r1cs_cols *cols);
+
+/* d_out[b * out_stride_elements + y] = sum_m rho_{b,m} sum_{records (i, c) of column y of M_m} pool[c] eq(x_b, i), canonical, for
+ * y < 2^n_y; zero for y >= n_wires.  eq(x_b, .): the canonical eq table of sumcheck b's own point of n_x coordinates (variable 1 =
+ * the most significant index bit, gkr_eq_table_device's order), built in context workspace under slot names of this path's own
+ * ("r1cs.cols.*").  Elements between the tables are not touched.  Exact: the order of summation is the library's.
+ * GKR_ERR_INVALID (plain returns, before a device is touched): NULL ctx, cols, x, rho or d_out; batch outside 1 .. 65535;
+ * out_stride_elements < 2^n_y; batch * 2 * 2^n_y or batch * 2^n_x above 2^30 values; cols prepared on another context.
+ * GKR_ERR_NON_CANONICAL (through the context) for an x or rho entry >= r. */
+int  gkr_r1cs_cols_device(gkr_ctx *ctx, const gkr_r1cs_cols *cols, const gkr_fr *x /* host, batch x n_x */,
+                          const gkr_fr *rho /* host, batch x 3 */, int batch, void *d_out, size_t out_stride_elements /* >= 2^n_y */);
+
+/* The tables {T_b, w_b zero-padded to 2^n_y} of every sumcheck into context workspace, laid out as the product path takes them
+ * (factor f of sumcheck b at (b * 2 + f) * 2^n_y), then that path at degree 2: the outputs are byte for byte what
+ * gkr_sumcheck_product_batch_device(.., n_y, 2, batch, ..) returns on those tables -- rows of 3 slots, its length rules, its
+ * all-[0] transcript when T is the zero table (rho = 0).  g_1(0) + g_1(1) = sum_m rho_m Mz_m~(x): with x = the zero-check's out_r,
+ * sum_m rho_m out_evals[m] of that call.  Witness b: the n_wires canonical elements at d_witness + b * stride_elements (canonical
+ * by precondition); not modified.
+ *   out_evals   batch x 2: T_b~(r_y), w_b~(r_y); or NULL
+ * GKR_ERR_INVALID as above, and for NULL d_witness, out_coeffs, out_len or out_r and stride_elements < n_wires;
+ * GKR_ERR_NON_CANONICAL as above. */
+int  gkr_r1cs_inner_batch_device(gkr_ctx *ctx, const gkr_r1cs_cols *cols, const void *d_witness, size_t stride_elements, int batch,
+                                 const gkr_fr *x /* host, batch x n_x */, const gkr_fr *rho /* host, batch x 3 */,
+                                 gkr_fr *out_coeffs /* batch x n_y rows of 3 slots */, uint32_t *out_len, gkr_fr *out_r /* batch x n_y */,
+                                 gkr_fr *out_evals /* batch x 2 or NULL */);
+
+/* A host witness of n_witness >= n_wires values: prepare + upload + the call above with batch 1 + free.  GKR_ERR_INVALID also for
+ * n_witness < n_wires; GKR_ERR_NON_CANONICAL also for a witness entry >= r. */
+int  gkr_r1cs_inner(gkr_ctx *ctx, const gkr_r1cs *r1cs, const gkr_fr *witness, size_t n_witness, const gkr_fr *x /* n_x */,
+                    const gkr_fr *rho /* 3 */, gkr_fr *out_coeffs, uint32_t *out_len, gkr_fr *out_r, gkr_fr *out_evals);
 
 /* ---- step-wise sessions: one sumcheck split across GPUs -------------------
  * The reference reduces each round's per-assignment polynomials with a rayon
