@@ -24,6 +24,8 @@ GKR_ERR_UNSUPPORTED = 7
 # verdicts of the verifiers (failed_check); 10 belongs to the plain, the product and the sum-of-products sumcheck's verifiers alone
 GKR_VERIFY_OK, GKR_VERIFY_SHAPE, GKR_VERIFY_NON_CANONICAL = 0, 1, 2
 GKR_VERIFY_ROUND_SUM, GKR_VERIFY_CHALLENGE, GKR_VERIFY_EVALUATION = 4, 5, 10
+# the R1CS verifier's own (gkr_r1cs_verify*): e_T against the public matrices, e_w against the witness
+GKR_VERIFY_MATRIX, GKR_VERIFY_WITNESS = 11, 12
 
 # rows of an R1CS matrix with more terms than this get a wave each on the device (GKR_R1CS_LONG_ROW)
 GKR_R1CS_LONG_ROW = 32
@@ -60,6 +62,7 @@ SYMBOLS = [
     "gkr_r1cs_zerocheck_batch_device", "gkr_r1cs_zerocheck",
     "gkr_r1cs_csc_info", "gkr_r1cs_csc_export", "gkr_r1cs_cols_prepare", "gkr_r1cs_cols_prepare_segment", "gkr_r1cs_cols_info", "gkr_r1cs_cols_free",
     "gkr_r1cs_cols_device", "gkr_r1cs_inner_batch_device", "gkr_r1cs_inner",
+    "gkr_r1cs_matrix_evals_device", "gkr_r1cs_verify_batch_device", "gkr_r1cs_verify",
     "gkr_wtns_parse", "gkr_wtns_serialize", "gkr_r1cs_compile", "gkr_layered_count", "gkr_layered_circuit",
     "gkr_layered_input_layer", "gkr_layered_input_values", "gkr_layered_free",
     "gkr_device_alloc", "gkr_device_free", "gkr_device_upload", "gkr_device_download",
@@ -234,6 +237,17 @@ def lib():
         # (ctx, r1cs, witness, n_witness, x, rho, out_coeffs, out_len, out_r, out_evals)
         L.gkr_r1cs_inner.restype = ctypes.c_int
         L.gkr_r1cs_inner.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_size_t] + [ctypes.c_void_p] * 6
+        # (ctx, rows, x, y, batch, out)
+        L.gkr_r1cs_matrix_evals_device.restype = ctypes.c_int
+        L.gkr_r1cs_matrix_evals_device.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_void_p]
+        # (ctx, rows, batch, z, coeffs_x, len_x, r_x, evals_abc, rho, coeffs_y, len_y, r_y, evals_tw, d_witness, stride_elements, accept,
+        #  failed_stage, failed_round, failed_check)
+        L.gkr_r1cs_verify_batch_device.restype = ctypes.c_int
+        L.gkr_r1cs_verify_batch_device.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 11 + [ctypes.c_size_t] + [ctypes.c_void_p] * 4
+        # (ctx, r1cs, z, coeffs_x, len_x, r_x, evals_abc, rho, coeffs_y, len_y, r_y, evals_tw, witness, n_witness, accept, failed_stage,
+        #  failed_round, failed_check)
+        L.gkr_r1cs_verify.restype = ctypes.c_int
+        L.gkr_r1cs_verify.argtypes = [ctypes.c_void_p] * 13 + [ctypes.c_size_t] + [ctypes.c_void_p] * 4
         L.gkr_selftest_product_geometry.restype = ctypes.c_int
         L.gkr_selftest_product_geometry.argtypes = [ctypes.c_int] * 2 + [ctypes.c_void_p] * 2
         for fn in (L.gkr_r1cs_free, L.gkr_layered_free):

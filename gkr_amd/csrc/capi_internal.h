@@ -2,7 +2,8 @@
 // memory; capi_mle.hip: the plain sumcheck's entry points, per-round schedules and sessions; capi_mle_passes.hip: its multi-round
 // schedule, whole tables and tables split over ranks; capi_layer.hip: the layer sumcheck over gate lists; capi_layer_dense.hip:
 // its dense form; capi_prove.hip: whole proofs; capi_product.hip: the sumcheck over a product of resident tables; capi_sop.hip: over a sum of
-// such products; capi_zerocheck.hip: the zero-check; capi_r1cs.hip: an R1CS's tables in front of it): the context,
+// such products; capi_zerocheck.hip: the zero-check; capi_r1cs.hip: an R1CS's tables in front of it; capi_r1cs_verify.hip: the
+// verifier of that pair of sumchecks): the context,
 // its caches and workspaces, profiling brackets, the host transcript's helpers, the hand-off wait, the plain sumcheck's group
 // hand-off.  Not a public header.
 #pragma once
@@ -33,6 +34,7 @@
 #include "mimc7.h"
 #include "mimc_adx.h"
 #include "mimc_ifma.h"
+#include "verify_rounds.h"
 
 using gkr::Fr;
 
@@ -747,6 +749,10 @@ int run_layer_dense(gkr_ctx* ctx, int batch, int k_i, int k, const uint8_t* d_gt
 // n rows of `slots` (3 or 4) right-aligned slots and their lengths, in device memory -> their slots in device memory, on stream s
 bool verify_device_hash_wanted(size_t rows);
 int verify_hash_rows_device(gkr_ctx* ctx, int slots, const uint32_t* d_rows, const uint32_t* d_len, size_t n, gkr::VerifyHashSlot* d_slots, hipStream_t s);
+// the same slot of one round vector on the calling thread: verify_rounds.h's rule with the host transcript's hash
+inline void host_hash_slot(const gkr_fr* row, uint32_t width, uint32_t len, gkr::verify::HashSlot* slot) {
+    gkr::verify::hash_slot(row, width, len, slot, [](const gkr::h64::F* v, int n) { return host_multi_hash(v, n, host_mimc_constants64()); });
+}
 // ---- defined in capi_product.hip
 // the shapes gkr_sumcheck_product* and gkr_sumcheck_product_verify* admit (batch itself, 1 .. 65535, is the caller's check)
 bool product_shape_ok(int n, int degree, int batch);
@@ -774,3 +780,36 @@ void line_restriction(const std::vector<gkr::h64::F>& vals, const std::vector<gk
 int check_circuit(gkr_ctx* ctx, const gkr_circuit_desc* c);
 
 }  // namespace gkr_host
+
+// The CSR form of an R1CS (r1cs.cpp) resident on a context's device: made and used by capi_r1cs.hip (the zero-check's tables),
+// used by capi_r1cs_verify.hip (the matrices' extensions at a point).
+struct gkr_r1cs_rows {
+    gkr_ctx* ctx = nullptr;
+    gkr_r1cs_csr_info_t info{};
+    uint32_t* row_ptr[3] = {nullptr, nullptr, nullptr};
+    uint2* terms[3] = {nullptr, nullptr, nullptr};
+    uint32_t* long_rows[3] = {nullptr, nullptr, nullptr};
+    Fr* pool_mont = nullptr;
+    size_t terms_total = 0;
+    void release() {
+        for (int m = 0; m < 3; ++m) {
+            if (row_ptr[m]) (void)hipFree(row_ptr[m]);
+            if (terms[m]) (void)hipFree(terms[m]);
+            if (long_rows[m]) (void)hipFree(long_rows[m]);
+        }
+        if (pool_mont) (void)hipFree(pool_mont);
+    }
+    gkr::R1csCsr csr() const {
+        gkr::R1csCsr c;
+        for (int m = 0; m < 3; ++m) {
+            c.row_ptr[m] = row_ptr[m];
+            c.terms[m] = terms[m];
+            c.long_rows[m] = long_rows[m];
+            c.n_long[m] = (uint32_t)info.n_long_rows[m];
+        }
+        c.pool_mont = pool_mont;
+        c.n_constraints = (uint32_t)info.n_constraints;
+        c.n = info.n;
+        return c;
+    }
+};

@@ -18,29 +18,27 @@
 //      hashes on the context's host threads.  Both fill the same slots by the same rule, so verdicts do not depend on where the
 //      hashes ran;
 //   3. meanwhile the host threads run everything that needs neither: shape, canonical checks, the round sums and the Horner
-//      steps of every transcript (pre_relations);
+//      steps of every transcript (pre_relations; verify_rounds.h holds the round relations, the R1CS verifier uses them too);
 //   4. ONE synchronisation, then per transcript the challenge comparisons and the last relation (finish).
 // The order of the checks is the reference's; a value computed from unchecked elements (a hash of a malformed row, T at a
 // non-canonical point) is never consulted: checks 1 and 2 come first.
 #include <atomic>
 
 #include "capi_internal.h"
-#include "verify_core.h"
+#include "verify_rounds.h"
 
 namespace {
 
 using gkr::h64::F;
 namespace V = gkr::verify;
 
-struct HashSlot {
-    gkr_fr h;
-    uint32_t valid;
-};
+using V::HashSlot;   // (verify_rounds.h)
+using V::Pre;
+using V::pre_relations;
 static_assert(sizeof(HashSlot) == sizeof(gkr::VerifyHashSlot) && offsetof(HashSlot, valid) == offsetof(gkr::VerifyHashSlot, valid),
               "the kernel writes the slots the relations read");
 constexpr int kRelPiece = 8, kHashPiece = 16; // transcripts / round vectors per piece of host work
-constexpr int kMaxWidth = GKR_PRODUCT_MAX_DEGREE + 1;
-static_assert(kMaxWidth == 4, "the hash kernel has rows of three and of four slots");
+static_assert(V::kMaxRowWidth == 4, "the hash kernel has rows of three and of four slots");
 
 // ONE driver for all the verifiers, parametrised by the sumcheck's term structure: a transcript's rows have D + 1 right-aligned
 // slots and it is tied to M resident tables, next to each other.  The hash kernel's rows have three slots up to D = 2 and four
@@ -76,99 +74,26 @@ Terms sop_terms(const gkr::SopTerms& ts, const gkr::SopCoeffs& cf) {
 inline size_t row_width(int degree) { return (size_t)degree + 1; }
 inline int hash_slots(int degree) { return degree <= 2 ? 3 : 4; }
 
-// what the host knows about a transcript before the hashes and the device's values are there
-struct Pre {
-    uint32_t check = 0, round = 0;   // the first failure among checks 1 and 2 (check 0: none)
-    uint32_t sum_round = 0;          // the first round whose sum check fails (n: none)
-    F last = {{0, 0, 0, 0}};         // g_n(r_n)
-    F proved = {{0, 0, 0, 0}};       // g_1(0) + g_1(1)
-};
-
-Pre pre_relations(int n, int degree, const gkr_fr* claim, const gkr_fr* coeffs, const uint32_t* len, const gkr_fr* r) {
-    const uint32_t W = (uint32_t)row_width(degree);
-    Pre p;
-    p.sum_round = (uint32_t)n;
-    for (int j = 0; j < n; ++j)
-        if (len[j] < 1 || len[j] > W) {
-            p.check = GKR_VERIFY_SHAPE;
-            p.round = (uint32_t)j;
-            return p;
-        }
-    if (claim && !V::canonical(*claim)) {
-        p.check = GKR_VERIFY_NON_CANONICAL;
-        return p;
-    }
-    for (int j = 0; j < n; ++j) {
-        bool ok = V::canonical(r[j]);
-        for (uint32_t t = W - len[j]; t < W; ++t) ok = ok && V::canonical(coeffs[W * j + t]);
-        if (!ok) {
-            p.check = GKR_VERIFY_NON_CANONICAL;
-            p.round = (uint32_t)j;
-            return p;
-        }
-    }
-    F running = claim ? V::load(*claim) : F{{0, 0, 0, 0}};
-    for (int j = 0; j < n; ++j) {
-        const gkr_fr* g = coeffs + W * j + (W - len[j]);
-        F sum = V::load(g[len[j] - 1]);                                  // g(0) + g(1) = 2 c_0 + c_1 + .. over the used slots
-        for (uint32_t t = 0; t < len[j]; ++t) sum = gkr::h64::add(sum, V::load(g[t]));
-        if (j == 0) p.proved = sum;
-        if ((j > 0 || claim) && !V::same(sum, running)) {
-            p.sum_round = (uint32_t)j;
-            return p;   // (challenges of earlier rounds are still compared: finish)
-        }
-        running = V::horner(g, (int)len[j], gkr::h64::to_mont(V::load(r[j])));
-    }
-    p.last = running;
-    return p;
-}
-
-// the host's rule for a slot -- the kernel's, restated for rows of `width` slots
-void hash_slot(const gkr_fr* row, uint32_t width, uint32_t len, HashSlot* slot) {
-    slot->valid = 0;
-    if (len < 1 || len > width) return;
-    F v[kMaxWidth];
-    for (uint32_t t = 0; t < len; ++t) {
-        if (!V::canonical(row[width - len + t])) return;
-        v[t] = V::load(row[width - len + t]);
-    }
-    const F h = host_multi_hash(v, (int)len, host_mimc_constants64());
-    memcpy(slot->h.l, h.l, 32);
-    slot->valid = 1;
-}
-
 // the verdict of one transcript from what the host found, its hash slots and the device's values T_m(r) of its T.M tables
 int finish(gkr_ctx* ctx, int n, const Terms& T, const Pre& p, const HashSlot* slots, const gkr_fr* r, const Fr* values, int* accept,
            uint32_t* failed_round, uint32_t* failed_check) {
-    uint32_t check = p.check, round = p.round;
+    uint32_t check = 0, round = 0;
+    if (!V::round_verdict(n, p, slots, r, &check, &round)) return ctx->fail(GKR_ERR_HIP, "sumcheck verifier: no hash for a well-formed round vector");
     if (!check) {
-        for (uint32_t j = 0; j < (uint32_t)n && j < p.sum_round && !check; ++j) {
-            if (!slots[j].valid) return ctx->fail(GKR_ERR_HIP, "sumcheck verifier: no hash for a well-formed round vector");
-            if (memcmp(slots[j].h.l, r[j].l, 32) != 0) {
-                check = GKR_VERIFY_CHALLENGE;
-                round = j;
+        F total = {{0, 0, 0, 0}};                                    // sum_k c_k prod_j T_t(k,j)(r)
+        for (int k = 0; k < T.K; ++k) {
+            const uint32_t d = T.term[k] & 0xFFu;
+            F prod = T.coeff[k];                                     // Montgomery, then canonical: a b = mont_mul(to_mont(a), b)
+            for (uint32_t j = 0; j < d; ++j) {
+                F v;
+                memcpy(v.l, &values[(T.term[k] >> (8u + 8u * j)) & 0xFFu], 32);
+                prod = gkr::h64::mont_mul(j ? gkr::h64::to_mont(prod) : prod, v);
             }
+            total = gkr::h64::add(total, prod);
         }
-        if (!check && p.sum_round < (uint32_t)n) {
-            check = GKR_VERIFY_ROUND_SUM;
-            round = p.sum_round;
-        }
-        if (!check) {
-            F total = {{0, 0, 0, 0}};                                    // sum_k c_k prod_j T_t(k,j)(r)
-            for (int k = 0; k < T.K; ++k) {
-                const uint32_t d = T.term[k] & 0xFFu;
-                F prod = T.coeff[k];                                     // Montgomery, then canonical: a b = mont_mul(to_mont(a), b)
-                for (uint32_t j = 0; j < d; ++j) {
-                    F v;
-                    memcpy(v.l, &values[(T.term[k] >> (8u + 8u * j)) & 0xFFu], 32);
-                    prod = gkr::h64::mont_mul(j ? gkr::h64::to_mont(prod) : prod, v);
-                }
-                total = gkr::h64::add(total, prod);
-            }
-            if (!V::same(p.last, total)) {
-                check = GKR_VERIFY_EVALUATION;
-                round = (uint32_t)n;
-            }
+        if (!V::same(p.last, total)) {
+            check = GKR_VERIFY_EVALUATION;
+            round = (uint32_t)n;
         }
     }
     *accept = check == 0 ? 1 : 0;
@@ -240,7 +165,7 @@ int verify_chunk(gkr_ctx* ctx, const Fr* d_tables, int n, const Terms& T, uint32
         const size_t a = next.fetch_add(1, std::memory_order_relaxed);
         if (a < hash_pieces) {   // (the hashes first: they are the long pieces)
             for (size_t s = a * kHashPiece; s < std::min(n_rows, (a + 1) * kHashPiece); ++s)
-                hash_slot(coeffs + W * s, (uint32_t)W, len[s], &host_slots[s]);
+                host_hash_slot(coeffs + W * s, (uint32_t)W, len[s], &host_slots[s]);
             return true;
         }
         if (a < hash_pieces + rel_pieces) {

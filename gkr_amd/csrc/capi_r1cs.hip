@@ -8,36 +8,7 @@
 static_assert(sizeof(gkr_r1cs_term) == sizeof(uint2), "a record is eight bytes: {wire, pool index}");
 static_assert(gkr::kR1csLongRow == GKR_R1CS_LONG_ROW, "the kernels and the host's long-row lists cut at the same length");
 
-struct gkr_r1cs_rows {
-    gkr_ctx* ctx = nullptr;
-    gkr_r1cs_csr_info_t info{};
-    uint32_t* row_ptr[3] = {nullptr, nullptr, nullptr};
-    uint2* terms[3] = {nullptr, nullptr, nullptr};
-    uint32_t* long_rows[3] = {nullptr, nullptr, nullptr};
-    Fr* pool_mont = nullptr;
-    size_t terms_total = 0;
-    void release() {
-        for (int m = 0; m < 3; ++m) {
-            if (row_ptr[m]) (void)hipFree(row_ptr[m]);
-            if (terms[m]) (void)hipFree(terms[m]);
-            if (long_rows[m]) (void)hipFree(long_rows[m]);
-        }
-        if (pool_mont) (void)hipFree(pool_mont);
-    }
-    gkr::R1csCsr csr() const {
-        gkr::R1csCsr c;
-        for (int m = 0; m < 3; ++m) {
-            c.row_ptr[m] = row_ptr[m];
-            c.terms[m] = terms[m];
-            c.long_rows[m] = long_rows[m];
-            c.n_long[m] = (uint32_t)info.n_long_rows[m];
-        }
-        c.pool_mont = pool_mont;
-        c.n_constraints = (uint32_t)info.n_constraints;
-        c.n = info.n;
-        return c;
-    }
-};
+// (struct gkr_r1cs_rows, the CSR form resident: capi_internal.h -- the verifier's translation unit reads it too)
 
 static_assert(gkr::kR1csLongCol == GKR_R1CS_LONG_COL, "the kernels and the host's long-column lists cut at the same length");
 static_assert(gkr::kR1csColSegment == GKR_R1CS_COL_SEGMENT, "the header names the kernels' segment length");

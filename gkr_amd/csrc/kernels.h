@@ -526,6 +526,16 @@ void launch_r1cs_cols(const R1csCsc& csc, const Fr* eq, uint32_t n_x, const Fr* 
 void launch_r1cs_pad_witness(const Fr* witness, size_t witness_stride, uint32_t n_wires, uint32_t n_y, uint32_t batch, Fr* dst,
                              size_t dst_stride, hipStream_t s);
 
+// ---- the R1CS verifier's last relation (kernels_r1cs.hip) --------------------------------------------------------------------------
+// out[b * 3 + m] = M_m~(x_b, y_b) = sum over the records (row i, wire w, coefficient c) of matrix m of c eq(x_b, i) eq(y_b, w),
+// canonical, from the resident CSR form in one pass: ex_mont = batch tables eq(x_b, .) of 2^n entries in MONTGOMERY form, ey =
+// batch tables eq(y_b, .) of 2^n_y >= n_wires entries, canonical (launch_eq_table's two forms).  partials: batch * 3 *
+// r1cs_matrix_eval_slots(csr) elements of scratch, every one written before it is read.  Three launches in stream order (two
+// where no matrix has a long row): a thread per row, a wave per long row, a block per (matrix, proof).
+uint32_t r1cs_matrix_eval_slots(const R1csCsr& csr);
+void launch_r1cs_matrix_evals(const R1csCsr& csr, const Fr* ex_mont, const Fr* ey, uint32_t n_y, uint32_t batch, Fr* partials, Fr* out,
+                              hipStream_t s);
+
 uint32_t layer_blocks(uint32_t h);
 void launch_layer_round(const Fr* A, const Fr* M, uint32_t h, uint32_t k, uint32_t phase, uint32_t hb, const Fr* Wb,
                         const Fr* Wc, uint32_t nblk, LayerPartial* partials, LayerBatch lb, hipStream_t s);

@@ -1,6 +1,8 @@
 // CDNA4 (gfx950) kernels of the R1CS zero-check's tables (gkr_r1cs_rows_device): Az, Bz, Cz of a witness as sparse matrix-vector
 // products over BN254 Fr, and the row-wise check a * b == c; and of the R1CS inner sumcheck's table (gkr_r1cs_cols_device): the
-// same records gathered by COLUMN against the eq table of a point (the second half of this file).
+// same records gathered by COLUMN against the eq table of a point (the second half of this file); and of the verifier's last
+// relation (gkr_r1cs_matrix_evals_device): the three matrices' multilinear extensions at a point, one pass over the CSR records
+// (the last part).
 //
 //   out[(b * 3 + m) * 2^n + i] = sum_t pool[coeff_t] * w_b[wire_t]   over the records of row i of matrix m, canonical;
 //   rows >= n_constraints are zero.
@@ -217,8 +219,90 @@ __global__ void __launch_bounds__(256) k_r1cs_pad_witness(const Fr* __restrict__
 }
 
 // ---------------------------------------------------------------------------
+// the matrices' extensions at a point: M_m~(x, y) = sum_{records (i, w, c) of M_m} pool[c] eq(x, i) eq(y, w)
+// ---------------------------------------------------------------------------
+// The rows kernels once more with ey = eq(y, .) (canonical, 2^n_y entries) as the gathered vector -- r1cs_term's arithmetic and
+// term bounds unchanged -- but a row's sum s_i is not stored: it is multiplied by ex[i] = eq(x, i) (MONTGOMERY form, so that
+// mont_mul(ex[i], s_i) is the canonical product) and added to an Acc<9>.  Bound: a partial is a sum of canonical values below
+// r < 2^254, an Acc<9> holds 288 bits: 2^34 of them, more than the 2^30 rows a table can have.  Nothing of 2^n entries is written;
+// the padding rows i >= n_constraints take no thread.  Slots of (matrix m, proof b), `slots` = short blocks + long blocks apart:
+// [0, short blocks) the blocks of k_r1cs_mat_short, behind them one per block of k_r1cs_mat_long.  Every slot is written by the
+// block that owns it, on every launch: no atomics, no memset.
+
+// One thread per row below n_constraints; rows with more than kR1csLongRow records are left to k_r1cs_mat_long, an empty row
+// takes neither the reduction nor the product.  One canonical partial per block.
+// grid = (ceil(n_constraints / 256), 3, batch)
+__global__ void __launch_bounds__(256) k_r1cs_mat_short(const R1csCsr csr, const Fr* __restrict__ ex_mont, const Fr* __restrict__ ey, uint32_t n_y,
+                                                        Fr* __restrict__ partials, uint32_t slots) {
+    __shared__ Acc<9> s_acc[4];
+    const uint32_t m = blockIdx.y, row = blockIdx.x * 256u + threadIdx.x;
+    Acc<9> sum[1] = {acc_zero<9>()};
+    if (row < csr.n_constraints) {
+        const uint32_t* __restrict__ rp = pick3(csr.row_ptr, m);
+        const uint32_t begin = rp[row], end = rp[row + 1];
+        if (begin != end && end - begin <= kR1csLongRow) {
+            const uint2* __restrict__ terms = pick3(csr.terms, m);
+            const Fr* e = ey + ((size_t)blockIdx.z << n_y);
+            Lazy17 acc = lazy_zero();
+            for (uint32_t t = begin; t < end; ++t) r1cs_term(acc, terms[t], e, csr.pool_mont);
+            acc_add_fr(sum[0], mont_mul(load_fr(ex_mont + ((size_t)blockIdx.z << csr.n) + row), lazy_reduce(acc)));
+        }
+    }
+    block_sum<9, 1>(sum, s_acc);
+    if (threadIdx.x == 0) store_fr(partials + ((size_t)blockIdx.z * 3 + m) * slots + blockIdx.x, acc_reduce(sum[0]));
+}
+
+// One wave per long row, the loop of k_r1cs_rows_long; lane 0 multiplies the row's sum by ex[row].  A matrix with fewer long rows
+// than the grid is wide has its surplus blocks store zero: the sum kernel reads every slot.
+// grid = (the largest number of long rows of a matrix, 3, batch), block = 64
+__global__ void __launch_bounds__(64) k_r1cs_mat_long(const R1csCsr csr, const Fr* __restrict__ ex_mont, const Fr* __restrict__ ey, uint32_t n_y,
+                                                      Fr* __restrict__ partials, uint32_t slots, uint32_t first_slot) {
+    const uint32_t m = blockIdx.y;
+    Fr* dst = partials + ((size_t)blockIdx.z * 3 + m) * slots + first_slot + blockIdx.x;
+    if (blockIdx.x >= pick3(csr.n_long, m)) {   // (block-uniform: before any shuffle)
+        if (threadIdx.x == 0) store_fr(dst, fr_zero());
+        return;
+    }
+    const uint32_t* __restrict__ rp = pick3(csr.row_ptr, m);
+    const uint2* __restrict__ terms = pick3(csr.terms, m);
+    const uint32_t row = pick3(csr.long_rows, m)[blockIdx.x];
+    const uint32_t begin = rp[row], end = rp[row + 1];
+    const Fr* e = ey + ((size_t)blockIdx.z << n_y);
+    Lazy17 acc = lazy_zero();
+    for (uint64_t t = (uint64_t)begin + threadIdx.x; t < end; t += 64u) r1cs_term(acc, terms[t], e, csr.pool_mont);   // (64 bits: begin + 63 may pass 2^32)
+    Acc<9> sum = acc_zero<9>();
+    acc_add_fr(sum, lazy_reduce(acc));
+    sum = wave_sum(sum);
+    if (threadIdx.x == 0) store_fr(dst, mont_mul(load_fr(ex_mont + ((size_t)blockIdx.z << csr.n) + row), acc_reduce(sum)));
+}
+
+// out[b * 3 + m] = the sum of the pair's slots, canonical
+// grid = (3, batch), block = 256
+__global__ void __launch_bounds__(256) k_r1cs_mat_sum(const Fr* __restrict__ partials, uint32_t slots, Fr* __restrict__ out) {
+    __shared__ Acc<9> s_acc[4];
+    const size_t pair = (size_t)blockIdx.y * 3 + blockIdx.x;
+    const Fr* p = partials + pair * slots;
+    Acc<9> sum[1] = {acc_zero<9>()};
+    for (uint32_t i = threadIdx.x; i < slots; i += 256u) acc_add_fr(sum[0], load_fr(p + i));
+    block_sum<9, 1>(sum, s_acc);
+    if (threadIdx.x == 0) store_fr(out + pair, acc_reduce(sum[0]));
+}
+
+// ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
+
+uint32_t r1cs_matrix_eval_slots(const R1csCsr& csr) {
+    return (csr.n_constraints + 255u) / 256u + std::max(csr.n_long[0], std::max(csr.n_long[1], csr.n_long[2]));
+}
+
+void launch_r1cs_matrix_evals(const R1csCsr& csr, const Fr* ex_mont, const Fr* ey, uint32_t n_y, uint32_t batch, Fr* partials, Fr* out,
+                              hipStream_t s) {
+    const uint32_t blocks = (csr.n_constraints + 255u) / 256u, slots = r1cs_matrix_eval_slots(csr), max_long = slots - blocks;
+    hipLaunchKernelGGL(k_r1cs_mat_short, dim3(blocks, 3, batch), dim3(256), 0, s, csr, ex_mont, ey, n_y, partials, slots);
+    if (max_long) hipLaunchKernelGGL(k_r1cs_mat_long, dim3(max_long, 3, batch), dim3(64), 0, s, csr, ex_mont, ey, n_y, partials, slots, blocks);
+    hipLaunchKernelGGL(k_r1cs_mat_sum, dim3(3, batch), dim3(256), 0, s, partials, slots, out);
+}
 
 void launch_r1cs_rows(const R1csCsr& csr, const Fr* witness, size_t witness_stride, uint32_t batch, Fr* out, hipStream_t s) {
     const uint32_t blocks = (uint32_t)((((size_t)1 << csr.n) + 255) / 256);

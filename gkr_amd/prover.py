@@ -701,6 +701,80 @@ class Context:
         self._check(N.lib().gkr_r1cs_inner(self._h, r1cs._h, _ptr(wl), wl.shape[0], _ptr(pts), _ptr(rh), _ptr(C), _ptr(L), _ptr(R), _ptr(E)))
         return [from_limbs(C[j])[3 - int(L[j]):] for j in range(n_y)], from_limbs(R), from_limbs(E)
 
+    # -- the R1CS verifier: the two transcripts against z, rho, the public matrices and, where there is one, the witness
+    @staticmethod
+    def _n_y(rows_info):
+        """n_y = max(2, ceil(log2 n_wires)) from a rows handle's info (the CSC info's rule)."""
+        return max(2, (rows_info["n_wires"] - 1).bit_length())
+
+    def r1cs_matrix_evals_device(self, rows, xs, ys):
+        """gkr_r1cs_matrix_evals_device: [A~, B~, C~](x_b, y_b) of the R1CS behind `rows` for a batch of points, one pass over its
+        non-zeros on the device.  xs: (batch, n, 4) limbs or `batch` lists of n integers; ys: the same with n_y coordinates.
+        -> (batch, 3, 4) uint64 limbs, value for value verifier.r1cs_matrix_evals(constraints, x_b, y_b)."""
+        inf = rows.info()
+        batch = len(xs)
+        px, py = self._points(xs, batch, inf["n"]), self._points(ys, batch, self._n_y(inf))
+        out = np.zeros((batch, 3, 4), dtype=np.uint64)
+        self._check(N.lib().gkr_r1cs_matrix_evals_device(self._h, rows._h, _ptr(px), _ptr(py), batch, _ptr(out)))
+        return out
+
+    def verify_r1cs_batch_device(self, rows, batch, z, zerocheck, rho, inner, d_witness=None, stride=None):
+        """gkr_r1cs_verify_batch_device: `batch` proofs of the two R1CS sumchecks against the R1CS behind `rows`.  z: (batch, n, 4)
+        limbs or `batch` lists of n integers; zerocheck = (C, L, R, E) as r1cs_zerocheck_batch_device returns them (its first four
+        arrays); rho: (batch, 3, 4) limbs or `batch` triples; inner = (C, L, R, E) as r1cs_inner_batch_device returns them.
+        d_witness: None, or the resident witnesses (witness b at d_witness + b * stride elements; None: n_wires) -- without one the
+        claim (r_y, e_w) on the witness is left to the caller.  -> (accept, failed_stage, failed_round, failed_check), (batch,)
+        arrays; verifier.verify_r1cs is the same verdict on plain integers."""
+        inf = rows.info()
+        n, n_y = inf["n"], self._n_y(inf)
+        pts, rh = self._points(z, batch, n), self._rho(rho, batch)
+        CX, LX, RX, EX = (np.ascontiguousarray(a) for a in zerocheck)
+        CY, LY, RY, EY = (np.ascontiguousarray(a) for a in inner)
+        want = [(CX, (batch, n, 4, 4), np.uint64), (LX, (batch, n), np.uint32), (RX, (batch, n, 4), np.uint64), (EX, (batch, 3, 4), np.uint64),
+                (CY, (batch, n_y, 3, 4), np.uint64), (LY, (batch, n_y), np.uint32), (RY, (batch, n_y, 4), np.uint64), (EY, (batch, 2, 4), np.uint64)]
+        if any(a.shape != shape or a.dtype != dtype for a, shape, dtype in want):
+            raise GkrError(N.GKR_ERR_INVALID, "transcript arrays do not match (batch, n, n_y)")
+        accept = np.zeros(batch, dtype=np.int32)
+        stage, rnd, check = (np.zeros(batch, dtype=np.uint32) for _ in range(3))
+        self._check(N.lib().gkr_r1cs_verify_batch_device(self._h, rows._h, batch, _ptr(pts), _ptr(CX), _ptr(LX), _ptr(RX), _ptr(EX), _ptr(rh), _ptr(CY),
+                                                         _ptr(LY), _ptr(RY), _ptr(EY), d_witness,
+                                                         (inf["n_wires"] if stride is None else int(stride)) if d_witness else 0, _ptr(accept),
+                                                         _ptr(stage), _ptr(rnd), _ptr(check)))
+        return accept, stage, rnd, check
+
+    def verify_r1cs(self, r1cs, z, rho, proof_x, proof_y, witness=None):
+        """gkr_r1cs_verify: one proof against `r1cs` (convert.R1cs) and, where given, a host witness (at least n_wires integers, or
+        (count, 4) limbs).  z: n integers; rho: three; proof_x = (proof, r, evals) of prove_r1cs_zerocheck (its first three
+        results); proof_y = (proof, r, evals) of prove_r1cs_inner.  -> (stage, round, check), (0, 0, 0) for an accepted proof:
+        verifier.verify_r1cs's verdict."""
+        inf = r1cs.csr_info()
+        n, n_y = inf["n"], self._n_y(inf)
+
+        def rows_of(proof, width, count):
+            if len(proof) != count:
+                raise GkrError(N.GKR_ERR_INVALID, "a transcript has one round vector per variable")
+            C, L = np.zeros((count, width, 4), dtype=np.uint64), np.zeros(count, dtype=np.uint32)
+            for j, g in enumerate(proof):
+                L[j] = len(g)
+                if 1 <= len(g) <= width:                                   # (another length: SHAPE, the slots are not read)
+                    C[j, width - len(g):] = to_limbs([int(c) for c in g])
+            return C, L
+        (gx, rx, ex), (gy, ry, ey) = proof_x, proof_y
+        CX, LX = rows_of(gx, 4, n)
+        CY, LY = rows_of(gy, 3, n_y)
+        RX, EX, RY, EY = to_limbs(list(rx)), to_limbs(list(ex)), to_limbs(list(ry)), to_limbs(list(ey))
+        if RX.shape != (n, 4) or EX.shape != (3, 4) or RY.shape != (n_y, 4) or EY.shape != (2, 4):
+            raise GkrError(N.GKR_ERR_INVALID, "n and n_y challenges, three and two evaluations expected")
+        pts = self._points(z if isinstance(z, np.ndarray) else [z], 1, n)
+        rh = self._rho(rho if isinstance(rho, np.ndarray) else [rho], 1)
+        wl = None if witness is None else as_limbs(witness)
+        accept = np.zeros(1, dtype=np.int32)
+        stage, rnd, check = (np.zeros(1, dtype=np.uint32) for _ in range(3))
+        self._check(N.lib().gkr_r1cs_verify(self._h, r1cs._h, _ptr(pts), _ptr(CX), _ptr(LX), _ptr(RX), _ptr(EX), _ptr(rh), _ptr(CY), _ptr(LY),
+                                            _ptr(RY), _ptr(EY), None if wl is None else _ptr(wl), 0 if wl is None else wl.shape[0],
+                                            _ptr(accept), _ptr(stage), _ptr(rnd), _ptr(check)))
+        return int(stage[0]), int(rnd[0]), int(check[0])
+
     # -- the plain sumcheck's verifier (verify_sumcheck, python/sumcheck.py:55-70, plus g_n(r_n) = T(r)) and the evaluation behind it
     def mle_eval_batch_device(self, d_tables, n, batch, points):
         """gkr_mle_eval_batch_device: the multilinear extension of each of `batch` resident tables of 2^n entries at its own point.

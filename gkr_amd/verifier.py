@@ -12,6 +12,7 @@ end-to-end check of a proof that needs neither the CPU checker under tests/ nor 
 
 from typing import List
 
+from . import _native as N
 from .field import MODULUS as P
 from .prover import GKRCircuit, Proof, multi_hash
 
@@ -230,6 +231,93 @@ def verify_r1cs_inner(constraints, rx: List[int], rho: List[int], claims_abc: Li
     if evals[0] % P != sum(r * v for r, v in zip(rho, mats)) % P:
         return None
     return ry, evals[1] % P
+
+
+def _transcript_form(rounds: List[List[int]], challenges: List[int], width: int, evals: List[int]):
+    """The checks of a transcript that read no relation, in the device verifiers' order: (round, check) of the first round vector
+    whose length is outside 1 .. width (SHAPE), else of the first round with a coefficient or a challenge outside 0 .. r - 1
+    (NON_CANONICAL), else (len(rounds), NON_CANONICAL) for such an evaluation; None when there is none."""
+    for j, g in enumerate(rounds):
+        if not 1 <= len(g) <= width:
+            return j, N.GKR_VERIFY_SHAPE
+    for j, (g, r) in enumerate(zip(rounds, challenges)):
+        if any(not 0 <= c < P for c in g) or not 0 <= r < P:
+            return j, N.GKR_VERIFY_NON_CANONICAL
+    if any(not 0 <= e < P for e in evals):
+        return len(rounds), N.GKR_VERIFY_NON_CANONICAL
+    return None
+
+
+def _transcript_rounds(rounds: List[List[int]], challenges: List[int], claim: int):
+    """python/sumcheck.py:55-70 round by round on a transcript that passed _transcript_form: -> ((round, check) of the first
+    failure -- ROUND_SUM before CHALLENGE within a round -- or None, the final claim g_n(r_n))."""
+    expected = claim % P
+    for j, (g, r) in enumerate(zip(rounds, challenges)):
+        if (eval_univariate(g, 0) + eval_univariate(g, 1)) % P != expected:
+            return (j, N.GKR_VERIFY_ROUND_SUM), expected
+        if multi_hash(g, 0) != r:
+            return (j, N.GKR_VERIFY_CHALLENGE), expected
+        expected = eval_univariate(g, r)
+    return None, expected
+
+
+def verify_r1cs(constraints, z: List[int], rho: List[int], zc_rounds: List[List[int]], r_x: List[int], evals_abc: List[int],
+                in_rounds: List[List[int]], r_y: List[int], evals_tw: List[int], witness=None):
+    """The verifier of the R1CS zero-check and inner sumcheck, tied together, on plain integers: what
+    Context.verify_r1cs_batch_device decides on the device.  constraints: R1cs.constraints(); z, rho: the verifier's own point
+    and weights (reduced modulo r); zc_rounds, r_x, evals_abc: the zero-check's transcript, challenges and [v_A, v_B, v_C];
+    in_rounds, r_y, evals_tw: the inner sumcheck's and [e_T, e_w]; witness: None or the n_wires values (at most 2^n_y).  Proof elements
+    are taken as they are: one outside 0 .. r - 1 is NON_CANONICAL.  -> (stage, round, check) of the first failure, (0, 0, 0) for
+    an accepted proof:
+      stage 1  verify_sumcheck_zerocheck's relations with R1CS_ZEROCHECK_TERMS and claim 0: SHAPE (rows of 1 .. 4), NON_CANONICAL
+               (a round's coefficients and challenge; evals_abc at round n), per round ROUND_SUM then CHALLENGE, EVALUATION (round n)
+               for g_n(r_n) != eq(z, r_x) (v_A v_B - v_C);
+      stage 2  verify_r1cs_inner's transcript part: the same on rows of 1 .. 3 with claim sum_m rho_m v_m, evals_tw at round n_y,
+               EVALUATION (round n_y) for g(r) != e_T e_w;
+      stage 3  MATRIX (round n_y): e_T != sum_m rho_m M_m~(r_x, r_y) (r1cs_matrix_evals);
+      stage 4  with a witness, WITNESS (round n_y): e_w != w~(r_y), the witness zero-padded to 2^n_y values.
+    Without a witness the claim (r_y, e_w) is the caller's to settle, as with verify_r1cs_inner."""
+    n, n_y = len(z), len(r_y)
+    if len(rho) != 3 or len(evals_abc) != 3 or len(evals_tw) != 2 or len(zc_rounds) != n or len(r_x) != n or len(in_rounds) != n_y or n < 1 or n_y < 1:
+        raise ValueError("n round vectors and challenges with three evaluations, n_y with two, three weights expected")
+    z, rho = [v % P for v in z], [v % P for v in rho]
+    # stage 1
+    bad = _transcript_form(zc_rounds, r_x, 4, evals_abc)
+    if bad is None:
+        bad, last = _transcript_rounds(zc_rounds, r_x, 0)
+    if bad is None:
+        total = 0
+        for c, idx in R1CS_ZEROCHECK_TERMS:
+            prod = c
+            for i in idx:
+                prod = prod * evals_abc[i] % P
+            total = (total + prod) % P
+        eq_r = 1
+        for zj, rj in zip(z, r_x):
+            eq_r = eq_r * (zj * rj + (1 - zj) * (1 - rj)) % P
+        if last != eq_r * total % P:
+            bad = (n, N.GKR_VERIFY_EVALUATION)
+    if bad is not None:
+        return (1,) + bad
+    # stage 2
+    bad = _transcript_form(in_rounds, r_y, 3, evals_tw)
+    if bad is None:
+        bad, last = _transcript_rounds(in_rounds, r_y, sum(r * v for r, v in zip(rho, evals_abc)))
+    if bad is None and last != evals_tw[0] * evals_tw[1] % P:
+        bad = (n_y, N.GKR_VERIFY_EVALUATION)
+    if bad is not None:
+        return (2,) + bad
+    # stage 3
+    if evals_tw[0] != sum(r * v for r, v in zip(rho, r1cs_matrix_evals(constraints, r_x, r_y))) % P:
+        return 3, n_y, N.GKR_VERIFY_MATRIX
+    # stage 4
+    if witness is not None:
+        w = [int(v) % P for v in witness]
+        if len(w) > 1 << n_y:
+            raise ValueError("a witness of at most 2^n_y values expected")
+        if evals_tw[1] != mle_eval(w + [0] * ((1 << n_y) - len(w)), r_y):
+            return 4, n_y, N.GKR_VERIFY_WITNESS
+    return 0, 0, 0
 
 
 def verify(proof: Proof, circuit: GKRCircuit) -> bool:

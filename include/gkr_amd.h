@@ -803,8 +803,11 @@ enum {
     GKR_VERIFY_R_STAR = 7,         /* r* != multi_hash(last round vector) */
     GKR_VERIFY_NEXT_Z = 8,         /* z[i+1] != b* + r* (c* - b*) */
     GKR_VERIFY_INPUT = 9,          /* q(r*) of the last layer != input_func(z[L]) */
-    GKR_VERIFY_EVALUATION = 10     /* plain, product and sum-of-products sumcheck (gkr_sumcheck_*_verify*): g_n(r_n) != the tables'
-                                      values at r combined as the sumcheck combines them: T~(r), prod_f T_f~(r), sum_k c_k prod_j T_t(k,j)~(r) */
+    GKR_VERIFY_EVALUATION = 10,    /* plain, product and sum-of-products sumcheck (gkr_sumcheck_*_verify*): g_n(r_n) != the tables'
+                                      values at r combined as the sumcheck combines them: T~(r), prod_f T_f~(r), sum_k c_k prod_j T_t(k,j)~(r);
+                                      gkr_r1cs_verify*: g_n(r_n) != the transcript's own evaluations combined */
+    GKR_VERIFY_MATRIX = 11,        /* gkr_r1cs_verify*: e_T != sum_m rho_m M_m~(r_x, r_y) from the public matrices */
+    GKR_VERIFY_WITNESS = 12        /* gkr_r1cs_verify* with a witness: e_w != w~(r_y) */
 };
 int  gkr_verify(const gkr_circuit_desc *circuit, const gkr_proof_buf *proof, int threads, int *accept, uint32_t *failed_layer,
                 uint32_t *failed_check);
@@ -1056,6 +1059,65 @@ int  gkr_r1cs_inner_batch_device(gkr_ctx *ctx, const gkr_r1cs_cols *cols, const 
  * n_witness < n_wires; GKR_ERR_NON_CANONICAL also for a witness entry >= r. */
 int  gkr_r1cs_inner(gkr_ctx *ctx, const gkr_r1cs *r1cs, const gkr_fr *witness, size_t n_witness, const gkr_fr *x /* n_x */,
                     const gkr_fr *rho /* 3 */, gkr_fr *out_coeffs, uint32_t *out_len, gkr_fr *out_r, gkr_fr *out_evals);
+
+/* ---- R1CS verifier: the two transcripts above against z, rho and the public matrices --------------------------
+ * A verifier of the two calls holds no table: it has the matrices, its own z and rho, and the proof.  What ties the proof to the
+ * R1CS is T~(r_y) = sum_m rho_m M_m~(r_x, r_y) with
+ *     M_m~(x, y) = sum over the records (row i, wire w, coefficient c) of matrix m of  c eq(x, i) eq(y, w),
+ * one pass over the non-zeros: the CSR form of the rows handle, eq(x, .) and eq(y, .) as tables of 2^n and 2^n_y entries in context
+ * workspace (slot names of this path's own, "r1cs.mat.*"), nothing else of 2^n entries written, the padding rows never visited.
+ * n_y = max(2, ceil(log2 n_wires)), the CSC info's rule, from the handle's n_wires.
+ *
+ * out[b * 3 + m] = M_m~(x_b, y_b), canonical; variable 1 = the most significant index bit on both sides.  A boolean (x, y) gives
+ * the sum of the coefficients at that (row, wire): zero for a row >= n_constraints or a wire >= n_wires.  Equal, value for value,
+ * to gkr_eq_table_device(y) -> gkr_r1cs_rows_device (that table as the witness) -> gkr_mle_eval_batch_device(x).
+ * GKR_ERR_INVALID before a device or the context is touched (plain returns): NULL pointer; batch outside 1 .. 65535; rows
+ * prepared on another context; n or n_y above 28; batch * (2^n + 2^n_y) above 2^30 values.  GKR_ERR_NON_CANONICAL (through the
+ * context) for a coordinate >= r.  Processed in chunks of verify_workspace_mb of device workspace. */
+int  gkr_r1cs_matrix_evals_device(gkr_ctx *ctx, const gkr_r1cs_rows *rows, const gkr_fr *x /* host, batch x n */,
+                                  const gkr_fr *y /* host, batch x n_y */, int batch, gkr_fr *out /* host, batch x 3 */);
+
+/* Verifier of gkr_r1cs_zerocheck_batch_device's and gkr_r1cs_inner_batch_device's transcripts, tied together.  Per proof b:
+ *   z          n elements, the zero-check's point                          rho        3 elements, the inner call's weights
+ *   coeffs_x   n rows of 4 slots, len_x, r_x: the zero-check's outputs     evals_abc  3 elements, its out_evals (v_A, v_B, v_C)
+ *   coeffs_y   n_y rows of 3 slots, len_y, r_y: the inner call's outputs   evals_tw   2 elements, its out_evals (e_T, e_w)
+ * all in host memory, batch of each one after the other.  d_witness: NULL, or witness b's n_wires canonical elements at
+ * d_witness + b * stride_elements in device memory (not modified).
+ * accept[batch] required; failed_stage / failed_round / failed_check (batch each) may be NULL.  The first failure in this order
+ * (failed_stage 1 .. 4, 0 for an accepted proof; failed_check: the GKR_VERIFY_* values):
+ *   stage 1, the zero-check's transcript (degree 3):
+ *     GKR_VERIFY_SHAPE          some len_x[j] outside 1 .. 4; failed_round = the first such j
+ *     GKR_VERIFY_NON_CANONICAL  a used slot or r_x[j] >= r: failed_round = the first such j; an evals_abc entry: failed_round = n
+ *     for j = 0 .. n-1:  GKR_VERIFY_ROUND_SUM  g_j(0) + g_j(1) != the running claim, which starts at ZERO;
+ *                        GKR_VERIFY_CHALLENGE  r_x[j] != multi_hash(used slots of row j, key 0)
+ *     GKR_VERIFY_EVALUATION     g_n(r_n) != eq(z, r_x) (v_A v_B - v_C), eq(z, r_x) the product of n factors; failed_round = n
+ *   stage 2, the inner transcript (degree 2): the same checks on rows of 3 slots, the running claim starting at sum_m rho_m v_m,
+ *     NON_CANONICAL also for an evals_tw entry (failed_round = n_y), EVALUATION for g(r) != e_T e_w (failed_round = n_y)
+ *   stage 3  GKR_VERIFY_MATRIX  e_T != sum_m rho_m M_m~(r_x, r_y), the three values from the call above's kernels; failed_round = n_y
+ *   stage 4  GKR_VERIFY_WITNESS only with d_witness: e_w != w~(r_y), the witness zero-padded to 2^n_y entries and evaluated on the
+ *            device; failed_round = n_y
+ * With d_witness == NULL the claim (r_y, e_w) on the witness is the CALLER's to settle: this library has no commitment to a
+ * witness, and an accepted proof then says "IF w~(r_y) = e_w".  A proof that fails SHAPE or NON_CANONICAL in either transcript
+ * never sends its point to the device: its slot is evaluated at zeros and its verdict is decided without that value.
+ * z and rho are the verifier's own inputs: an entry >= r is GKR_ERR_NON_CANONICAL for the whole call (through the context), not a
+ * verdict.  The return value is the status of the CALL, not the verdict.  GKR_ERR_INVALID (plain returns): what
+ * gkr_r1cs_matrix_evals_device refuses, NULL for any required array, stride_elements < n_wires when a witness is given.
+ * The round relations run on the context's host threads; both transcripts' round vectors are hashed on the device from
+ * verify_device_hash_min of them per chunk on, on the host threads below; chunks of verify_workspace_mb.  Verdicts depend on
+ * neither option. */
+int  gkr_r1cs_verify_batch_device(gkr_ctx *ctx, const gkr_r1cs_rows *rows, int batch, const gkr_fr *z /* batch x n */,
+                                  const gkr_fr *coeffs_x /* batch x n rows of 4 slots */, const uint32_t *len_x, const gkr_fr *r_x,
+                                  const gkr_fr *evals_abc /* batch x 3 */, const gkr_fr *rho /* batch x 3 */,
+                                  const gkr_fr *coeffs_y /* batch x n_y rows of 3 slots */, const uint32_t *len_y, const gkr_fr *r_y,
+                                  const gkr_fr *evals_tw /* batch x 2 */, const void *d_witness /* or NULL */, size_t stride_elements,
+                                  int *accept, uint32_t *failed_stage, uint32_t *failed_round, uint32_t *failed_check);
+
+/* A host gkr_r1cs and an optional host witness of n_witness >= n_wires values (NULL: none): prepare + upload + the call above
+ * with batch 1 + free.  GKR_ERR_INVALID also for n_witness < n_wires; GKR_ERR_NON_CANONICAL also for a witness entry >= r. */
+int  gkr_r1cs_verify(gkr_ctx *ctx, const gkr_r1cs *r1cs, const gkr_fr *z, const gkr_fr *coeffs_x, const uint32_t *len_x, const gkr_fr *r_x,
+                     const gkr_fr *evals_abc, const gkr_fr *rho, const gkr_fr *coeffs_y, const uint32_t *len_y, const gkr_fr *r_y,
+                     const gkr_fr *evals_tw, const gkr_fr *witness /* or NULL */, size_t n_witness,
+                     int *accept, uint32_t *failed_stage, uint32_t *failed_round, uint32_t *failed_check);
 
 /* ---- step-wise sessions: one sumcheck split across GPUs -------------------
  * The reference reduces each round's per-assignment polynomials with a rayon
