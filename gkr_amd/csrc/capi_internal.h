@@ -613,6 +613,17 @@ inline int mle_pass_rounds(int m, int n, int jmax) {
     return j < 1 ? 1 : j;
 }
 
+// The first fold at two levels (kernels.hip k_mle_multifold2_mfma): the schedule of a host-hashed 2^n-point sumcheck starts
+// 10 | 5 instead of 5 | 3 | 5 -- ten variables bound in the table's second read, the rounds 6-10 hashed from sums the device
+// forms out of pass 0's partials.  Needs 1024 partials of whole 256-entry chunks from pass 0 (n >= 18) and a one-block pass
+// behind the fold, which is what reads its partial planes (2^(n-15) <= kSmallPassEntries outputs: n <= 24).
+constexpr int kMleFirstFoldLevels = 2;   // what option first_fold_levels = 0 means
+constexpr int kMleTwoLevelRounds = 2 * gkr::kMlePassMaxRounds;
+inline bool mle_two_level_first_fold(int n, const gkr::Options& o) {
+    const long long levels = o.v[gkr::OPT_first_fold_levels] == 1 || o.v[gkr::OPT_first_fold_levels] == 2 ? o.v[gkr::OPT_first_fold_levels] : kMleFirstFoldLevels;
+    return levels == 2 && n >= 18 && n <= 24 && !o.v[gkr::OPT_no_mfma_fold] && o.v[gkr::OPT_rounds_per_pass] <= 0;
+}
+
 // ---- shared by the plain sumcheck's two host-transcript drivers (capi_mle.hip: one round per pass; capi_mle_passes.hip: multi-round passes)
 // One round of one sumcheck in the caller's arrays (row = sumcheck x rounds per sumcheck + round; c0, c1, r: 32 canonical bytes
 // each): the linear slot is zero unless the round vector has two coefficients.

@@ -63,6 +63,7 @@ struct MlePassTables {
     gkr::MleSubPartial* partials = nullptr;
     unsigned char* plans = nullptr;        // per sumcheck: the digit matrix of the matrix-core fold pass
     Fr* h_w = nullptr;                     // pinned: up to 32 Montgomery weights per sumcheck
+    Fr *h_w2 = nullptr, *d_w2 = nullptr;   // the two-level first fold: the weights of rounds 6-10 as the host writes them (pinned), and on the device
     gkr::MleHostRecSub* h_rec = nullptr;   // pinned: the records the host reads
     gkr::MleHostRecSub* rec = nullptr;     // the records the passes publish to: h_rec, or device records on their way through an exchange
     uint32_t* arrivals = nullptr;          // zeroed counters of passes that publish from their last block; null: no pass does
@@ -114,7 +115,15 @@ struct MlePassPolicy {
     const char* row = nullptr;   // profile row of the streaming kernel
     int plan_event = -1;         // >= 0: the fold's digit matrices on the side stream, ordered by this aux event; -1: on the pass's own stream, untimed
     Fr* export_tail = nullptr;   // a one-block fold leaves its tables here as well (the host tail's slice of h_tail)
+    int blocks_jout = 0;         // pass 0, > 0: blocks per table as for 2^blocks_jout sub-blocks (the two-level first fold's fine sums)
+    uint32_t src_planes = 1;     // a one-block fold: its source is the sum of this many planes, 2^m_src entries apart
 };
+// pass 0's blocks per table; ahead of a two-level first fold a multiple of 1024 (every fine sum a run of partials) of whole 256-entry chunks
+static uint32_t pass0_blocks(size_t len, int jout, int nb, const MlePassPolicy& P) {
+    uint32_t nblk = gkr::mle_pass_blocks((uint32_t)len, (uint32_t)(P.blocks_jout > 0 ? P.blocks_jout : jout), nb);
+    if (P.blocks_jout > 0 && len / nblk < 256u) nblk = (uint32_t)(len / 256u);
+    return nblk;
+}
 static void queue_sub_reduce(gkr_ctx* ctx, const MlePassTables& T, int b0, int nb, uint32_t nblk, int jout, uint32_t ticket, hipStream_t st) {
     Timed t(ctx, "mle_sub_reduce", 0.0, st, true);
     gkr::launch_mle_sub_reduce(T.partials + (size_t)b0 * gkr::kMaxBlocksPerTable, nblk, (uint32_t)jout, nb, T.rec + b0, ticket, st);
@@ -129,7 +138,7 @@ static void queue_pass0(gkr_ctx* ctx, const MlePassTables& T, int b0, int nb, in
         gkr::launch_mle_multifold_small(0, src, len, nullptr, 0, (uint32_t)len, (uint32_t)jout, nb, T.h_w + (size_t)b0 * gkr::kMleMaxSub, T.rec + b0, ticket, st);
         return;
     }
-    const uint32_t nblk = gkr::mle_pass_blocks((uint32_t)len, (uint32_t)jout, nb);
+    const uint32_t nblk = pass0_blocks(len, jout, nb, P);
     gkr::MlePublish pub;
     const bool fused = fused_publish(T, b0, nb, nblk, bytes, ticket, jout, pub);
     {
@@ -146,11 +155,11 @@ static void queue_fold(gkr_ctx* ctx, const MlePassTables& T, int b0, int nb, boo
     const size_t src_stride = from_input ? T.in_stride : T.work_len;
     Fr* dst = T.work + (size_t)b0 * T.work_len;
     const Fr* w = T.h_w + (size_t)b0 * gkr::kMleMaxSub;
-    const double bytes = (double)nb * ((double)src_len + (double)S) * 32.0;
+    const double bytes = (double)nb * ((double)src_len * P.src_planes + (double)S) * 32.0;
     if (S <= gkr::kSmallPassEntries) {
         Timed t(ctx, "mle_pass_small", bytes, st, true);
         gkr::launch_mle_multifold_small(jin, src, src_stride, dst, T.work_len, (uint32_t)S, (uint32_t)jout, nb, w, T.rec + b0, ticket, st, P.export_tail,
-                                        1u << kMleTailLog2);
+                                        1u << kMleTailLog2, P.src_planes, (uint32_t)src_len);
         return;
     }
     const uint32_t nblk = gkr::mle_multifold_blocks((uint32_t)S, (uint32_t)jout, nb);
@@ -187,6 +196,7 @@ struct MleSchedule {
     int bound[kMaxGroups + 1];    // group g: sumchecks [bound[g], bound[g + 1])
     uint32_t chunk[kMaxGroups];   // sumchecks a hashing thread takes at a time from group g
     bool tail_on = false;         // the host finishes tables of 2^kMleTailLog2 entries and fewer
+    bool two_level = false;       // the host-hashed groups' first fold binds ten variables (capi_internal.h mle_two_level_first_fold)
 };
 static MleSchedule mle_schedule(int n, int batch, int hash_threads, bool is_tail, const gkr::Options& o) {
     MleSchedule sc;
@@ -197,6 +207,8 @@ static MleSchedule mle_schedule(int n, int batch, int hash_threads, bool is_tail
     const int jwant = o.v[gkr::OPT_rounds_per_pass] > 0 ? (int)o.v[gkr::OPT_rounds_per_pass] : jcap;
     sc.jmax = jwant > jcap ? jcap : jwant;
     sc.j_first = mle_pass_rounds(n, n, sc.jmax);
+    // (the driver of a table split over ranks finishes on a gathered tail table: its schedule stays what it was)
+    sc.two_level = !is_tail && mle_two_level_first_fold(n, o);
     // Groups of ~4 GiB of tables, at least four and at most eight (1024 x 2^20: eight groups of 128); sixteen for batches
     // beyond 96 GiB (4096 x 2^20: 4.64e11 field-ops/s with sixteen groups of 256, 4.48e11 with eight of 512).  Larger launches
     // stream slightly better, smaller groups feed the host's hashing more evenly and leave a shorter exposed tail (the
@@ -268,6 +280,9 @@ struct PassGroup : GroupHandoff {   // (generation of the hand-off = pass number
     int pass = 0, index = 0;
     hipStream_t chain = nullptr;   // a device-hashed group: the stream its whole chain runs on
     bool on_host = false;          // the host tail: the group's tables (2^m entries each) are in h_tail, the device is done with them
+    // the two-level first fold: rounds 1-5 hashed -> launch_fine_sums -> (mid) its record landed, rounds 6-10 hashed ->
+    // launch_fold2, which leaves the table in planes for the one pass after it
+    bool mid = false, planes = false;
 };
 // GKR_DEBUG_TIMING: the phases of a call on the host clock
 struct MlePassClock {
@@ -314,6 +329,7 @@ struct MlePassRun {
         G.ticket = ++ctx->ticket;
         MlePassPolicy P;
         P.row = G.chain ? "mle_sub_sums_dev" : "mle_sub_sums";
+        if (two_level(G)) P.blocks_jout = kMleTwoLevelRounds;
         queue_pass0(ctx, T, G.b0, G.nb, G.j, G.ticket, G.chain ? G.chain : s, P);
     }
     void launch_next_first() {
@@ -336,7 +352,58 @@ struct MlePassRun {
         // (the table it leaves is small enough for the host to finish, and there is a pass left to save)
         G.on_host = sc.tail_on && !G.chain && G.m <= (int)kMleTailLog2 && G.m - G.j > 0;
         if (G.on_host) P.export_tail = T.h_tail + ((size_t)G.b0 << kMleTailLog2);
+        if (G.planes) P.src_planes = gkr::kMleFold2Planes;
+        G.planes = false;
         queue_fold(ctx, T, G.b0, G.nb, from_input, m_src, jin, G.j, G.ticket, st, P);
+    }
+    // ---- the two-level first fold of a host-hashed group (kernels.hip, capi_internal.h mle_two_level_first_fold)
+    bool two_level(const PassGroup& G) const { return sc.two_level && !G.chain; }
+    // the small launches beside the streaming passes: on the side stream, as the fold's digit matrices are (launch_fold)
+    bool side_launches() const { return !gkr::opt(gkr::OPT_plan_main) && sc.groups != 1; }
+    // rounds 1-5 are hashed: the digit matrices of their weights, and the sums of rounds 6-10 from pass 0's partials, which
+    // stay as they are until the record of these sums has landed (the fold writes its own only after that)
+    void launch_fine_sums(PassGroup& G) {
+        const int J = G.j;
+        G.mid = true;
+        G.round0 += J;
+        G.ticket = ++ctx->ticket;
+        hipStream_t side = side_launches() ? ctx->aux : s;
+        MlePassPolicy P0;
+        P0.blocks_jout = kMleTwoLevelRounds;
+        const uint32_t nblk0 = pass0_blocks(T.in_stride, J, G.nb, P0);
+        const Fr* w = T.h_w + (size_t)G.b0 * gkr::kMleMaxSub;
+        Timed t(ctx, "mle_fold_plan", 0.0, side, true);
+        // (the sums first: the host waits for them, the fold for the matrices only five hashes later)
+        gkr::launch_mle_fine_sums(T.partials + (size_t)G.b0 * gkr::kMaxBlocksPerTable, nblk0, w, G.nb, T.rec + G.b0, G.ticket, side);
+        gkr::launch_mle_fold_plan(J, w, T.plans + (size_t)G.b0 * gkr::mle_fold_plan_bytes(), G.nb, side, side == s ? 0u : 256u);
+    }
+    // rounds 6-10 are hashed: their weights to the device, then the fold that binds all ten variables and the sums of the five
+    // rounds after them
+    void launch_fold2(PassGroup& G) {
+        const bool side = side_launches();
+        {
+            Timed t(ctx, "mle_fold_plan", 0.0, side ? ctx->aux : s, true);
+            gkr::launch_mle_copy_weights(T.h_w2 + (size_t)G.b0 * gkr::kMleMaxSub, T.d_w2 + (size_t)G.b0 * gkr::kMleMaxSub, G.nb, side ? ctx->aux : s);
+        }
+        if (side) {   // (one stream: this event is behind the digit matrices too)
+            (void)hipEventRecord(ctx->aux_events[G.index], ctx->aux);
+            (void)hipStreamWaitEvent(s, ctx->aux_events[G.index], 0);
+        }
+        const uint32_t S = 1u << (n - gkr::kMlePassMaxRounds), npart = gkr::mle_multifold2_partials(S);
+        G.mid = false;
+        G.planes = true;
+        G.on_host = false;
+        G.m = n - kMleTwoLevelRounds;
+        G.round0 += G.j;
+        G.j = gkr::kMlePassMaxRounds;   // (the fold's partials are fine enough at every n it takes, whatever rounds_for says of a streaming fold)
+        G.ticket = ++ctx->ticket;
+        {
+            Timed t(ctx, "mle_multifold", (double)G.nb * ((double)T.in_stride + (double)(gkr::kMleFold2Planes * (S >> gkr::kMlePassMaxRounds))) * 32.0, s);
+            gkr::launch_mle_multifold2(T.input + (size_t)G.b0 * T.in_stride, T.in_stride, T.work + (size_t)G.b0 * T.work_len, T.work_len, S, G.nb,
+                                       T.plans + (size_t)G.b0 * gkr::mle_fold_plan_bytes(), T.d_w2 + (size_t)G.b0 * gkr::kMleMaxSub,
+                                       T.partials + (size_t)G.b0 * gkr::kMaxBlocksPerTable, s);
+        }
+        queue_sub_reduce(ctx, T, G.b0, G.nb, npart, G.j, G.ticket, s);
     }
     // the same pass on the host (the group's tables are in h_tail): T'[i] = sum_t w_t T[t S + i], then the sub-block sums of the
     // next rounds into the record the device pass would have written
@@ -374,7 +441,8 @@ struct MlePassRun {
         }
         static_assert(sizeof(gkr::MleHostRecSub) % 8 == 0, "hand-off records are addressed in 64-bit words");
         const uint64_t* sums = reinterpret_cast<const uint64_t*>(T.h_rec[b_first].sums);
-        uint64_t* weights = G.m - J > 0 ? reinterpret_cast<uint64_t*>(T.h_w + (size_t)b_first * gkr::kMleMaxSub) : nullptr;
+        // (the sums of rounds 6-10 ahead of a two-level first fold: their weights go beside those of rounds 1-5, which the fold needs too)
+        uint64_t* weights = G.m - J > 0 ? reinterpret_cast<uint64_t*>((G.mid ? T.h_w2 : T.h_w) + (size_t)b_first * gkr::kMleMaxSub) : nullptr;
         (host_ifma_ready() && count >= 3 && !scalar_book ? gkr::gkr_ifma_pass : host_pass_scalar)(
             sums, sizeof(gkr::MleHostRecSub) / 8, count, J, final_pass ? final_len : nullptr, c0, c1, r, ln, weights, 4 * gkr::kMleMaxSub);
         for (int i = 0; i < count; ++i)
@@ -438,7 +506,14 @@ struct MlePassRun {
         if (G.state != 1 || !G.all_done()) return false;
         if (G.m - G.j > 0) {
             const bool first_fold = G.m == n;
-            if (G.on_host)
+            if (first_fold && two_level(G) && !G.mid) {
+                launch_fine_sums(G);
+                G.state = 0;
+                return true;
+            }
+            if (first_fold && two_level(G))
+                launch_fold2(G);
+            else if (G.on_host)
                 host_fold(G, G.j);
             else
                 launch_fold(G, G.j);
@@ -471,6 +546,9 @@ struct MlePassRun {
 // 2^J sub-block sums of the current table; the host runs J rounds on them (J <= 5 hashes in a row,
 // eight or sixteen sumchecks per IFMA call), derives the 2^J fold weights, and the next pass binds all J
 // variables at once.  Length rules as in run_mle_batch.
+// Tables of 2^18 .. 2^24 points (MleSchedule::two_level): the first fold binds TEN variables in its one read of the table -- the
+// host hashes rounds 1-5, the device forms the sums of rounds 6-10 from pass 0's partials and those weights (launch_fine_sums),
+// the host hashes rounds 6-10, then the fold (launch_fold2) -- so that n = 20 is 10 | 5 | 5 instead of 5 | 3 | 5 | 5 | 2.
 int run_mle_batch_passes(gkr_ctx* ctx, const Fr* d_tables, int n, int batch, gkr_fr* out_coeffs, uint32_t* out_len, gkr_fr* out_r,
                          const MleTailArgs* tail) {
     MlePassRun R{ctx, n, batch, tail, out_coeffs, out_len, out_r};
@@ -481,6 +559,10 @@ int run_mle_batch_passes(gkr_ctx* ctx, const Fr* d_tables, int n, int batch, gkr
     const MleSchedule& sc = R.sc = mle_schedule(n, batch, pool->workers() + 1, tail != nullptr, o ? *o : gkr::default_options());
     if (int rc = mle_pass_tables(ctx, "mlep", d_tables, len, len >> sc.j_first, batch, R.T)) return rc;
     if (int rc = mle_arrival_counters(ctx, len, R.T)) return rc;
+    if (sc.two_level) {
+        HIP_TRY(ctx, ctx->pinned_host("mlep.w2", sizeof(Fr) * gkr::kMleMaxSub * batch, reinterpret_cast<void**>(&R.T.h_w2)));
+        WS(ctx, "mlep.d_w2", Fr, (size_t)batch * gkr::kMleMaxSub, R.T.d_w2);
+    }
     HIP_TRY(ctx, ctx->aux_stream(sc.groups));
     if (sc.tail_on) HIP_TRY(ctx, ctx->pinned_host("mlep.tail", sizeof(Fr) * ((size_t)batch << kMleTailLog2), reinterpret_cast<void**>(&R.T.h_tail)));
     if (!gkr::opt(gkr::OPT_no_late_stream) && sc.groups > 1) HIP_TRY(ctx, ctx->late_stream(&R.late));

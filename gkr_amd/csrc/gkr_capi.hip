@@ -339,13 +339,20 @@ int gkr_selftest_fold(const gkr_fr* lo, const gkr_fr* hi, const gkr_fr* r, gkr_f
 }
 
 // the pass schedule of a 2^n-point sumcheck (host logic only): rounds[i] = rounds covered by pass i, *passes = how many.
-// mfma != 0: the default schedule (up to 5 rounds per pass), 0: the v_mad_u64_u32 fold's (up to 3).
+// mfma != 0: the matrix-core fold's schedule (up to 5 rounds per pass), 0: the v_mad_u64_u32 fold's (up to 3).  mfma == 2: with the
+// first fold at two levels where it applies (18 <= n <= 24: 10 | 5 | ..., the ten rounds of the sweep reported as one entry) --
+// what a batch of host-hashed sumchecks runs under option first_fold_levels = 2.
 int gkr_selftest_pass_schedule(int n, int mfma, uint32_t* rounds, size_t capacity, size_t* passes) {
     if (n < 1 || n > 40 || !passes) return GKR_ERR_INVALID;
     const int jmax = mfma ? gkr::kMlePassMaxRounds : 3;
+    gkr::Options two = gkr::default_options();
+    two.v[gkr::OPT_first_fold_levels] = 2;
+    two.v[gkr::OPT_no_mfma_fold] = two.v[gkr::OPT_rounds_per_pass] = 0;
+    const bool two_level = mfma == 2 && mle_two_level_first_fold(n, two);
     size_t count = 0;
     for (int m = n; m > 0;) {
-        const int j = mle_pass_rounds(m, n, jmax);
+        // (behind the two-level fold one pass of five rounds: its partials are fine enough at every n it takes)
+        const int j = two_level && m == n ? kMleTwoLevelRounds : (two_level && m == n - kMleTwoLevelRounds ? gkr::kMlePassMaxRounds : mle_pass_rounds(m, n, jmax));
         if (rounds && count < capacity) rounds[count] = (uint32_t)j;
         ++count;
         m -= j;

@@ -125,7 +125,7 @@ void launch_mle_sub_sums(const Fr* tables, size_t stride, uint32_t len, uint32_t
 void launch_mle_sub_reduce(const MleSubPartial* partials, uint32_t nblk, uint32_t jout, uint32_t batch, MleHostRecSub* host_rec,
                            uint32_t ticket, hipStream_t s);
 size_t mle_fold_plan_bytes();
-void launch_mle_fold_plan(int jin, const Fr* weights, void* plans, uint32_t batch, hipStream_t s);
+void launch_mle_fold_plan(int jin, const Fr* weights, void* plans, uint32_t batch, hipStream_t s, uint32_t threads = 0);
 void launch_mle_multifold(int jin, const Fr* src, size_t src_stride, Fr* dst, size_t dst_stride, uint32_t S, uint32_t batch,
                           uint32_t nblk, const Fr* weights, const void* plans, MleSubPartial* partials, hipStream_t s,
                           const MlePublish* publish = nullptr);
@@ -136,7 +136,19 @@ void launch_mle_pass_hash_lanes(const MleHostRecSub* rec, uint32_t count, uint32
 // tail (may be null; pinned host memory, tail_stride entries per sumcheck): the folded table (S <= tail_stride entries) is left there
 // too -- the host binds the remaining variables itself (capi_mle.hip, the host tail of a lone sumcheck).
 void launch_mle_multifold_small(int jin, const Fr* src, size_t src_stride, Fr* dst, size_t dst_stride, uint32_t S, uint32_t jout,
-                                uint32_t batch, const Fr* weights, MleHostRecSub* host_rec, uint32_t ticket, hipStream_t s, Fr* tail = nullptr, uint32_t tail_stride = 0);
+                                uint32_t batch, const Fr* weights, MleHostRecSub* host_rec, uint32_t ticket, hipStream_t s, Fr* tail = nullptr, uint32_t tail_stride = 0,
+                                uint32_t planes = 1, uint32_t plane_stride = 0);
+// The first fold at two levels (kernels.hip): launch_mle_fine_sums turns pass 0's partials (nblk a multiple of 1024 per table) and the
+// weights of rounds 1-5 into the 32 sums of rounds 6-10; launch_mle_multifold2 binds the ten variables in one read of the table
+// (S = 2^(n-5), plans: launch_mle_fold_plan(5) of the first five, w2: the other 32 weights copied to device memory by
+// launch_mle_copy_weights) and leaves eight partial planes of S / 32 entries and mle_multifold2_partials(S) partials per table.
+constexpr uint32_t kMleFold2Planes = 8;
+uint32_t mle_multifold2_partials(uint32_t S);
+void launch_mle_fine_sums(const MleSubPartial* partials, uint32_t nblk, const Fr* weights, uint32_t batch, MleHostRecSub* host_rec, uint32_t ticket,
+                          hipStream_t s);
+void launch_mle_copy_weights(const Fr* src, Fr* dst, uint32_t batch, hipStream_t s);
+void launch_mle_multifold2(const Fr* src, size_t src_stride, Fr* dst, size_t dst_stride, uint32_t S, uint32_t batch, const void* plans, const Fr* w2,
+                           MleSubPartial* partials, hipStream_t s);
 void launch_layer_round_reduce(const LayerPartial* partials, uint32_t nblk, LayerHostRec* host_rec, uint32_t ticket,
                                LayerBatch lb, hipStream_t s);
 void launch_fold_small(Fr* W, uint32_t hw, const FixedMul* rtab, LayerBatch lb, hipStream_t s);

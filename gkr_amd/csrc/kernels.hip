@@ -401,6 +401,104 @@ __global__ void __launch_bounds__(256) k_mle_multifold_mfma(const Fr* __restrict
     if (pub.arrivals) mle_publish_from_last_block(partials, pub);
 }
 
+// ---- the first fold at two levels: ten variables bound in the one read of the table --------------------------------------------
+// Index the table as b 2^(n-5) + c I + i (b = variables 1-5, c = variables 6-10, I = 2^(n-10)):
+//     T''[i] = sum_c w'_c ( sum_b w_b T[b 2^(n-5) + c I + i] ),   i < I.
+// The inner sum is the matrix-core fold's output at j = c I + i (mfma_multifold_stream<5>, the same 32 streams, 2^(n-13)
+// blocks per table as k_mle_multifold_mfma<5> has); the outer one is what k_mle_eval_mfma's sink does with a wave-uniform
+// Montgomery multiplier.  The rounds 6-10 that produce w' need the sums over i of the inner sums, S'[c]; these are linear in
+// the sums F[b][c] of the table's runs of I entries, which pass 0 left as partials: k_mle_fine_sums forms them from w without
+// a read of the table.
+
+// S'[c] = sum_b w_b F[b][c] from pass 0's partials (nblk a multiple of 1024: every F is a run of nblk / 1024 partials) into
+// the host record; the record's dep flag stays pass 0's.  It runs beside a streaming pass that fills the chip, and a block finds
+// room on a CU the sooner the smaller it is (a block of 1024 threads waits for most of a streaming kernel: 0.5 ms): 256 threads,
+// thread 32 q + c takes b = q, q + 8, q + 16, q + 24 in one unreduced sum.  grid = (batch), block = 256
+__global__ void __launch_bounds__(256) k_mle_fine_sums(const MleSubPartial* __restrict__ partials, uint32_t nblk, const Fr* __restrict__ weights,
+                                                       MleHostRecSub* __restrict__ host_rec, uint32_t ticket) {
+    __shared__ Fr s_w[kMleMaxSub];
+    __shared__ Fr s_p[kMleMaxSub][8];   // [c][q]
+    const uint32_t t = threadIdx.x, q = t >> 5, c = t & 31u, run = nblk >> 10;
+    const MleSubPartial* p = partials + (size_t)blockIdx.x * nblk;
+    // (the weights sit in pinned host memory: fetched once per block, 4 bytes per lane)
+    s_w[t >> 3].l[t & 7u] = reinterpret_cast<const uint32_t*>(weights + (size_t)blockIdx.x * kMleMaxSub)[t];
+    static_assert(kMleMaxSub * 8 == 256, "one word of the weights per thread");
+    __syncthreads();
+    Lazy17 dot = lazy_zero();
+    for (uint32_t k = 0; k < 4u; ++k) {
+        const uint32_t b = q + 8u * k;
+        Acc<10> f = acc_zero<10>();
+        for (uint32_t i = 0; i < run; ++i) acc_add_acc(f, p[(size_t)(b * 32u + c) * run + i].sum);
+        lazy_mac_v(dot, acc_reduce(f), s_w[b]);
+    }
+    s_p[c][q] = lazy_reduce(dot);   // canonical * Montgomery = canonical products
+    __syncthreads();
+    MleHostRecSub* r = host_rec + blockIdx.x;
+    if (t < kMleMaxSub) {
+        Acc<9> tot = acc_zero<9>();
+        for (uint32_t k = 0; k < 8u; ++k) acc_add_fr(tot, s_p[t][k]);
+        r->sums[t] = acc_reduce(tot);
+    }
+    __syncthreads();   // every record store is issued and waited for before the release below
+    if (t == 0) __hip_atomic_store(&r->seq, ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// the weights of rounds 6-10 from the pinned array the host wrote them to into device memory: the fold's waves read theirs
+// with scalar loads, once per block.  grid = (batch), block = 8 * kMleMaxSub
+__global__ void __launch_bounds__(256) k_mle_copy_weights(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst) {
+    const size_t i = (size_t)blockIdx.x * (8u * kMleMaxSub) + threadIdx.x;
+    dst[i] = src[i];
+}
+
+// The fold.  S = 2^(n-5) inner outputs per table, I = S / 32 >= 256 entries of T''.  A block takes ONE 64-entry tile of i and four
+// consecutive c, one per wave: each wave multiplies its 64 finished inner outputs by w'_c (SGPRs) into an unreduced product,
+// the four are added through LDS and reduced once, and the block stores 64 entries of the partial plane P[c >> 2][i] -- eight
+// planes of I entries per table, which the one-block pass after it adds up as it reads (k_mle_multifold_small).  Sums of
+// T'' for the next five rounds: a sub-block is I / 32 entries, g = min(I / 32, 64) lanes of the tile; the block leaves 64 / g
+// partials at ((64 it + lane) / g) * 8 + (c >> 2), so that each sub-block is a run of consecutive partials and
+// mle_total_and_publish(nblk = 8 I / g, jout = 5) totals them as any pass's.
+// Registers (120) and LDS (45 KB) put three blocks on a CU, one more than k_mle_multifold_mfma<5> has: what runs beside this kernel
+// on the side and late streams must fit into the 22 KB of LDS they leave, or it waits for the kernel's end (k_mle_fine_sums and
+// k_mle_multifold_small behind this fold do; the next group's digit matrices, 33 KB, wait -- they have a streaming pass of time).
+// grid = (I / 8, batch): block x = (c >> 2) * (I / 64) + it; block = 256
+__global__ void __launch_bounds__(256) k_mle_multifold2_mfma(const Fr* __restrict__ src, size_t src_stride, Fr* __restrict__ dst, size_t dst_stride,
+                                                             uint32_t S, const MfmaFoldPlan* __restrict__ plans, const Fr* __restrict__ w2,
+                                                             MleSubPartial* __restrict__ partials) {
+    __shared__ Lazy17 s_prod[3][64];
+    __shared__ __attribute__((aligned(16))) unsigned char digits[32 * 32 * (1 << kMfmaMaxJ)];
+    const Fr* s = src + (size_t)blockIdx.y * src_stride;
+    const uint32_t I = S >> kMfmaMaxJ, tiles = I >> 6;   // (powers of two)
+    const uint32_t it = blockIdx.x & (tiles - 1u), cq = blockIdx.x / tiles;
+    const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t begin = 4u * cq * I + 64u * it;
+    const Fr wc = load_fr(w2 + (size_t)blockIdx.y * kMleMaxSub + 4u * cq + wave);   // wave-uniform: scalar registers
+    Lazy17 prod = lazy_zero();
+    // (one iteration: begin + 256 only says that all four waves have a tile; wave w's is begin + w I)
+    mfma_multifold_stream<kMfmaMaxJ>(s, S, plans + blockIdx.y, begin, begin + 256u, 0u, digits,
+                                     [&](uint32_t, uint32_t, uint32_t, const Fr& y) { lazy_mac_s(prod, y, wc); }, I);
+    if (wave != 0u) s_prod[wave - 1u][lane] = prod;
+    __syncthreads();
+    if (wave != 0u) return;
+#pragma unroll
+    for (int w = 0; w < 3; ++w) lazy_add(prod, s_prod[w][lane]);
+    const Fr y = lazy_reduce(prod);
+    store_fr(dst + (size_t)blockIdx.y * dst_stride + (size_t)cq * I + 64u * it + lane, y);
+    const uint32_t sub = I >> 5, g = sub < 64u ? sub : 64u;
+    Acc<9> acc = acc_zero<9>();
+    acc_add_fr(acc, y);
+    for (uint32_t off = g >> 1; off >= 1u; off >>= 1) {
+        Acc<9> o;
+#pragma unroll
+        for (int l = 0; l < 9; ++l) o.l[l] = __shfl_down(acc.l[l], off, 64);
+        acc_add_acc(acc, o);
+    }
+    if ((lane & (g - 1u)) == 0u) {
+        MleSubPartial* p = partials + (size_t)blockIdx.y * (8u * (I / g)) + (size_t)((64u * it + lane) / g) * 8u + cq;
+        p->sum = acc;
+        p->dep = 0;
+    }
+}
+
 // partials of a pass -> 2^jout canonical sub-block sums per table -> pinned host record (mle_total_and_publish).  Streaming
 // passes and passes of many blocks publish through this second launch; fusing it into them (the last block to arrive
 // reduces: mle_publish_from_last_block) costs a streaming pass 15 % of its bandwidth, three times what the launch saves.
@@ -454,13 +552,19 @@ __global__ void __launch_bounds__(256) k_mle_sums_small(const Fr* __restrict__ s
 // instead of one thread per output walking its 32 products (128 and then 4 busy threads of 256: 31 and 29 us per pass
 // for a lone sumcheck; the pass's weights, which sit in pinned host memory, are fetched once per block, not once per
 // product).  The partial sums are reduced where they are (any order of exact sums gives the same canonical element),
-// totalled per output, and the outputs' sub-block sums are taken from LDS.  grid = (batch), block = 1024
+// totalled per output, and the outputs' sub-block sums are taken from LDS.  planes = 1: the source is one table;
+// kMleFold2Planes: the sum of that many.  grid = (batch), block = 1024 (256 behind the two-level fold: see NT below),
+// dynamic LDS = 32 bytes per thread
 __global__ void __launch_bounds__(1024) k_mle_multifold_small(const Fr* __restrict__ src, size_t src_stride, Fr* __restrict__ dst,
                                                               size_t dst_stride, uint32_t S, uint32_t jin, uint32_t jout,
                                                               const Fr* __restrict__ weights, MleHostRecSub* __restrict__ host_rec,
-                                                              uint32_t ticket, Fr* __restrict__ tail, uint32_t tail_stride) {
+                                                              uint32_t ticket, Fr* __restrict__ tail, uint32_t tail_stride, uint32_t planes,
+                                                              uint32_t plane_stride) {
     __shared__ Fr s_w[kMleMaxSub];
-    __shared__ Fr s_y[1024];       // partial sums [q][i], then (the first S) the outputs
+    // partial sums [q][i], then (the first S) the outputs: NT entries of dynamic LDS (a block of 256 threads then takes 11 KB,
+    // which a CU has left beside three blocks of the two-level fold)
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_y_bytes[];
+    Fr* s_y = reinterpret_cast<Fr*>(s_y_bytes);
     __shared__ Acc<9> s_part[kMleMaxSub];
     const uint32_t b = blockIdx.x;
     const Fr* s = src + (size_t)b * src_stride;
@@ -469,13 +573,26 @@ __global__ void __launch_bounds__(1024) k_mle_multifold_small(const Fr* __restri
     if (threadIdx.x < nterm * 8u)
         s_w[threadIdx.x >> 3].l[threadIdx.x & 7u] = reinterpret_cast<const uint32_t*>(weights + (size_t)b * kMleMaxSub)[threadIdx.x];
     __syncthreads();
-    const uint32_t items = S << jin, per = items > 1024u ? items >> 10 : 1u, groups = nterm / per;
+    // (NT threads: 1024, or fewer for the pass behind the two-level first fold -- a smaller block finds room on a CU beside the
+    // streaming fold of another group, a block of 1024 waits for that kernel's end; NT a power of two >= max(S, 256))
+    const uint32_t NT = blockDim.x;
+    const uint32_t items = S << jin, per = items > NT ? items / NT : 1u, groups = nterm / per;
     const uint32_t i = threadIdx.x & (S - 1u), q = threadIdx.x / S;   // S is a power of two
     if (q < groups) {
         Lazy17 acc = lazy_zero();
         for (uint32_t t = 0; t < per; ++t) {
             const uint32_t term = q * per + t;
-            lazy_mac_v(acc, load_fr(s + (size_t)term * S + i), s_w[term]);
+            // (behind the two-level first fold a source entry is the sum of that fold's `planes` partial planes: modular
+            // additions, no product more)
+            Fr x = load_fr(s + (size_t)term * S + i);
+            if (planes == kMleFold2Planes) {   // (all loads in flight together)
+                Fr xp[kMleFold2Planes - 1];
+#pragma unroll
+                for (uint32_t pl = 1; pl < kMleFold2Planes; ++pl) xp[pl - 1] = load_fr(s + (size_t)pl * plane_stride + (size_t)term * S + i);
+#pragma unroll
+                for (uint32_t pl = 1; pl < kMleFold2Planes; ++pl) x = fr_add(x, xp[pl - 1]);
+            }
+            lazy_mac_v(acc, x, s_w[term]);
         }
         s_y[q * S + i] = lazy_reduce(acc);
     }
@@ -493,9 +610,9 @@ __global__ void __launch_bounds__(1024) k_mle_multifold_small(const Fr* __restri
     __syncthreads();   // every partial has been read
     if (threadIdx.x < S) s_y[threadIdx.x] = y;
     __syncthreads();
-    // sub-block sums of the outputs: min(sub, 1024 / nsub) threads per sub-block, totals through LDS
+    // sub-block sums of the outputs: min(sub, NT / nsub) threads per sub-block, totals through LDS
     const uint32_t nsub = 1u << jout, sub = S >> jout;
-    uint32_t tps = 1024u >> jout;
+    uint32_t tps = NT >> jout;
     if (tps > sub) tps = sub;
     const uint32_t sb = threadIdx.x / tps, rr = threadIdx.x % tps;
     MleHostRecSub* r = host_rec + b;
@@ -2574,7 +2691,8 @@ size_t mle_fold_plan_bytes() { return sizeof(MfmaFoldPlan); }
 // the plans of `batch` sumchecks (batch * mle_fold_plan_bytes() of device memory) from their weights; only needed
 // when mle_multifold_uses_mfma says so.  One thread per row of the digit matrix (32 * 2^jin rows: the kernel sits on a lone
 // sumcheck's round path, where four rows per thread cost 14 us instead of 7)
-void launch_mle_fold_plan(int jin, const Fr* weights, void* plans, uint32_t batch, hipStream_t s) {
+// threads (jin = 5 only; 0: 1024): smaller blocks for plans built beside a streaming pass that fills the chip -- they find room on a CU sooner
+void launch_mle_fold_plan(int jin, const Fr* weights, void* plans, uint32_t batch, hipStream_t s, uint32_t threads) {
     MfmaFoldPlan* pl = static_cast<MfmaFoldPlan*>(plans);
     if (jin == 1)
         hipLaunchKernelGGL(k_mle_fold_plan<1>, dim3(batch), dim3(64), 0, s, weights, pl);
@@ -2585,7 +2703,7 @@ void launch_mle_fold_plan(int jin, const Fr* weights, void* plans, uint32_t batc
     else if (jin == 4)
         hipLaunchKernelGGL(k_mle_fold_plan<4>, dim3(batch), dim3(512), 0, s, weights, pl);
     else
-        hipLaunchKernelGGL(k_mle_fold_plan<5>, dim3(batch), dim3(1024), 0, s, weights, pl);
+        hipLaunchKernelGGL(k_mle_fold_plan<5>, dim3(batch), dim3(threads ? threads : 1024u), 0, s, weights, pl);
 }
 
 // plans: what launch_mle_fold_plan built for this pass (matrix-core form), unused otherwise
@@ -2638,13 +2756,38 @@ uint32_t mle_multifold_blocks(uint32_t S, uint32_t jout, uint32_t batch) {
 }
 
 void launch_mle_multifold_small(int jin, const Fr* src, size_t src_stride, Fr* dst, size_t dst_stride, uint32_t S, uint32_t jout,
-                                uint32_t batch, const Fr* weights, MleHostRecSub* host_rec, uint32_t ticket, hipStream_t s, Fr* tail, uint32_t tail_stride) {
+                                uint32_t batch, const Fr* weights, MleHostRecSub* host_rec, uint32_t ticket, hipStream_t s, Fr* tail, uint32_t tail_stride,
+                                uint32_t planes, uint32_t plane_stride) {
     dim3 grid(batch);
+    const uint32_t threads = planes > 1 && S <= 256u ? 256u : 1024u;
     if (jin == 0)
         hipLaunchKernelGGL(k_mle_sums_small, grid, dim3(256), 0, s, src, src_stride, S, jout, host_rec, ticket);
     else
-        hipLaunchKernelGGL(k_mle_multifold_small, grid, dim3(1024), 0, s, src, src_stride, dst, dst_stride, S, (uint32_t)jin, jout, weights,
-                           host_rec, ticket, tail, tail_stride);
+        hipLaunchKernelGGL(k_mle_multifold_small, grid, dim3(threads), threads * sizeof(Fr), s, src, src_stride, dst, dst_stride, S, (uint32_t)jin, jout, weights,
+                           host_rec, ticket, tail, tail_stride, planes, plane_stride);
+}
+
+// the two-level first fold (k_mle_multifold2_mfma): partials per table it leaves for mle_total_and_publish(jout = 5)
+uint32_t mle_multifold2_partials(uint32_t S) {
+    const uint32_t I = S >> kMfmaMaxJ, sub = I >> 5;
+    return 8u * (I / (sub < 64u ? sub : 64u));
+}
+
+void launch_mle_fine_sums(const MleSubPartial* partials, uint32_t nblk, const Fr* weights, uint32_t batch, MleHostRecSub* host_rec, uint32_t ticket,
+                          hipStream_t s) {
+    hipLaunchKernelGGL(k_mle_fine_sums, dim3(batch), dim3(256), 0, s, partials, nblk, weights, host_rec, ticket);
+}
+
+void launch_mle_copy_weights(const Fr* src, Fr* dst, uint32_t batch, hipStream_t s) {
+    hipLaunchKernelGGL(k_mle_copy_weights, dim3(batch), dim3(8 * kMleMaxSub), 0, s, reinterpret_cast<const uint32_t*>(src),
+                       reinterpret_cast<uint32_t*>(dst));
+}
+
+// S = 2^(n-5) with 2^13 <= S <= 2^19; dst: eight planes of S / 32 entries per table; w2: device memory
+void launch_mle_multifold2(const Fr* src, size_t src_stride, Fr* dst, size_t dst_stride, uint32_t S, uint32_t batch, const void* plans, const Fr* w2,
+                           MleSubPartial* partials, hipStream_t s) {
+    hipLaunchKernelGGL(k_mle_multifold2_mfma, dim3(S >> 8, batch), dim3(256), 0, s, src, src_stride, dst, dst_stride, S,
+                       static_cast<const MfmaFoldPlan*>(plans), w2, partials);
 }
 
 void launch_mle_round_reduce(const MlePartial* partials, uint32_t nblk, uint32_t batch, MleHostRec* host_rec,

@@ -174,9 +174,12 @@ __device__ __forceinline__ Fr mf_finish(const mf_v16i& a0, const mf_v16i& a1) {
 // `sink(e0, h, c, y)`: what becomes of a finished output -- y is entry e0 + 32 h + c of the folded table, 32 h + c = the lane's place
 // in the wave's 64-entry tile (h its half, c its column), e0 (a multiple of 64 past `begin`) wave-uniform.  The fold pass stores it (mfma_multifold_block below);
 // the multilinear evaluation (kernels_mle_eval.hip) multiplies it into a sum and stores nothing.
+// `wave_stride`: entries between the tiles of neighbouring waves -- 64: the block's four tiles are consecutive (every caller but
+// the two-level first fold, whose waves take the same tile of four consecutive planes of the folded table: kernels.hip).
 template <int JIN, class Sink>
 __device__ __forceinline__ void mfma_multifold_stream(const Fr* __restrict__ s, uint32_t S, const MfmaFoldPlan* __restrict__ plan,
-                                                      uint32_t begin, uint32_t end, uint32_t rot, unsigned char* lds, Sink&& sink) {
+                                                      uint32_t begin, uint32_t end, uint32_t rot, unsigned char* lds, Sink&& sink,
+                                                      uint32_t wave_stride = 64u) {
     constexpr int NB = 1 << JIN;
     constexpr int KS = NB < 8 ? NB : 8;     // k-steps per stage
     constexpr int NST = NB / KS;            // stages per iteration: 1, 2 or 4
@@ -234,8 +237,8 @@ __device__ __forceinline__ void mfma_multifold_stream(const Fr* __restrict__ s, 
 
     const uint32_t span = end - begin;
     const uint32_t iters = (span + 255u) / 256u;
-    const uint32_t woff = wave * 64u;
-    if (woff >= span) return;                             // chunks shorter than 256 leave waves idle
+    const uint32_t woff = wave * wave_stride;
+    if (wave * 64u >= span) return;                       // chunks shorter than 256 leave waves idle
     uint32_t cur = rot % iters;
     auto next_pos = [&]() {   // entry offset of the iteration after the current one (wraps around the chunk)
         cur = cur + 1u == iters ? 0u : cur + 1u;

@@ -21,6 +21,7 @@ namespace gkr {
     /* ---- plain sumcheck (prove_sumcheck, sumcheck.rs:158-214) ---- */                                                              \
     X(rounds_per_pass, "rounds_per_pass", "GKR_ROUNDS_PER_PASS", 0, "rounds a pass of the plain sumcheck covers (0: 5; 3 without the MFMA fold)") \
     X(no_mfma_fold, "no_mfma_fold", "GKR_NO_MFMA_FOLD", 0, "fold passes on v_mad_u64_u32 instead of int8 MFMA")                      \
+    X(first_fold_levels, "first_fold_levels", "GKR_FIRST_FOLD_LEVELS", 0, "variables the first fold of a host-hashed 2^18 .. 2^24-point sumcheck binds: 1 five, 2 ten in the one read (0: the default, capi_internal.h kMleFirstFoldLevels)") \
     X(no_fused_reduce, "no_fused_reduce", "GKR_NO_FUSED_REDUCE", 0, "latency-bound passes publish through k_mle_sub_reduce instead of from their last block") \
     X(hash_chunk, "hash_chunk", "GKR_HASH_CHUNK", 0, "8 or 16: sumchecks per host hash call (0: 16 when host threads are scarce)")    \
     X(device_hash_percent, "device_hash_percent", "GKR_DEVICE_HASH_PERCENT", 0, "share of a batch of >= 64 plain sumchecks hashed on the device (0..90)") \

@@ -205,8 +205,9 @@ int  gkr_selftest_host_prod_pass(const gkr_fr *recs, int count, int J, const uin
                                  gkr_fr *c0, gkr_fr *r, gkr_fr *w, int *used_ifma);
 /* sum_i a_i b_i through the unreduced 544-bit dot-product accumulator of the fused layer kernel */
 int  gkr_selftest_dot(const gkr_fr *a, const gkr_fr *b, size_t n, gkr_fr *out);
-/* the pass schedule of a 2^n-point plain sumcheck (host logic): rounds covered by each pass; mfma = 1 default
- * (up to 5 rounds per pass), 0 the v_mad_u64_u32 fold's (up to 3).  *passes = number of passes. */
+/* the pass schedule of a 2^n-point plain sumcheck (host logic): rounds covered by each pass; mfma = 1 the matrix-core
+ * fold's (up to 5 rounds per pass), 0 the v_mad_u64_u32 fold's (up to 3), 2 the matrix-core fold's with the first fold at
+ * two levels where it applies (18 <= n <= 24: 10 | 5 | ..., option first_fold_levels = 2).  *passes = number of passes. */
 int  gkr_selftest_pass_schedule(int n, int mfma, uint32_t *rounds, size_t capacity, size_t *passes);
 /* the launch geometry of gkr_sumcheck_product_batch_device (host logic, the process-default options; the degree does not enter):
  * nblk[j] = blocks per sumcheck of round j's pass (j = 0 .. n-1; round 0 the value pass, later rounds the fold-and-value pass),
