@@ -119,6 +119,13 @@ constexpr uint32_t kSmallPassEntries = 512;   // passes whose output has <= this
 uint32_t mle_pass_blocks(uint32_t items, uint32_t jout, uint32_t batch);
 uint32_t mle_multifold_blocks(uint32_t S, uint32_t jout, uint32_t batch);
 bool mle_multifold_uses_mfma(uint32_t S, uint32_t nblk);
+// pass 0 (launch_mle_sub_sums): k_mle_sub_sums, or for streaming launches (no publish, chunk = len / nblk a multiple of 256 entries, nblk a
+// multiple of 4) its pipelined form k_mle_sub_sums_stream -- the same partials, bit for bit
+constexpr int kMlePass0Stream = 2;   // what option pass0_stream = 0 means: 1 k_mle_sub_sums always, 2 the pipelined form where it applies
+// launches of at least this many partials (and chunks of whole 512 entries) take the form with sixteen loads per lane and two partials per
+// wave: 2 partials x 12 resident waves x 256 CUs x 4 generations.  Reasoned, not tuned: only 128 tables x 1024 partials was measured
+// (profiles/r22); what smaller launches take is a guess that keeps their block count at the chip's size or above
+constexpr uint64_t kMlePass0DeepMinPartials = 2u * 12u * 256u * 4u;
 // Every pass: per-block partial sums, then a reduce kernel that writes the pinned host record.
 void launch_mle_sub_sums(const Fr* tables, size_t stride, uint32_t len, uint32_t batch, uint32_t nblk, MleSubPartial* partials,
                          hipStream_t s, const MlePublish* publish = nullptr);

@@ -344,6 +344,117 @@ __global__ void __launch_bounds__(256) k_mle_sub_sums(const Fr* __restrict__ tab
     if (pub.arrivals) mle_publish_from_last_block(partials, pub);
 }
 
+// ---- pass 0 of a streaming launch as a pipelined read (option pass0_stream) -----------------------------------------------------
+// The same partials as k_mle_sub_sums -- partial p the exact sum of entries [p chunk, (p + 1) chunk) and "some entry 2m differs
+// from 2m + 1 there" -- read the way the matrix-core fold reads: a WAVE owns PPW consecutive partials, one contiguous range of
+// the table, and takes it in steps of 1 KiB, 16 bytes per lane (non-temporal).  Piece 64 k + lane of the range is half
+// (lane & 1) of entry 32 k + (lane >> 1): a lane always sees the same half of an entry and keeps a 128-bit sum with a carry limb
+// (one addend per step: chunk <= 2^30 entries is far from the limb's 2^32).  Entries 2m and 2m + 1 are the four lanes of a quad
+// (ranges start at even entries: chunk % 256 == 0), so the neighbour's half is lane ^ 2's register, DPP quad_perm [2,3,0,1].
+// U loads per lane are in flight in two sets of U / 2: a set is added up and loaded again at once, U steps ahead, while the other
+// set is still on its way -- every wait in the loop is for the older set only, and the loads stay in flight over the loop's back
+// edge and over the end of a partial (the last round is peeled so that no load sits behind a branch).  A partial ends with the two
+// halves put at bit 0 and bit 128 of an Acc<9>, a sum over the wave and one store by lane 0: no LDS, no barrier.
+// Integer sums do not depend on their order: every partial is bit for bit k_mle_sub_sums'.
+// grid = (nblk / (4 PPW), batch), block = 256; chunk % (32 U) == 0; never publishes (streaming launches only).
+// (U, PPW) = (8, 1) and (16, 2) are built: launch_mle_sub_sums chooses.
+// a lane's 128-bit half sum with its carry limb += one 16-byte piece: acc_add_fr's padded carry chain (fr32.h, "gfx950 forms": a
+// VALU that reads a carry needs two wait states after the VALU that wrote it, and the hazard pass does not see inside an asm
+// string; with several waves per SIMD the pads cost no throughput, and this kernel waits for memory, not for issue slots)
+__device__ __forceinline__ void half_acc_add(uint32_t (&a)[5], const mf_v4u& x) {
+    asm("v_add_co_u32_e32 %0, vcc, %0, %5\n\ts_nop 1\n\t"
+        "v_addc_co_u32_e32 %1, vcc, %1, %6, vcc\n\ts_nop 1\n\t"
+        "v_addc_co_u32_e32 %2, vcc, %2, %7, vcc\n\ts_nop 1\n\t"
+        "v_addc_co_u32_e32 %3, vcc, %3, %8, vcc\n\ts_nop 1\n\t"
+        "v_addc_co_u32_e32 %4, vcc, 0, %4, vcc"
+        : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4])
+        : "v"(x.x), "v"(x.y), "v"(x.z), "v"(x.w)
+        : "vcc");
+}
+
+template <int U, int PPW>
+__global__ void __launch_bounds__(256) k_mle_sub_sums_stream(const Fr* __restrict__ tables, size_t table_stride, uint32_t chunk, uint32_t nblk,
+                                                             MleSubPartial* __restrict__ partials) {
+    static_assert(U >= 2 && (U & (U - 1)) == 0, "two sets of U / 2 loads");
+    constexpr int H = U / 2;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t p0 = (blockIdx.x * 4u + wave) * (uint32_t)PPW;   // the wave's first partial
+    const uint32_t rpp = chunk / (32u * U);                        // rounds of U steps per partial
+    const mf_v4u* src = reinterpret_cast<const mf_v4u*>(tables + (size_t)blockIdx.y * table_stride + (size_t)p0 * chunk) + lane;
+    MleSubPartial* out = partials + (size_t)blockIdx.y * nblk + p0;
+
+    mf_v4u xa[H], xb[H];
+    uint32_t acc[5] = {0u, 0u, 0u, 0u, 0u}, diff = 0u;
+    auto load_set = [&](mf_v4u (&x)[H], const mf_v4u* p) {
+#pragma unroll
+        for (int u = 0; u < H; ++u) x[u] = __builtin_nontemporal_load(p + (size_t)u * 64u);
+    };
+    auto add_set = [&](const mf_v4u (&x)[H]) {
+#pragma unroll
+        for (int u = 0; u < H; ++u) {
+            half_acc_add(acc, x[u]);
+            const mf_v4u v = x[u];
+            diff |= (v.x ^ (uint32_t)__builtin_amdgcn_mov_dpp((int)v.x, 0x4E, 0xF, 0xF, true)) |
+                    (v.y ^ (uint32_t)__builtin_amdgcn_mov_dpp((int)v.y, 0x4E, 0xF, 0xF, true)) |
+                    (v.z ^ (uint32_t)__builtin_amdgcn_mov_dpp((int)v.z, 0x4E, 0xF, 0xF, true)) |
+                    (v.w ^ (uint32_t)__builtin_amdgcn_mov_dpp((int)v.w, 0x4E, 0xF, 0xF, true));
+        }
+    };
+    auto finish = [&](MleSubPartial* p) {
+        const bool odd = (lane & 1u) != 0u;
+        Acc<9> s;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            s.l[i] = odd ? 0u : acc[i];
+            s.l[4 + i] = odd ? acc[i] : (i == 0 ? acc[4] : 0u);
+        }
+        s.l[8] = odd ? acc[4] : 0u;
+        s = wave_sum(s);
+        const uint32_t dep = __any(diff != 0u) ? 1u : 0u;
+        if (lane == 0) {
+            p->sum = s;
+            p->dep = dep;
+        }
+    };
+
+    // (the first loads in the loop's order, pinned: the waits at the loop's head are counted for the worse of the two ways in,
+    // and a prologue the scheduler had shuffled made them drain every round)
+#pragma unroll
+    for (int u = 0; u < H; ++u) {
+        xa[u] = __builtin_nontemporal_load(src + (size_t)u * 64u);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int u = 0; u < H; ++u) {
+        xb[u] = __builtin_nontemporal_load(src + (size_t)(H + u) * 64u);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    src += (size_t)U * 64u;
+    [[maybe_unused]] uint32_t left = rpp;
+    for (uint32_t r = (uint32_t)PPW * rpp - 1u; r != 0u; --r) {
+        add_set(xa);
+        load_set(xa, src);
+        __builtin_amdgcn_sched_barrier(0);
+        add_set(xb);
+        load_set(xb, src + (size_t)H * 64u);
+        __builtin_amdgcn_sched_barrier(0);
+        src += (size_t)U * 64u;
+        if constexpr (PPW > 1) {
+            if (--left == 0u) {
+                finish(out++);
+#pragma unroll
+                for (int i = 0; i < 5; ++i) acc[i] = 0u;
+                diff = 0u;
+                left = rpp;
+            }
+        }
+    }
+    add_set(xa);
+    add_set(xb);
+    finish(out);
+}
+
 // one pass: bind JIN variables with the weights w[0 .. 2^JIN) (Montgomery, wave-uniform), write the
 // folded table of S entries, accumulate its sub-block sums.  grid = (nblk, batch), chunk = S / nblk.
 template <int JIN>
@@ -2670,9 +2781,31 @@ uint32_t mle_pass_blocks(uint32_t items, uint32_t jout, uint32_t batch) {
     return b;
 }
 
+// The pipelined form (k_mle_sub_sums_stream) takes the streaming launches: nothing published from the last block, whole rounds
+// of loads per partial, whole blocks of waves.  Two instances (measured: profiles/r22): sixteen loads per lane and two partials
+// per wave where the launch is at least kMlePass0DeepMinPartials partials -- three waves per SIMD, so this is four generations of
+// resident waves -- and a partial is at least 512 entries; eight loads and a partial per wave otherwise (chunks of 256 entries,
+// and launches of few tables, which the deeper form would put on fewer blocks than the chip has CUs).  Only the headline's launch
+// (128 tables x 1024 partials) was measured: there the deeper form is ahead; the threshold and the choice below it are reasoned, small
+// launches were not tuned (a lone 2^20-point table runs the shallow form as 256 blocks).  0: k_mle_sub_sums.
+// Option pass0_stream = 1 keeps k_mle_sub_sums everywhere, 2 asks for the pipelined form wherever it applies.
+static int mle_sub_sums_stream_form(uint32_t len, uint32_t batch, uint32_t nblk, bool publishes) {
+    const long long want = opt(OPT_pass0_stream) == 1 || opt(OPT_pass0_stream) == 2 ? opt(OPT_pass0_stream) : kMlePass0Stream;
+    if (want != 2 || publishes || nblk == 0 || len % nblk != 0) return 0;
+    const uint32_t chunk = len / nblk;
+    if (chunk % 512u == 0 && nblk % 8u == 0 && (uint64_t)batch * nblk >= kMlePass0DeepMinPartials) return 2;
+    return chunk % 256u == 0 && nblk % 4u == 0 ? 1 : 0;
+}
+
 void launch_mle_sub_sums(const Fr* tables, size_t stride, uint32_t len, uint32_t batch, uint32_t nblk, MleSubPartial* partials,
                          hipStream_t s, const MlePublish* publish) {
-    hipLaunchKernelGGL(k_mle_sub_sums, dim3(nblk, batch), dim3(256), 0, s, tables, stride, len, partials, publish ? *publish : MlePublish{});
+    const int form = mle_sub_sums_stream_form(len, batch, nblk, publish != nullptr);
+    if (form == 2)
+        hipLaunchKernelGGL((k_mle_sub_sums_stream<16, 2>), dim3(nblk / 8u, batch), dim3(256), 0, s, tables, stride, len / nblk, nblk, partials);
+    else if (form == 1)
+        hipLaunchKernelGGL((k_mle_sub_sums_stream<8, 1>), dim3(nblk / 4u, batch), dim3(256), 0, s, tables, stride, len / nblk, nblk, partials);
+    else
+        hipLaunchKernelGGL(k_mle_sub_sums, dim3(nblk, batch), dim3(256), 0, s, tables, stride, len, partials, publish ? *publish : MlePublish{});
 }
 
 void launch_mle_sub_reduce(const MleSubPartial* partials, uint32_t nblk, uint32_t jout, uint32_t batch, MleHostRecSub* host_rec,
