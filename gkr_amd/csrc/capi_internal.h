@@ -2,8 +2,9 @@
 // memory; capi_mle.hip: the plain sumcheck's entry points, per-round schedules and sessions; capi_mle_passes.hip: its multi-round
 // schedule, whole tables and tables split over ranks; capi_layer.hip: the layer sumcheck over gate lists; capi_layer_dense.hip:
 // its dense form; capi_prove.hip: whole proofs; capi_product.hip: the sumcheck over a product of resident tables; capi_sop.hip: over a sum of
-// such products; capi_zerocheck.hip: the zero-check; capi_r1cs.hip: an R1CS's tables in front of it; capi_r1cs_verify.hip: the
-// verifier of that pair of sumchecks): the context,
+// such products; capi_zerocheck.hip: the zero-check -- the entry points and shape checks of the three, whose one driver is
+// capi_resident.hip; capi_r1cs.hip: an R1CS's tables in front of it; capi_r1cs_verify.hip: the verifier of that pair of
+// sumchecks): the context,
 // its caches and workspaces, profiling brackets, the host transcript's helpers, the hand-off wait, the plain sumcheck's group
 // hand-off.  Not a public header.
 #pragma once
@@ -503,6 +504,23 @@ struct DevBuf {
     hipError_t alloc(size_t count) { return hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T)); }
 };
 
+// The host-side entry points' way to their resident forms: `count` elements of the caller's in a device buffer of their own,
+// which lives until run(buffer) -- the resident form at batch 1 -- has returned.
+template <typename Run>
+int run_on_upload(gkr_ctx* ctx, const gkr_fr* host, size_t count, Run run) {
+    GKR_ENTER(ctx);
+    DevBuf<Fr> d;
+    HIP_TRY(ctx, d.alloc(count));
+    HIP_TRY(ctx, hipMemcpyAsync(d.p, host, count * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+    return run(d.p);
+}
+// the same for a sumcheck's tables, which must be canonical
+template <typename Run>
+int run_on_tables(gkr_ctx* ctx, const gkr_fr* tables, size_t count, Run run) {
+    if (!all_canonical(tables, count)) return ctx->fail(GKR_ERR_NON_CANONICAL, "table entry >= r");
+    return run_on_upload(ctx, tables, count, run);
+}
+
 // ------------------------------------------------------------- hand-off waiting
 // Spin on the seq words the reduce kernel stores last (system-scope release) into
 // pinned host memory.  Bounded: a device fault or a lost launch turns into an
@@ -767,19 +785,22 @@ inline void host_hash_slot(const gkr_fr* row, uint32_t width, uint32_t len, gkr:
 // ---- defined in capi_product.hip
 // the shapes gkr_sumcheck_product* and gkr_sumcheck_product_verify* admit (batch itself, 1 .. 65535, is the caller's check)
 bool product_shape_ok(int n, int degree, int batch);
-// blocks per sumcheck of round `round` (0-based) of the product passes; the sum-of-products passes (capi_sop.hip) launch the same
+// blocks per sumcheck of round `round` (0-based) of the passes of all three sumchecks over resident tables (capi_resident.hip)
 uint32_t product_round_blocks(int n, int batch, int round);
-// `batch` product sumchecks on resident tables, the whole of gkr_sumcheck_product_batch_device behind its argument checks (the
-// R1CS inner sumcheck runs it on the tables it builds): everything already queued on the context's stream is waited for, the
-// outputs are in the caller's arrays
-int run_product_batch(gkr_ctx* ctx, const Fr* d_tables, int n, int degree, int batch, gkr_fr* out_coeffs, uint32_t* out_len, gkr_fr* out_r,
-                      gkr_fr* out_evals);
 // ---- defined in capi_sop.hip
 // the shapes gkr_sumcheck_sop* and gkr_sumcheck_sop_verify* admit, with the term structure in the kernels' form; the term
 // coefficients in the kernels' form (NULL: all one), false: one is >= r
 bool sop_shape(int n, int n_tables, const gkr_sop_term* terms, int n_terms, int batch, gkr::SopTerms* ts);
 bool sop_coeffs(const gkr_fr* term_coeffs, int n_terms, gkr::SopCoeffs* cf);
-// ---- defined in capi_zerocheck.hip
+// ---- defined in capi_resident.hip: the three families' fillings of the one driver
+// `batch` product sumchecks on resident tables, the whole of gkr_sumcheck_product_batch_device behind its argument checks (the
+// R1CS inner sumcheck runs it on the tables it builds): everything already queued on the context's stream is waited for, the
+// outputs are in the caller's arrays
+int run_product_batch(gkr_ctx* ctx, const Fr* d_tables, int n, int degree, int batch, gkr_fr* out_coeffs, uint32_t* out_len, gkr_fr* out_r,
+                      gkr_fr* out_evals);
+// the same for sums of products: the whole of gkr_sumcheck_sop_batch_device behind its argument checks
+int run_sop_batch(gkr_ctx* ctx, const Fr* d_tables, int n, const gkr::SopTerms& ts, const gkr::SopCoeffs& cf, int batch, gkr_fr* out_coeffs,
+                  uint32_t* out_len, gkr_fr* out_r, gkr_fr* out_evals);
 // `batch` zero-checks eq(z_b, .) * (the terms) on resident tables, the whole of gkr_sumcheck_zerocheck_batch_device behind its
 // argument checks: everything already queued on the context's stream is waited for, the outputs are in the caller's arrays
 int run_zerocheck_batch(gkr_ctx* ctx, const Fr* d_tables, int n, const gkr::SopTerms& ts, const gkr::SopCoeffs& cf, int batch,

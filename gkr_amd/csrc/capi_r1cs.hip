@@ -1,8 +1,8 @@
 // The R1CS zero-check: the CSR form of an R1CS (r1cs.cpp) resident on a context's device, the tables Az, Bz, Cz of a batch of
 // resident witnesses (kernels_r1cs.hip), the row check a * b == c, and the zero-check eq(z, .) (A B - C) on those tables
-// (run_zerocheck_batch, capi_zerocheck.hip).  And the inner sumcheck that reduces the zero-check's three claims to the witness: the
+// (run_zerocheck_batch, capi_resident.hip).  And the inner sumcheck that reduces the zero-check's three claims to the witness: the
 // column-major form resident, the table T(y) = sum_m rho_m sum_i M_m[i][y] eq(x, i), the product path at degree 2 on (T, w)
-// (run_product_batch, capi_product.hip).  C ABI: include/gkr_amd.h.
+// (run_product_batch, capi_resident.hip).  C ABI: include/gkr_amd.h.
 #include "capi_internal.h"
 
 static_assert(sizeof(gkr_r1cs_term) == sizeof(uint2), "a record is eight bytes: {wire, pool index}");
@@ -309,11 +309,9 @@ int gkr_r1cs_inner(gkr_ctx* ctx, const gkr_r1cs* r1cs, const gkr_fr* witness, si
     gkr_r1cs_cols* raw = nullptr;
     if (const int rc = gkr_r1cs_cols_prepare(ctx, r1cs, &raw)) return rc;
     std::unique_ptr<gkr_r1cs_cols, void (*)(gkr_r1cs_cols*)> cols(raw, gkr_r1cs_cols_free);
-    GKR_ENTER(ctx);
-    DevBuf<Fr> d;
-    HIP_TRY(ctx, d.alloc(info.n_wires));
-    HIP_TRY(ctx, hipMemcpyAsync(d.p, witness, (size_t)info.n_wires * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
-    return run_r1cs_inner(ctx, cols.get(), d.p, info.n_wires, 1, x, rho, out_coeffs, out_len, out_r, out_evals);
+    return run_on_upload(ctx, witness, info.n_wires, [&](const Fr* d) {
+        return run_r1cs_inner(ctx, cols.get(), d, info.n_wires, 1, x, rho, out_coeffs, out_len, out_r, out_evals);
+    });
 }
 
 int gkr_r1cs_rows_prepare(gkr_ctx* ctx, const gkr_r1cs* r1cs, gkr_r1cs_rows** out) {
@@ -374,11 +372,9 @@ int gkr_r1cs_zerocheck(gkr_ctx* ctx, const gkr_r1cs* r1cs, const gkr_fr* witness
     gkr_r1cs_rows* raw = nullptr;
     if (const int rc = gkr_r1cs_rows_prepare(ctx, r1cs, &raw)) return rc;
     std::unique_ptr<gkr_r1cs_rows, void (*)(gkr_r1cs_rows*)> rows(raw, gkr_r1cs_rows_free);
-    GKR_ENTER(ctx);
-    DevBuf<Fr> d;
-    HIP_TRY(ctx, d.alloc(info.n_wires));
-    HIP_TRY(ctx, hipMemcpyAsync(d.p, witness, (size_t)info.n_wires * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
-    return run_r1cs_zerocheck(ctx, rows.get(), d.p, info.n_wires, 1, z, out_coeffs, out_len, out_r, out_evals, out_eq, out_first_bad);
+    return run_on_upload(ctx, witness, info.n_wires, [&](const Fr* d) {
+        return run_r1cs_zerocheck(ctx, rows.get(), d, info.n_wires, 1, z, out_coeffs, out_len, out_r, out_evals, out_eq, out_first_bad);
+    });
 }
 
 }  // extern "C"

@@ -16,6 +16,8 @@
 //
 // Launch geometry: that of the plain sumcheck (k_mle_sum_first / k_mle_fold_sum): grid (blocks per sumcheck, batch), blocked
 // distribution with chunk starts at multiples of 256; one block walks all D factors of its chunk.
+// The chunk, the lanes, the values -> coefficients step and the round's publication (row, hash, r) are product_common.h's, shared
+// with kernels_sop.hip and kernels_zerocheck.hip; the length rule of round n and the zero-factor rule are this path's own.
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
@@ -47,9 +49,8 @@ __global__ void __launch_bounds__(256) k_product_first(const Fr* __restrict__ ta
     if (threadIdx.x == 0) s_flags = 0;
     __syncthreads();
     // h is a power of two >= 2 and chunk starts are multiples of 256: lanes i and i ^ 1 are neighbours of one wave, both active
-    const uint32_t chunk = ((h + gridDim.x - 1) / gridDim.x + 255u) & ~255u;
-    const uint32_t begin = blockIdx.x * chunk;
-    const uint32_t end = begin + chunk < h ? begin + chunk : h;
+    uint32_t begin, end;
+    block_chunk(h, begin, end);
     for (uint32_t i = begin + threadIdx.x; i < end; i += blockDim.x) {
         Fr lo[D], hi[D];
 #pragma unroll
@@ -88,9 +89,8 @@ __global__ void __launch_bounds__(256) k_product_fold_sum(const Fr* __restrict__
     ProductLane<D> lane[D + 1];
 #pragma unroll
     for (int k = 0; k <= D; ++k) lane[k] = product_lane_zero<D>();
-    const uint32_t chunk = ((q + gridDim.x - 1) / gridDim.x + 255u) & ~255u;   // blocked distribution, see k_mle_sum_first
-    const uint32_t begin = blockIdx.x * chunk;
-    const uint32_t end = begin + chunk < q ? begin + chunk : q;
+    uint32_t begin, end;
+    block_chunk(q, begin, end);
     for (uint32_t i = begin + threadIdx.x; i < end; i += blockDim.x) {
         Fr lo[D], hi[D];
 #pragma unroll
@@ -163,44 +163,20 @@ __global__ void __launch_bounds__(64) k_product_round(const ProductPartial* __re
     product_values_to_coeffs<D>(v, c);
     uint32_t len;
     if (round + 1 < n) {
-        uint32_t lead = 0;
-        bool leading = true;
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-            leading = leading && fr_is_zero(c[k]);
-            lead += leading ? 1u : 0u;
-        }
-        len = (uint32_t)D + 1u - lead;
-    } else {
+        len = round_length<D + 1>(c);
+    } else {   // this path's own rule; the slots in front of the last len are cleared (zero already, by the rule's own argument)
         const uint32_t m = meta[b];
         len = (m >> 8) ? 1u : 1u + (m & 0xFFu);
+#pragma unroll
+        for (int k = 0; k < D; ++k)
+            if ((uint32_t)k + len < (uint32_t)D + 1u) c[k] = fr_zero();
     }
     const size_t row = (size_t)b * n + round;
-    Fr* oc = out_coeffs + row * (D + 1);
-    // multi_hash(used slots, key 0) as mimc7_multi_hash does it, the slots indexed statically (no private array in memory)
-    Fr h = fr_zero();
-#pragma unroll
-    for (int k = 0; k <= D; ++k) {
-        const bool used = (uint32_t)k + len >= (uint32_t)D + 1u;
-        if (!used) c[k] = fr_zero();   // (zero already, by the length rule's own argument)
-        oc[k] = c[k];
-        if (used) {
-            const Fr a = to_mont(c[k]);
-            h = fr_add(fr_add(h, a), mimc7_hash_mont(a, h, cts));
-        }
-    }
-    const Fr r = from_mont(h);
-    out_len[row] = len;
-    out_r[row] = r;
-    if (round + 1 < n) {
+    const Fr r = round_publish<D + 1>(c, len, (uint32_t)D, row, cts, out_coeffs, out_len, out_r);
+    if (round + 1 < n)
         store_fixed_mul(rtab + row, r);
-    } else {
-        const Fr r_mont = to_mont(r);
-        for (int f = 0; f < D; ++f) {
-            const Fr* t = work + ((size_t)b * D + f) * work_stride;
-            evals[(size_t)b * D + f] = fr_fold(t[0], t[1], r_mont);
-        }
-    }
+    else
+        fold_last_entries(work, work_stride, b, (uint32_t)D, to_mont(r), evals);
 }
 
 // ---------------------------------------------------------------------------

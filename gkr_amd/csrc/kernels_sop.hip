@@ -13,7 +13,8 @@
 //   3. the term's block partial goes to partials[(b nblk + block) K + k].
 // The round kernel (one wave per sumcheck) totals term after term, undoes the term's 2^(-256 (d_k - 1)) scaling, forms its
 // coefficients, multiplies by c_k and adds them right-aligned into four slots; then the length rule, the hash, the next fold's
-// multiplier table and, after round n, the tables' values at the challenges.
+// multiplier table and, after round n, the tables' values at the challenges.  The chunk, the fold of the tables and the round
+// kernel's steps are product_common.h's, shared with the zero-check (kernels_zerocheck.hip).
 //
 // The term structure is a kernel argument (SopTerms, SopCoeffs): wave-uniform, read with scalar loads; nothing indexes a
 // per-thread array with a runtime value.  Term bounds: those of kernels_product.hip per term (the lanes start at zero for every
@@ -28,9 +29,6 @@
 namespace gkr {
 
 namespace {
-
-__device__ __forceinline__ uint32_t sop_term_degree(uint32_t term) { return term & 0xFFu; }
-__device__ __forceinline__ uint32_t sop_term_table(uint32_t term, int j) { return (term >> (8 + 8 * j)) & 0xFFu; }
 
 // one term's D + 1 values over entries begin .. end of the block's chunk: lo = T[i], hi = T[i + hi_off] of the term's D tables
 // (t: table 0 of this sumcheck)
@@ -78,9 +76,8 @@ __global__ void __launch_bounds__(256) k_sop_first(const Fr* __restrict__ tables
                                                    ProductPartial* __restrict__ partials) {
     __shared__ Acc<9> smem[4 * (kProductMaxDegree + 1)];
     const Fr* t = tables + (size_t)blockIdx.y * ts.n_tables * table_stride;
-    const uint32_t chunk = ((h + gridDim.x - 1) / gridDim.x + 255u) & ~255u;   // blocked distribution, see k_mle_sum_first
-    const uint32_t begin = blockIdx.x * chunk;
-    const uint32_t end = begin + chunk < h ? begin + chunk : h;
+    uint32_t begin, end;
+    block_chunk(h, begin, end);
     sop_terms_pass(t, table_stride, h, begin, end, ts, smem, partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * ts.n_terms);
 }
 
@@ -94,21 +91,9 @@ __global__ void __launch_bounds__(256) k_sop_fold_sum(const Fr* src, size_t src_
     const Fr* s = src + (size_t)blockIdx.y * ts.n_tables * src_stride;
     Fr* d = dst + (size_t)blockIdx.y * ts.n_tables * dst_stride;
     const FixedMul T = rtab[(size_t)blockIdx.y * r_stride];   // wave-uniform -> scalar loads, lives in SGPRs
-    const uint32_t chunk = ((q + gridDim.x - 1) / gridDim.x + 255u) & ~255u;
-    const uint32_t begin = blockIdx.x * chunk;
-    const uint32_t end = begin + chunk < q ? begin + chunk : q;
-    for (uint32_t i = begin + threadIdx.x; i < end; i += blockDim.x) {
-        for (uint32_t m = 0; m < ts.n_tables; ++m) {
-            const Fr* sm = s + (size_t)m * src_stride;
-            Fr* dm = d + (size_t)m * dst_stride;
-            const Fr x0 = load_fr(sm + i), x1 = load_fr(sm + i + 2 * (size_t)q);
-            const Fr x2 = load_fr(sm + i + q), x3 = load_fr(sm + i + 3 * (size_t)q);
-            Fr lo, hi;
-            fr_fold_fixed2(x0, x1, x2, x3, T, lo, hi);
-            store_fr(dm + i, lo);
-            store_fr(dm + i + q, hi);
-        }
-    }
+    uint32_t begin, end;
+    block_chunk(q, begin, end);
+    fold_tables_chunk(s, src_stride, d, dst_stride, ts.n_tables, q, T, begin, end);
     sop_terms_pass(d, dst_stride, q, begin, end, ts, smem, partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * ts.n_terms);
 }
 
@@ -127,87 +112,14 @@ __global__ void __launch_bounds__(64) k_sop_round(const ProductPartial* __restri
     const uint32_t b = blockIdx.x, K = ts.n_terms;
     const ProductPartial* p = partials + (size_t)b * nblk * K;
     Fr sum[S];   // highest degree first, right-aligned (thread 0's)
-#pragma unroll
-    for (int k = 0; k < S; ++k) sum[k] = fr_zero();
-    for (uint32_t t = 0; t < K; ++t) {
-        const uint32_t d = sop_term_degree(ts.term[t]);
-        Acc<10> tot[S];
-#pragma unroll
-        for (int k = 0; k < S; ++k) tot[k] = acc_zero<10>();
-        for (uint32_t i = threadIdx.x; i < nblk; i += 64) {
-            const ProductPartial* pp = p + (size_t)i * K + t;
-#pragma unroll
-            for (int k = 0; k < S; ++k)
-                if ((uint32_t)k <= d) acc_add_acc(tot[k], pp->s[k]);
-        }
-#pragma unroll
-        for (int k = 0; k < S; ++k) tot[k] = wave_sum(tot[k]);
-        if (threadIdx.x == 0) {
-            Fr v[S];
-#pragma unroll
-            for (int k = 0; k < S; ++k) {
-                v[k] = acc_reduce(tot[k]);
-#pragma unroll
-                for (int m = 1; m < kProductMaxDegree; ++m)
-                    if ((uint32_t)m < d) v[k] = mont_mul(v[k], fr_r2());   // x 2^256 per lazy or Montgomery reduction taken
-            }
-            Fr c[S];
-#pragma unroll
-            for (int k = 0; k < S; ++k) c[k] = fr_zero();
-            if (d == 1) {
-                const Fr v1[2] = {v[0], v[1]};
-                Fr c1[2];
-                product_values_to_coeffs<1>(v1, c1);
-                c[2] = c1[0];
-                c[3] = c1[1];
-            } else if (d == 2) {
-                const Fr v2[3] = {v[0], v[1], v[2]};
-                Fr c2[3];
-                product_values_to_coeffs<2>(v2, c2);
-                c[1] = c2[0];
-                c[2] = c2[1];
-                c[3] = c2[2];
-            } else {
-                product_values_to_coeffs<3>(v, c);
-            }
-            const Fr ck = to_mont(cf.c[t]);
-#pragma unroll
-            for (int k = 0; k < S; ++k) sum[k] = fr_add(sum[k], mont_mul(c[k], ck));
-        }
-    }
+    terms_total<kProductMaxDegree>(p, nblk, ts, cf, sum);
     if (threadIdx.x != 0) return;
-    uint32_t lead = 0;
-    bool leading = true;
-#pragma unroll
-    for (int k = 0; k < S - 1; ++k) {   // (slots above the call's degree hold zero: no term reaches them)
-        leading = leading && fr_is_zero(sum[k]);
-        lead += leading ? 1u : 0u;
-    }
-    const uint32_t len = (uint32_t)S - lead, D = ts.max_degree;
-    const size_t row = (size_t)b * n + round;
-    Fr* oc = out_coeffs + row * (D + 1);
-    // multi_hash(used slots, key 0) as mimc7_multi_hash does it, the slots indexed statically (no private array in memory)
-    Fr h = fr_zero();
-#pragma unroll
-    for (int k = 0; k < S; ++k) {
-        if ((uint32_t)k + D >= (uint32_t)S - 1u) oc[(uint32_t)k + D - ((uint32_t)S - 1u)] = sum[k];   // (an unused slot holds zero)
-        if ((uint32_t)k + len >= (uint32_t)S) {
-            const Fr a = to_mont(sum[k]);
-            h = fr_add(fr_add(h, a), mimc7_hash_mont(a, h, cts));
-        }
-    }
-    const Fr r = from_mont(h);
-    out_len[row] = len;
-    out_r[row] = r;
-    if (round + 1 < n) {
+    const size_t row = (size_t)b * n + round;   // (the slots above the call's degree hold zero: no term reaches them)
+    const Fr r = round_publish<S>(sum, round_length<S>(sum), ts.max_degree, row, cts, out_coeffs, out_len, out_r);
+    if (round + 1 < n)
         store_fixed_mul(rtab + row, r);
-    } else {
-        const Fr r_mont = to_mont(r);
-        for (uint32_t m = 0; m < ts.n_tables; ++m) {
-            const Fr* t = work + ((size_t)b * ts.n_tables + m) * work_stride;
-            evals[(size_t)b * ts.n_tables + m] = fr_fold(t[0], t[1], r_mont);
-        }
-    }
+    else
+        fold_last_entries(work, work_stride, b, ts.n_tables, to_mont(r), evals);
 }
 
 // ---------------------------------------------------------------------------

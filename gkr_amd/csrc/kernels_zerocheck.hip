@@ -25,7 +25,8 @@
 // 2^-256 meets E_lo's Montgomery form), a degree-2 value carries 2^-256 as on the SOP path; the round kernel undoes it.
 //
 // The term structure is a kernel argument (SopTerms, SopCoeffs): wave-uniform, read with scalar loads; nothing indexes a
-// per-thread array with a runtime value.
+// per-thread array with a runtime value.  The chunk, the fold of the tables and the round kernel's steps (a term's total, the
+// length rule, the row and its hash, the tables' last values) are product_common.h's, shared with kernels_sop.hip.
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
@@ -39,9 +40,6 @@ namespace {
 
 constexpr int kZcValues = 3;   // values (and coefficients) of h_j: inner degree <= 2
 
-__device__ __forceinline__ uint32_t zc_term_degree(uint32_t term) { return term & 0xFFu; }
-__device__ __forceinline__ uint32_t zc_term_table(uint32_t term, int j) { return (term >> (8 + 8 * j)) & 0xFFu; }
-
 // one term's D + 1 WEIGHTED values over entries begin .. end of the block's chunk (begin a multiple of 256, blockDim.x = 256):
 // e_hi this sumcheck's E_hi of the round, e_lo this thread's E_lo entry (both Montgomery)
 template <int D>
@@ -50,7 +48,7 @@ __device__ __forceinline__ void zc_term_values(const Fr* t, size_t stride, uint3
     static_assert(D == 1 || D == 2, "inner degree 1 or 2");
     const Fr* tf[D];
 #pragma unroll
-    for (int j = 0; j < D; ++j) tf[j] = t + (size_t)zc_term_table(term, j) * stride;
+    for (int j = 0; j < D; ++j) tf[j] = t + (size_t)sop_term_table(term, j) * stride;
     Lazy17 lane[D + 1];
 #pragma unroll
     for (int k = 0; k <= D; ++k) lane[k] = lazy_zero();
@@ -93,7 +91,7 @@ __device__ __forceinline__ void zc_terms_pass(const Fr* t, size_t stride, uint32
     const Fr lo = threadIdx.x < (1u << kl) ? load_fr(e_lo + ((size_t)blockIdx.y << kl) + threadIdx.x) : fr_zero();
     for (uint32_t k = 0; k < ts.n_terms; ++k) {
         const uint32_t term = ts.term[k];
-        if (zc_term_degree(term) == 1)
+        if (sop_term_degree(term) == 1)
             zc_term_values<1>(t, stride, term, hi_off, begin, end, hi, lo, smem, out + k);
         else
             zc_term_values<2>(t, stride, term, hi_off, begin, end, hi, lo, smem, out + k);
@@ -110,9 +108,8 @@ __global__ void __launch_bounds__(256) k_zc_first(const Fr* __restrict__ tables,
                                                   ProductPartial* __restrict__ partials) {
     __shared__ Acc<9> smem[4 * kZcValues];
     const Fr* t = tables + (size_t)blockIdx.y * ts.n_tables * table_stride;
-    const uint32_t chunk = ((h + gridDim.x - 1) / gridDim.x + 255u) & ~255u;   // blocked distribution, see k_mle_sum_first
-    const uint32_t begin = blockIdx.x * chunk;
-    const uint32_t end = begin + chunk < h ? begin + chunk : h;
+    uint32_t begin, end;
+    block_chunk(h, begin, end);
     zc_terms_pass(t, table_stride, h, begin, end, ts, e_hi, kh, e_lo, kl, smem,
                   partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * ts.n_terms);
 }
@@ -128,30 +125,18 @@ __global__ void __launch_bounds__(256) k_zc_fold_sum(const Fr* src, size_t src_s
     const Fr* s = src + (size_t)blockIdx.y * ts.n_tables * src_stride;
     Fr* d = dst + (size_t)blockIdx.y * ts.n_tables * dst_stride;
     const FixedMul T = rtab[(size_t)blockIdx.y * r_stride];   // wave-uniform -> scalar loads, lives in SGPRs
-    const uint32_t chunk = ((q + gridDim.x - 1) / gridDim.x + 255u) & ~255u;
-    const uint32_t begin = blockIdx.x * chunk;
-    const uint32_t end = begin + chunk < q ? begin + chunk : q;
-    for (uint32_t i = begin + threadIdx.x; i < end; i += blockDim.x) {
-        for (uint32_t m = 0; m < ts.n_tables; ++m) {
-            const Fr* sm = s + (size_t)m * src_stride;
-            Fr* dm = d + (size_t)m * dst_stride;
-            const Fr x0 = load_fr(sm + i), x1 = load_fr(sm + i + 2 * (size_t)q);
-            const Fr x2 = load_fr(sm + i + q), x3 = load_fr(sm + i + 3 * (size_t)q);
-            Fr lo, hi;
-            fr_fold_fixed2(x0, x1, x2, x3, T, lo, hi);
-            store_fr(dm + i, lo);
-            store_fr(dm + i + q, hi);
-        }
-    }
+    uint32_t begin, end;
+    block_chunk(q, begin, end);
+    fold_tables_chunk(s, src_stride, d, dst_stride, ts.n_tables, q, T, begin, end);
     zc_terms_pass(d, dst_stride, q, begin, end, ts, e_hi, kh, e_lo, kl, smem,
                   partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * ts.n_terms);
 }
 
 // One wave per sumcheck and round: term after term the blocks' partials are totalled, a degree-2 term's 2^-256 undone, the term's
 // coefficients formed (product_values_to_coeffs<d_k>), multiplied by c_k and added right-aligned into h_j's three slots.  Then
-// g_j = (a + b X) h_j with a = s_j (1 - z_j), b = s_j (2 z_j - 1), written out slot by slot, and what k_sop_round does in EVERY
-// round: leading zero coefficients dropped, one kept at least, MiMC7 of the used slots, r published canonical and as the next
-// fold's multiplier table.  s_{j+1} = a + b r_j goes to the sumcheck's slot s_slot[b] (Montgomery).  Rows of out_coeffs have
+// g_j = (a + b X) h_j with a = s_j (1 - z_j), b = s_j (2 z_j - 1), written out slot by slot, and the sum-of-products path's steps
+// of EVERY round (product_common.h): leading zero coefficients dropped, one kept at least, MiMC7 of the used slots, r published
+// canonical and as the next fold's multiplier table.  s_{j+1} = a + b r_j goes to the sumcheck's slot s_slot[b] (Montgomery).  Rows of out_coeffs have
 // D + 1 slots, D = ts.max_degree + 1.  After round n: evals[b M + m] = T_m~(r_1 .. r_n) and eq_out[b] = s_{n+1} = eq(z, r).
 // grid = (batch), block = 64
 __global__ void __launch_bounds__(64) k_zc_round(const ProductPartial* __restrict__ partials, uint32_t nblk, uint32_t round, uint32_t n,
@@ -163,44 +148,7 @@ __global__ void __launch_bounds__(64) k_zc_round(const ProductPartial* __restric
     const uint32_t b = blockIdx.x, K = ts.n_terms;
     const ProductPartial* p = partials + (size_t)b * nblk * K;
     Fr h[V];   // h_j, highest degree first, right-aligned (thread 0's)
-#pragma unroll
-    for (int k = 0; k < V; ++k) h[k] = fr_zero();
-    for (uint32_t t = 0; t < K; ++t) {
-        const uint32_t d = zc_term_degree(ts.term[t]);
-        Acc<10> tot[V];
-#pragma unroll
-        for (int k = 0; k < V; ++k) tot[k] = acc_zero<10>();
-        for (uint32_t i = threadIdx.x; i < nblk; i += 64) {
-            const ProductPartial* pp = p + (size_t)i * K + t;
-#pragma unroll
-            for (int k = 0; k < V; ++k)
-                if ((uint32_t)k <= d) acc_add_acc(tot[k], pp->s[k]);
-        }
-#pragma unroll
-        for (int k = 0; k < V; ++k) tot[k] = wave_sum(tot[k]);
-        if (threadIdx.x == 0) {
-            Fr v[V];
-#pragma unroll
-            for (int k = 0; k < V; ++k) {
-                v[k] = acc_reduce(tot[k]);
-                if (d == 2) v[k] = mont_mul(v[k], fr_r2());   // x 2^256: the lazy reduction of a product of two table entries
-            }
-            Fr c[V];
-            if (d == 1) {
-                const Fr v1[2] = {v[0], v[1]};
-                Fr c1[2];
-                product_values_to_coeffs<1>(v1, c1);
-                c[0] = fr_zero();
-                c[1] = c1[0];
-                c[2] = c1[1];
-            } else {
-                product_values_to_coeffs<2>(v, c);
-            }
-            const Fr ck = to_mont(cf.c[t]);
-#pragma unroll
-            for (int k = 0; k < V; ++k) h[k] = fr_add(h[k], mont_mul(c[k], ck));
-        }
-    }
+    terms_total<V - 1>(p, nblk, ts, cf, h);
     if (threadIdx.x != 0) return;
     // the linear factor of the round's own variable times the bound variables' scalar, in Montgomery form
     const Fr zj = load_fr(z + (size_t)b * n + round);
@@ -214,39 +162,15 @@ __global__ void __launch_bounds__(64) k_zc_round(const ProductPartial* __restric
     sum[1] = fr_add(mont_mul(h[0], fa), mont_mul(h[1], fb));
     sum[2] = fr_add(mont_mul(h[1], fa), mont_mul(h[2], fb));
     sum[3] = mont_mul(h[2], fa);
-    uint32_t lead = 0;
-    bool leading = true;
-#pragma unroll
-    for (int k = 0; k < S - 1; ++k) {   // (slots above the call's degree hold zero: no term reaches them)
-        leading = leading && fr_is_zero(sum[k]);
-        lead += leading ? 1u : 0u;
-    }
-    const uint32_t len = (uint32_t)S - lead, D = ts.max_degree + 1u;
     const size_t row = (size_t)b * n + round;
-    Fr* oc = out_coeffs + row * (D + 1);
-    // multi_hash(used slots, key 0) as k_sop_round does it, the slots indexed statically (no private array in memory)
-    Fr hs = fr_zero();
-#pragma unroll
-    for (int k = 0; k < S; ++k) {
-        if ((uint32_t)k + D >= (uint32_t)S - 1u) oc[(uint32_t)k + D - ((uint32_t)S - 1u)] = sum[k];   // (an unused slot holds zero)
-        if ((uint32_t)k + len >= (uint32_t)S) {
-            const Fr a = to_mont(sum[k]);
-            hs = fr_add(fr_add(hs, a), mimc7_hash_mont(a, hs, cts));
-        }
-    }
-    const Fr r = from_mont(hs);
-    out_len[row] = len;
-    out_r[row] = r;
+    const Fr r = round_publish<S>(sum, round_length<S>(sum), ts.max_degree + 1u, row, cts, out_coeffs, out_len, out_r);
     const Fr r_mont = to_mont(r);
     const Fr s_next = fr_add(fa, mont_mul(fb, r_mont));   // s_j eq(z_j, r_j)
     if (round + 1 < n) {
         store_fixed_mul(rtab + row, r);
         store_fr(s_slot + b, s_next);
     } else {
-        for (uint32_t m = 0; m < ts.n_tables; ++m) {
-            const Fr* t = work + ((size_t)b * ts.n_tables + m) * work_stride;
-            evals[(size_t)b * ts.n_tables + m] = fr_fold(t[0], t[1], r_mont);
-        }
+        fold_last_entries(work, work_stride, b, ts.n_tables, r_mont, evals);
         store_fr(eq_out + b, from_mont(s_next));
     }
 }

@@ -1,6 +1,8 @@
-// Device helpers shared by the kernels of the sumcheck over a product of resident tables (kernels_product.hip) and over a sum of
-// such products (kernels_sop.hip): what a thread accumulates a round polynomial's values in, one index's terms of the D + 1
-// values, the block's partial, and the values -> coefficients step of the round kernels.  Internal to the library.
+// Device helpers shared by the kernels of the sumchecks over resident tables -- a product (kernels_product.hip), a sum of products
+// (kernels_sop.hip), the zero-check (kernels_zerocheck.hip): a block's chunk, the fold of every table of a chunk, what a thread
+// accumulates a round polynomial's values in, one index's terms of the D + 1 values, the block's partial, the term structure's
+// decoders, and the round kernels' steps: a term's partials -> its scaled coefficients, the length rule, the row with its hash
+// and challenge, the tables' values after the last round.  Internal to the library.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,10 +10,41 @@
 
 #include "kernels.h"
 #include "dev_util.h"
+#include "mimc7.h"
 
 namespace gkr {
 
 namespace {
+
+// SopTerms::term
+__device__ __forceinline__ uint32_t sop_term_degree(uint32_t term) { return term & 0xFFu; }
+__device__ __forceinline__ uint32_t sop_term_table(uint32_t term, int j) { return (term >> (8 + 8 * j)) & 0xFFu; }
+
+// this block's entries begin .. end of a pass over `items` per sumcheck, grid.x blocks each: blocked distribution, chunk starts at
+// multiples of 256 (see k_mle_sum_first)
+__device__ __forceinline__ void block_chunk(uint32_t items, uint32_t& begin, uint32_t& end) {
+    const uint32_t chunk = ((items + gridDim.x - 1) / gridDim.x + 255u) & ~255u;
+    begin = blockIdx.x * chunk;
+    end = begin + chunk < items ? begin + chunk : items;
+}
+
+// entries begin .. end of every one of a sumcheck's tables folded ONCE with the round's multiplier T: src 4q entries per table
+// -> dst 2q.  src and dst may be the same buffer with equal strides: a thread writes only slots it alone has read.
+__device__ __forceinline__ void fold_tables_chunk(const Fr* src, size_t src_stride, Fr* dst, size_t dst_stride, uint32_t n_tables, uint32_t q,
+                                                  const FixedMul& T, uint32_t begin, uint32_t end) {
+    for (uint32_t i = begin + threadIdx.x; i < end; i += blockDim.x) {
+        for (uint32_t m = 0; m < n_tables; ++m) {
+            const Fr* sm = src + (size_t)m * src_stride;
+            Fr* dm = dst + (size_t)m * dst_stride;
+            const Fr x0 = load_fr(sm + i), x1 = load_fr(sm + i + 2 * (size_t)q);
+            const Fr x2 = load_fr(sm + i + q), x3 = load_fr(sm + i + 3 * (size_t)q);
+            Fr lo, hi;
+            fr_fold_fixed2(x0, x1, x2, x3, T, lo, hi);
+            store_fr(dm + i, lo);
+            store_fr(dm + i + q, hi);
+        }
+    }
+}
 
 // what one thread accumulates a value in: a wide sum of elements at degree 1, a lazy sum of products above
 template <int D>
@@ -100,6 +133,123 @@ __device__ __forceinline__ void product_values_to_coeffs(const Fr (&v)[D + 1], F
         c[1] = c2;
         c[2] = fr_sub(fr_sub(fr_sub(v[1], v[0]), c2), v[2]);
         c[3] = v[0];
+    }
+}
+
+// the same into V >= D + 1 slots, right-aligned: zeros in front
+template <int D, int V>
+__device__ __forceinline__ void product_values_to_coeffs_right(const Fr (&v)[V], Fr (&c)[V]) {
+    if constexpr (V == D + 1) {
+        product_values_to_coeffs<D>(v, c);
+    } else {
+        Fr vd[D + 1], cd[D + 1];
+#pragma unroll
+        for (int k = 0; k <= D; ++k) vd[k] = v[k];
+        product_values_to_coeffs<D>(vd, cd);
+#pragma unroll
+        for (int k = 0; k < V; ++k) c[k] = k < V - D - 1 ? fr_zero() : cd[k - (V - D - 1)];
+    }
+}
+
+// ---- the round kernels' steps (one wave per sumcheck and round)
+
+// One term of a sum of products with term degrees <= MAXD: the blocks' partials of term t (degree d) of this sumcheck (p: block
+// 0's, K terms per block) totalled over the wave, the 2^(-256 (d - 1)) of the lazy and Montgomery reductions undone, values ->
+// coefficients, times c_k: thread 0's out, right-aligned in MAXD + 1 slots (highest degree first).  The other threads' is not set.
+template <int MAXD>
+__device__ __forceinline__ void term_total_coeffs(const ProductPartial* p, uint32_t nblk, uint32_t K, uint32_t t, uint32_t d, const Fr& ck,
+                                                  Fr (&out)[MAXD + 1]) {
+    static_assert(MAXD == 2 || MAXD == 3, "the zero-check's inner degree or the product path's");
+    constexpr int V = MAXD + 1;
+    Acc<10> tot[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) tot[k] = acc_zero<10>();
+    for (uint32_t i = threadIdx.x; i < nblk; i += 64) {
+        const ProductPartial* pp = p + (size_t)i * K + t;
+#pragma unroll
+        for (int k = 0; k < V; ++k)
+            if ((uint32_t)k <= d) acc_add_acc(tot[k], pp->s[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < V; ++k) tot[k] = wave_sum(tot[k]);
+    if (threadIdx.x != 0) return;
+    Fr v[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+        v[k] = acc_reduce(tot[k]);
+#pragma unroll
+        for (int m = 1; m < MAXD; ++m)
+            if ((uint32_t)m < d) v[k] = mont_mul(v[k], fr_r2());   // x 2^256 per lazy or Montgomery reduction taken
+    }
+    Fr c[V];
+    if (d == 1)
+        product_values_to_coeffs_right<1>(v, c);
+    else if (MAXD == 2 || d == 2)
+        product_values_to_coeffs_right<2>(v, c);
+    else if constexpr (MAXD == 3)
+        product_values_to_coeffs_right<3>(v, c);
+    const Fr ck_mont = to_mont(ck);
+#pragma unroll
+    for (int k = 0; k < V; ++k) out[k] = mont_mul(c[k], ck_mont);
+}
+
+// every term's, added up: thread 0's sum
+template <int MAXD>
+__device__ __forceinline__ void terms_total(const ProductPartial* p, uint32_t nblk, const SopTerms& ts, const SopCoeffs& cf, Fr (&sum)[MAXD + 1]) {
+#pragma unroll
+    for (int k = 0; k <= MAXD; ++k) sum[k] = fr_zero();
+    for (uint32_t t = 0; t < ts.n_terms; ++t) {
+        Fr c[MAXD + 1];
+        term_total_coeffs<MAXD>(p, nblk, ts.n_terms, t, sop_term_degree(ts.term[t]), cf.c[t], c);
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int k = 0; k <= MAXD; ++k) sum[k] = fr_add(sum[k], c[k]);
+        }
+    }
+}
+
+// the length rule of a merged polynomial (add_poly merges by exponent and drops zero sums, poly.rs:324-327): leading zero
+// coefficients dropped, one kept at least.  sum: S coefficients, highest degree first.
+template <int S>
+__device__ __forceinline__ uint32_t round_length(const Fr (&sum)[S]) {
+    uint32_t lead = 0;
+    bool leading = true;
+#pragma unroll
+    for (int k = 0; k < S - 1; ++k) {
+        leading = leading && fr_is_zero(sum[k]);
+        lead += leading ? 1u : 0u;
+    }
+    return (uint32_t)S - lead;
+}
+
+// Thread 0 publishes a round: the last D + 1 <= S of the slots (right-aligned; the ones in front hold zero) to the row, the row's
+// length, and r = multi_hash(the last len slots, key 0) as mimc7_multi_hash does it -- the slots indexed statically (no private
+// array in memory).  Returns r (canonical).
+template <int S>
+__device__ __forceinline__ Fr round_publish(const Fr (&sum)[S], uint32_t len, uint32_t D, size_t row, const Fr* __restrict__ cts,
+                                            Fr* __restrict__ out_coeffs, uint32_t* __restrict__ out_len, Fr* __restrict__ out_r) {
+    Fr* oc = out_coeffs + row * (D + 1);
+    Fr h = fr_zero();
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+        if ((uint32_t)k + D >= (uint32_t)S - 1u) oc[(uint32_t)k + D - ((uint32_t)S - 1u)] = sum[k];   // (an unused slot holds zero)
+        if ((uint32_t)k + len >= (uint32_t)S) {
+            const Fr a = to_mont(sum[k]);
+            h = fr_add(fr_add(h, a), mimc7_hash_mont(a, h, cts));
+        }
+    }
+    const Fr r = from_mont(h);
+    out_len[row] = len;
+    out_r[row] = r;
+    return r;
+}
+
+// after round n, the last fold of every table's two remaining entries: evals[b M + m] = T_m~(r_1 .. r_n)
+__device__ __forceinline__ void fold_last_entries(const Fr* __restrict__ work, size_t work_stride, uint32_t b, uint32_t n_tables,
+                                                  const Fr& r_mont, Fr* __restrict__ evals) {
+    for (uint32_t m = 0; m < n_tables; ++m) {
+        const Fr* t = work + ((size_t)b * n_tables + m) * work_stride;
+        evals[(size_t)b * n_tables + m] = fr_fold(t[0], t[1], r_mont);
     }
 }
 

@@ -155,6 +155,22 @@ def test_terms_that_cancel(ctx, n):
     assert got[0][0] == _model([A, B], [(P - k, (0, 1))], n)[0]
 
 
+def test_a_zero_table_in_the_middle_sumcheck_in_both_transcript_modes():
+    """A B C - A D at batch 3 with A the zero table in the middle sumcheck: its round vectors are all [0], its neighbours' are not.
+    n = 2 (the first pass and one fold, a chunk below 256 entries), 9 and 10 (one block and two blocks per sumcheck in round 1)."""
+    _, n_tables, terms = next(s for s in STRUCTURES if s[0] == "ABC-AD")
+    with Context(0) as c:
+        for mode in (N.GKR_TRANSCRIPT_HOST, N.GKR_TRANSCRIPT_DEVICE):
+            c.set_transcript(mode)
+            for n in (2, 9, 10):
+                rng = random.Random(1000 + n)
+                groups = [[factor("zero" if (b, m) == (1, 0) else "random", n, rng) for m in range(n_tables)] for b in range(3)]
+                got = _run(c, groups, n, terms)
+                assert got == [_model(g, terms, n) for g in groups], (mode, n)
+                assert got[1][0] == [[0]] * n and got[1][1] == [multi_hash([0], 0)] * n
+                assert all(len(v) == 4 for b in (0, 2) for v in got[b][0])
+
+
 # ---- d. bookkeeping ---------------------------------------------------------------------------------------------------------------------
 BOOKKEEPING = {
     "mixed degrees under D = 3": (3, [(1, (0, 1, 2)), (3, (1, 2)), (P - 5, (0,))]),

@@ -316,6 +316,24 @@ def test_a_satisfied_zero_check_and_terms_that_cancel(ctx, n):
             assert verify_sumcheck_zerocheck(proof, r, evals, terms, z, 0)
 
 
+def test_a_zero_table_in_the_middle_sumcheck_in_both_transcript_modes():
+    """A B - A C at batch 3 with A the zero table in the middle sumcheck: its round vectors are all [0], its neighbours' are not.
+    n = 2 (the first pass and one fold, a chunk below 256 entries), 9 and 10 (round 1 without and with an E_hi table; one block and
+    two blocks per sumcheck in round 1)."""
+    _, n_tables, terms = _structure("AB-AC")
+    with Context(0) as c:
+        for mode in (N.GKR_TRANSCRIPT_HOST, N.GKR_TRANSCRIPT_DEVICE):
+            c.set_transcript(mode)
+            for n in (2, 9, 10):
+                rng = random.Random(7600 + n)
+                groups = [[factor("zero" if (b, m) == (1, 0) else "random", n, rng) for m in range(n_tables)] for b in range(3)]
+                zs = [_random_point(rng, n) for _ in range(3)]
+                got = _run(c, groups, n, terms, zs)
+                assert got == [_model(g, terms, z, n) for g, z in zip(groups, zs)], (mode, n)
+                assert got[1][0] == [[0]] * n and got[1][1] == [multi_hash([0], 0)] * n
+                assert all(len(v) == 4 for b in (0, 2) for v in got[b][0])
+
+
 @pytest.mark.parametrize("n", [4, 10])
 def test_coefficients_zero_one_and_r_minus_one(ctx, n):
     terms = [(0, (0, 1)), (1, (1, 2)), (P - 1, (0,))]
