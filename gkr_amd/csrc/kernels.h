@@ -151,6 +151,8 @@ void launch_mle_multifold_small(int jin, const Fr* src, size_t src_stride, Fr* d
 // launch_mle_copy_weights) and leaves eight partial planes of S / 32 entries and mle_multifold2_partials(S) partials per table.
 constexpr uint32_t kMleFold2Planes = 8;
 uint32_t mle_multifold2_partials(uint32_t S);
+// tiles of 64 entries a block of the fold takes: one, or what option fold2_tiles forces
+uint32_t mle_multifold2_tiles(uint32_t S);
 void launch_mle_fine_sums(const MleSubPartial* partials, uint32_t nblk, const Fr* weights, uint32_t batch, MleHostRecSub* host_rec, uint32_t ticket,
                           hipStream_t s);
 void launch_mle_copy_weights(const Fr* src, Fr* dst, uint32_t batch, hipStream_t s);

@@ -562,52 +562,74 @@ __global__ void __launch_bounds__(256) k_mle_copy_weights(const uint32_t* __rest
 }
 
 // The fold.  S = 2^(n-5) inner outputs per table, I = S / 32 >= 256 entries of T''.  A block takes ONE 64-entry tile of i and four
-// consecutive c, one per wave: each wave multiplies its 64 finished inner outputs by w'_c (SGPRs) into an unreduced product,
-// the four are added through LDS and reduced once, and the block stores 64 entries of the partial plane P[c >> 2][i] -- eight
+// consecutive c, one per wave: each wave multiplies its 64 finished inner outputs by w'_c (SGPRs),
+// the four products are added through LDS, and the block stores 64 entries of the partial plane P[c >> 2][i] -- eight
 // planes of I entries per table, which the one-block pass after it adds up as it reads (k_mle_multifold_small).  Sums of
 // T'' for the next five rounds: a sub-block is I / 32 entries, g = min(I / 32, 64) lanes of the tile; the block leaves 64 / g
 // partials at ((64 it + lane) / g) * 8 + (c >> 2), so that each sub-block is a run of consecutive partials and
 // mle_total_and_publish(nblk = 8 I / g, jout = 5) totals them as any pass's.
-// Registers (120) and LDS (45 KB) put three blocks on a CU, one more than k_mle_multifold_mfma<5> has: what runs beside this kernel
-// on the side and late streams must fit into the 22 KB of LDS they leave, or it waits for the kernel's end (k_mle_fine_sums and
+// Registers (163, no scratch) and LDS (45 KB) put three blocks on a CU, one more than k_mle_multifold_mfma<5> has: what runs beside this
+// kernel on the side and late streams must fit into the 22 KB of LDS they leave, or it waits for the kernel's end (k_mle_fine_sums and
 // k_mle_multifold_small behind this fold do; the next group's digit matrices, 33 KB, wait -- they have a streaming pass of time).
-// grid = (I / 8, batch): block x = (c >> 2) * (I / 64) + it; block = 256
-__global__ void __launch_bounds__(256) k_mle_multifold2_mfma(const Fr* __restrict__ src, size_t src_stride, Fr* __restrict__ dst, size_t dst_stride,
+// The read is mfma_multifold_stream's rolling form (mfma_fold.h, kLoadFirst): the first table loads go out between the digit
+// matrix's global loads and its LDS stores, and every k-step's two loads are issued again as soon as its MFMAs have their
+// operands -- 14 - 16 KB per wave in flight from the first instruction to the last tile's last stage, on one 64-register buffer.
+// A block takes T consecutive tiles of one (table, cq), T a power of two up to I / 64, with one digit copy, one w'_c and one plan;
+// the loads of the next tile are in flight across the sink.  Per tile each wave reduces its own product (the four waves sit on four
+// SIMDs), the three behind the finishing wave leave theirs in LDS, and the finishing wave -- tile number mod 4 -- adds the four
+// canonical values, stores 64 entries and leaves the tile's partials: one barrier per tile, the slots alternate by tile parity.
+// T = 1 is what every launch takes (mle_multifold2_tiles: more tiles per block read slower); the option fold2_tiles forces more.
+// grid = (I / (8 T), batch): block x = (c >> 2) * (I / (64 T)) + it / T; block = 256
+__global__ void __launch_bounds__(256, 3) k_mle_multifold2_mfma(const Fr* __restrict__ src, size_t src_stride, Fr* __restrict__ dst, size_t dst_stride,
                                                              uint32_t S, const MfmaFoldPlan* __restrict__ plans, const Fr* __restrict__ w2,
-                                                             MleSubPartial* __restrict__ partials) {
-    __shared__ Lazy17 s_prod[3][64];
-    __shared__ __attribute__((aligned(16))) unsigned char digits[32 * 32 * (1 << kMfmaMaxJ)];
+                                                             MleSubPartial* __restrict__ partials, uint32_t T) {
+    __shared__ Fr s_prod[2][3][64];   // [tile parity][wave behind the finishing one][lane]
+    __shared__ __attribute__((aligned(16))) unsigned char digits[32 * 32 * (1 << kMfmaMaxJ) + 128];   // (+ the accumulators' start values)
     const Fr* s = src + (size_t)blockIdx.y * src_stride;
-    const uint32_t I = S >> kMfmaMaxJ, tiles = I >> 6;   // (powers of two)
-    const uint32_t it = blockIdx.x & (tiles - 1u), cq = blockIdx.x / tiles;
+    const uint32_t I = S >> kMfmaMaxJ, per = (I >> 6) / T;   // (powers of two; per: blocks of a (table, cq))
+    const uint32_t cq = blockIdx.x / per;
+    uint32_t it = (blockIdx.x & (per - 1u)) * T;
     const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t begin = 4u * cq * I + 64u * it;
     const Fr wc = load_fr(w2 + (size_t)blockIdx.y * kMleMaxSub + 4u * cq + wave);   // wave-uniform: scalar registers
-    Lazy17 prod = lazy_zero();
-    // (one iteration: begin + 256 only says that all four waves have a tile; wave w's is begin + w I)
-    mfma_multifold_stream<kMfmaMaxJ>(s, S, plans + blockIdx.y, begin, begin + 256u, 0u, digits,
-                                     [&](uint32_t, uint32_t, uint32_t, const Fr& y) { lazy_mac_s(prod, y, wc); }, I);
-    if (wave != 0u) s_prod[wave - 1u][lane] = prod;
-    __syncthreads();
-    if (wave != 0u) return;
-#pragma unroll
-    for (int w = 0; w < 3; ++w) lazy_add(prod, s_prod[w][lane]);
-    const Fr y = lazy_reduce(prod);
-    store_fr(dst + (size_t)blockIdx.y * dst_stride + (size_t)cq * I + 64u * it + lane, y);
+    Fr* d = dst + (size_t)blockIdx.y * dst_stride + (size_t)cq * I;
     const uint32_t sub = I >> 5, g = sub < 64u ? sub : 64u;
-    Acc<9> acc = acc_zero<9>();
-    acc_add_fr(acc, y);
-    for (uint32_t off = g >> 1; off >= 1u; off >>= 1) {
-        Acc<9> o;
+    MleSubPartial* part = partials + (size_t)blockIdx.y * (8u * (I / g)) + cq;
+    // (T iterations of one 64-entry tile, rot = 0: the tiles come in order; begin + 256 T only counts them and says that all four
+    // waves have a tile; wave w's is begin + w I)
+    mfma_multifold_stream<kMfmaMaxJ, true>(
+        s, S, plans + blockIdx.y, begin, begin + 256u * T, 0u, digits,
+        [&](uint32_t, uint32_t, uint32_t, const Fr& yw) {
+            Lazy17 prod = lazy_zero();
+            lazy_mac_s(prod, yw, wc);
+            Fr y = lazy_reduce(prod);   // canonical * Montgomery: this wave's canonical product
+            const uint32_t fin = it & 3u, buf = it & 1u;   // (block- and wave-uniform: the barrier below is)
+            if (wave != fin) store_fr(&s_prod[buf][(wave - fin - 1u) & 3u][lane], y);
+            // (one barrier per tile: the slots of this parity are written again two tiles on, behind the next tile's barrier, which
+            // this tile's finishing wave reaches only after it has read them)
+            __syncthreads();
+            if (wave == fin) {
 #pragma unroll
-        for (int l = 0; l < 9; ++l) o.l[l] = __shfl_down(acc.l[l], off, 64);
-        acc_add_acc(acc, o);
-    }
-    if ((lane & (g - 1u)) == 0u) {
-        MleSubPartial* p = partials + (size_t)blockIdx.y * (8u * (I / g)) + (size_t)((64u * it + lane) / g) * 8u + cq;
-        p->sum = acc;
-        p->dep = 0;
-    }
+                for (int w = 0; w < 3; ++w) y = fr_add(y, load_fr(&s_prod[buf][w][lane]));
+                store_fr(d + 64u * it + lane, y);
+                Acc<9> acc = acc_zero<9>();
+                acc_add_fr(acc, y);
+                for (uint32_t off = g >> 1; off >= 1u; off >>= 1) {
+                    Acc<9> o;
+#pragma unroll
+                    for (int l = 0; l < 9; ++l) o.l[l] = __shfl_down(acc.l[l], off, 64);
+                    acc_add_acc(acc, o);
+                }
+                if ((lane & (g - 1u)) == 0u) {
+                    MleSubPartial* p = part + (size_t)((64u * it + lane) / g) * 8u;
+                    p->sum = acc;
+                    p->dep = 0;
+                }
+            }
+            ++it;
+            __builtin_amdgcn_sched_barrier(0);   // (the sink stays whole: the next tile's k-steps are not drawn into it)
+        },
+        I, 64u);
 }
 
 // partials of a pass -> 2^jout canonical sub-block sums per table -> pinned host record (mle_total_and_publish).  Streaming
@@ -2916,11 +2938,25 @@ void launch_mle_copy_weights(const Fr* src, Fr* dst, uint32_t batch, hipStream_t
                        reinterpret_cast<uint32_t*>(dst));
 }
 
+// Tiles per block of the two-level first fold: a power of two, at most I / 64 = S / 2048.  Option fold2_tiles = k forces
+// min(k, I / 64), rounded down to a power of two; 0 is ONE tile at every size.  Measured for the headline's launch, 128 tables x
+// 2^20 (profiles/r24): every T > 1 reads slower, 2 by 5 %, 4 by 10 %, 8 and 16 by 12 - 14 % -- the resident blocks then work on T
+// times as many tables at once (mle_multifold_blocks above on what that costs).  Other launches were not measured; nothing
+// speaks for more tiles there.
+uint32_t mle_multifold2_tiles(uint32_t S) {
+    const uint32_t tiles = S >> 11;
+    const long long want = opt(OPT_fold2_tiles);
+    uint32_t T = 1;
+    while (2u * T <= tiles && 2ll * T <= want) T <<= 1;
+    return T;
+}
+
 // S = 2^(n-5) with 2^13 <= S <= 2^19; dst: eight planes of S / 32 entries per table; w2: device memory
 void launch_mle_multifold2(const Fr* src, size_t src_stride, Fr* dst, size_t dst_stride, uint32_t S, uint32_t batch, const void* plans, const Fr* w2,
                            MleSubPartial* partials, hipStream_t s) {
-    hipLaunchKernelGGL(k_mle_multifold2_mfma, dim3(S >> 8, batch), dim3(256), 0, s, src, src_stride, dst, dst_stride, S,
-                       static_cast<const MfmaFoldPlan*>(plans), w2, partials);
+    const uint32_t T = mle_multifold2_tiles(S);
+    hipLaunchKernelGGL(k_mle_multifold2_mfma, dim3((S >> 8) / T, batch), dim3(256), 0, s, src, src_stride, dst, dst_stride, S,
+                       static_cast<const MfmaFoldPlan*>(plans), w2, partials, T);
 }
 
 void launch_mle_round_reduce(const MlePartial* partials, uint32_t nblk, uint32_t batch, MleHostRec* host_rec,

@@ -168,7 +168,7 @@ __device__ __forceinline__ Fr mf_finish(const mf_v16i& a0, const mf_v16i& a1) {
 // The 2^JIN source entries of an output are taken in stages of (at most) eight k-steps: the loads of the next
 // stage (of this or the next iteration) are issued before the current stage's arithmetic, so a wave keeps
 // 2 x 16 KB in flight whatever JIN is.  lds: 32 * 32 * 2^JIN bytes for JIN > 2 (the digit matrix; it stays
-// in registers for JIN <= 2), unused otherwise.
+// in registers for JIN <= 2), unused otherwise; kLoadFirst: 128 bytes more.
 // `rot`: each block starts at its own iteration and wraps around, so the blocks of a launch do not walk
 // their chunks in step.
 // `sink(e0, h, c, y)`: what becomes of a finished output -- y is entry e0 + 32 h + c of the folded table, 32 h + c = the lane's place
@@ -176,18 +176,29 @@ __device__ __forceinline__ Fr mf_finish(const mf_v16i& a0, const mf_v16i& a1) {
 // the multilinear evaluation (kernels_mle_eval.hip) multiplies it into a sum and stores nothing.
 // `wave_stride`: entries between the tiles of neighbouring waves -- 64: the block's four tiles are consecutive (every caller but
 // the two-level first fold, whose waves take the same tile of four consecutive planes of the folded table: kernels.hip).
-template <int JIN, class Sink>
+// `iter_stride`: entries between a wave's consecutive tiles -- 256: the block walks [begin, end) (every caller but the two-level
+// first fold, whose four waves share ONE 64-entry tile per iteration: 64, and (end - begin) / 256 only counts its iterations).
+// kLoadFirst (JIN > 2, every wave has a tile): the table loads of the first stage are issued between the digit matrix's global
+// loads and its LDS stores, so that the block's first HBM latency runs beside the copy and its barrier, not after them.
+template <int JIN, bool kLoadFirst = false, class Sink>
 __device__ __forceinline__ void mfma_multifold_stream(const Fr* __restrict__ s, uint32_t S, const MfmaFoldPlan* __restrict__ plan,
                                                       uint32_t begin, uint32_t end, uint32_t rot, unsigned char* lds, Sink&& sink,
-                                                      uint32_t wave_stride = 64u) {
+                                                      uint32_t wave_stride = 64u, uint32_t iter_stride = 256u) {
     constexpr int NB = 1 << JIN;
     constexpr int KS = NB < 8 ? NB : 8;     // k-steps per stage
     constexpr int NST = NB / KS;            // stages per iteration: 1, 2 or 4
     constexpr bool kRegs = NB <= 4;         // digit matrix in registers (from eight k-steps on, LDS: the registers
                                             // are needed for the two load buffers)
     const uint32_t tid = threadIdx.x, lane = tid & 63u, c = lane & 31u, h = lane >> 5;
+    static_assert(!kLoadFirst || !kRegs, "kLoadFirst: the digit matrix goes through LDS");
+    constexpr int DG = 32 * 32 * NB / 16 / 256;   // kLoadFirst: 16-byte pieces of the digit matrix per thread of a 256-thread block
     mf_v4i wf[kRegs ? NB : 1];
-    if constexpr (kRegs) {
+    mf_v4u dg[kLoadFirst ? DG : 1];
+    if constexpr (kLoadFirst) {
+#pragma unroll
+        for (int i = 0; i < DG; ++i) dg[i] = reinterpret_cast<const mf_v4u*>(plan->digits)[tid + 256u * (uint32_t)i];
+        __builtin_amdgcn_sched_barrier(0);
+    } else if constexpr (kRegs) {
 #pragma unroll
         for (int b = 0; b < NB; ++b) wf[b] = *reinterpret_cast<const mf_v4i*>(plan->digits + ((b * 2 + h) * 32 + c) * 16);
     } else {
@@ -195,9 +206,22 @@ __device__ __forceinline__ void mfma_multifold_stream(const Fr* __restrict__ s, 
             reinterpret_cast<mf_v4u*>(lds)[i] = reinterpret_cast<const mf_v4u*>(plan->digits)[i];
         __syncthreads();
     }
+    // the accumulators' start values: in registers, or (kLoadFirst) in the 128 bytes of LDS behind the digit matrix, read again
+    // per iteration -- sixteen registers less across the sink
     mf_v16i init;
+    int start_word = 0;
+    if constexpr (kLoadFirst) {
+        if (tid < 32u) start_word = reinterpret_cast<const int*>(plan->start)[tid];
+    } else {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) init[r] = plan->start[h][r];
+        for (int r = 0; r < 16; ++r) init[r] = plan->start[h][r];
+    }
+    auto acc_start = [&]() -> mf_v16i {
+        if constexpr (kLoadFirst)
+            return *reinterpret_cast<const mf_v16i*>(lds + 32 * 32 * NB + 64u * h);
+        else
+            return init;
+    };
 
     // (readfirstlane: the compiler cannot see that tid >> 6 is the same on every lane, and the tile start e0 derived
     // from it must be, to sit in the scalar stream base below)
@@ -242,13 +266,68 @@ __device__ __forceinline__ void mfma_multifold_stream(const Fr* __restrict__ s, 
     uint32_t cur = rot % iters;
     auto next_pos = [&]() {   // entry offset of the iteration after the current one (wraps around the chunk)
         cur = cur + 1u == iters ? 0u : cur + 1u;
-        return begin + cur * 256u + woff;
+        return begin + cur * iter_stride + woff;
     };
     // (the scheduling barriers keep the compiler from hoisting a buffer's next loads above its last use, which
     // would cost a third and fourth buffer in registers)
     mf_v4u xa[2][KS], xb[2][KS];
-    uint32_t e0 = begin + cur * 256u + woff;
+    uint32_t e0 = begin + cur * iter_stride + woff;
     load_stage(e0, 0, xa);
+    if constexpr (kLoadFirst) {
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < DG; ++i) reinterpret_cast<mf_v4u*>(lds)[tid + 256u * (uint32_t)i] = dg[i];
+        if (tid < 32u) reinterpret_cast<int*>(lds + 32 * 32 * NB)[tid] = start_word;
+        __syncthreads();
+        // The rolling form: ONE buffer of eight k-steps.  The two loads of a k-step are issued again, for the next stage (of this
+        // or the next iteration), as soon as its two MFMAs have taken their operands, so a wave keeps 14 - 16 KB in flight at every
+        // point of the loop -- across the sink too -- on 64 data registers where the two buffers below take 128: what lets a looping
+        // block stay within the 168 registers of three blocks per CU.  The loads are pinned in the order they are waited for.
+        // The k-steps are reloaded in the order of the streams, S entries apart, so ONE wave-uniform pointer walks them (the empty
+        // asm keeps it one scalar pair: as 2^JIN loop-invariant stream offsets the addresses spill over into vector registers).
+        const uint32_t voff = c * 32u + 16u * h;
+        const uint64_t stream_bytes = (uint64_t)S * sizeof(Fr);
+        uint64_t step_bytes = stream_bytes;
+        uint64_t next = reinterpret_cast<uint64_t>(s + e0) + KS * stream_bytes;   // stage 1, k-step 0
+        auto load_step = [&](int k) {
+            asm volatile("" : "+s"(next));
+            // (an integer has no address space: said here, or the loads are flat ones, which the compiler waits for one by one)
+            typedef const __attribute__((address_space(1))) mf_v4u* GlobalPiece;
+            xa[0][k] = __builtin_nontemporal_load(reinterpret_cast<GlobalPiece>(next + voff));
+            xa[1][k] = __builtin_nontemporal_load(reinterpret_cast<GlobalPiece>(next + voff + 1024u));
+            next += step_bytes;
+        };
+        auto digit_frag = [&](int row) { return *reinterpret_cast<const mf_v4i*>(lds + ((row * 2 + h) * 32 + c) * 16); };
+        for (uint32_t it = 0; it < iters; ++it) {
+            const bool more = it + 1u < iters;
+            const uint32_t e1 = next_pos();
+            mf_v16i a0 = acc_start(), a1 = a0;
+            mf_v4i w = digit_frag(0);
+            auto steps = [&](int st, auto&& reload) {
+#pragma unroll
+                for (int k = 0; k < KS; ++k) {
+                    const mf_v4i wn = digit_frag((st * KS + k + 1) % NB);   // (the next k-step's fragment, ahead of this one's MFMAs)
+                    const mf_v4u f0 = xa[0][k] ^ 0x80808080u, f1 = xa[1][k] ^ 0x80808080u;
+                    a0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(w, (mf_v4i)f0, a0, 0, 0, 0);
+                    a1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(w, (mf_v4i)f1, a1, 0, 0, 0);
+                    reload(k);
+                    w = wn;
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            };
+#pragma unroll
+            for (int st = 0; st + 1 < NST; ++st) steps(st, [&](int k) { load_step(k); });
+            // (No branch around the last iteration's reloads -- it would drain the loads in flight at every one, and a second copy
+            // of the stage costs a second pair of accumulators: they read the first 2 KiB of the digit matrix again, which is in
+            // bounds and sits in L2, and nobody takes their results.)
+            next = more ? reinterpret_cast<uint64_t>(s + e1) : reinterpret_cast<uint64_t>(plan->digits);
+            step_bytes = more ? stream_bytes : 0u;
+            steps(NST - 1, [&](int k) { load_step(k); });
+            store_entry(e0, a0, a1);
+            e0 = e1;
+        }
+        return;
+    }
     if constexpr (NST == 1) {
         // one stage per iteration: iterations alternate between the two buffers
         for (uint32_t it = 0; it < iters; it += 2u) {
@@ -256,7 +335,7 @@ __device__ __forceinline__ void mfma_multifold_stream(const Fr* __restrict__ s, 
             const uint32_t e1 = next_pos();
             if (more1) load_stage(e1, 0, xb);
             {
-                mf_v16i a0 = init, a1 = init;
+                mf_v16i a0 = acc_start(), a1 = a0;
                 mac_stage(0, xa, a0, a1);
                 store_entry(e0, a0, a1);
             }
@@ -266,7 +345,7 @@ __device__ __forceinline__ void mfma_multifold_stream(const Fr* __restrict__ s, 
             e0 = next_pos();
             if (more2) load_stage(e0, 0, xa);
             {
-                mf_v16i a0 = init, a1 = init;
+                mf_v16i a0 = acc_start(), a1 = a0;
                 mac_stage(0, xb, a0, a1);
                 store_entry(e1, a0, a1);
             }
@@ -277,7 +356,7 @@ __device__ __forceinline__ void mfma_multifold_stream(const Fr* __restrict__ s, 
         for (uint32_t it = 0; it < iters; ++it) {
             const bool more = it + 1u < iters;
             const uint32_t e1 = next_pos();
-            mf_v16i a0 = init, a1 = init;
+            mf_v16i a0 = acc_start(), a1 = a0;
 #pragma unroll
             for (int st = 0; st < NST; st += 2) {
                 load_stage(e0, st + 1, xb);
