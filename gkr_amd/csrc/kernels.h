@@ -120,8 +120,10 @@ uint32_t mle_pass_blocks(uint32_t items, uint32_t jout, uint32_t batch);
 uint32_t mle_multifold_blocks(uint32_t S, uint32_t jout, uint32_t batch);
 bool mle_multifold_uses_mfma(uint32_t S, uint32_t nblk);
 // pass 0 (launch_mle_sub_sums): k_mle_sub_sums, or for streaming launches (no publish, chunk = len / nblk a multiple of 256 entries, nblk a
-// multiple of 4) its pipelined form k_mle_sub_sums_stream -- the same partials, bit for bit
-constexpr int kMlePass0Stream = 2;   // what option pass0_stream = 0 means: 1 k_mle_sub_sums always, 2 the pipelined form where it applies
+// multiple of 4) its pipelined form k_mle_sub_sums_stream (a wave per one or two partials, its loads in flight in two sets), or, for
+// the launches of the two-partial form, k_mle_sub_sums_roll (a wave per partial, ONE buffer of sixteen loads each reloaded as soon as
+// it is added, the blocks of an XCD on one contiguous eighth of the launch) -- the same partials, bit for bit
+constexpr int kMlePass0Stream = 3;   // what option pass0_stream = 0 means: 1 k_mle_sub_sums always, 2 the pipelined form where it applies, 3 the rolling form where the deeper pipelined form applies
 // launches of at least this many partials (and chunks of whole 512 entries) take the form with sixteen loads per lane and two partials per
 // wave: 2 partials x 12 resident waves x 256 CUs x 4 generations.  Reasoned, not tuned: only 128 tables x 1024 partials was measured
 // (profiles/r22); what smaller launches take is a guess that keeps their block count at the chip's size or above

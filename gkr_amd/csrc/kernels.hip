@@ -455,6 +455,107 @@ __global__ void __launch_bounds__(256) k_mle_sub_sums_stream(const Fr* __restric
     finish(out);
 }
 
+// (the two-set form's add_set and finish as functions, for the rolling form below: the two-set kernels keep their own text, which
+// compiles to other instructions than these)
+// one 16-byte piece into a lane's half sum and its x_n test (the neighbour entry's same half is lane ^ 2's register)
+__device__ __forceinline__ void half_piece_eat(uint32_t (&acc)[5], uint32_t& diff, const mf_v4u& v) {
+    half_acc_add(acc, v);
+    diff |= (v.x ^ (uint32_t)__builtin_amdgcn_mov_dpp((int)v.x, 0x4E, 0xF, 0xF, true)) |
+            (v.y ^ (uint32_t)__builtin_amdgcn_mov_dpp((int)v.y, 0x4E, 0xF, 0xF, true)) |
+            (v.z ^ (uint32_t)__builtin_amdgcn_mov_dpp((int)v.z, 0x4E, 0xF, 0xF, true)) |
+            (v.w ^ (uint32_t)__builtin_amdgcn_mov_dpp((int)v.w, 0x4E, 0xF, 0xF, true));
+}
+
+// a partial ends: the two halves at bit 0 and bit 128 of an Acc<9>, a sum over the wave, one store by lane 0
+__device__ __forceinline__ void half_sums_finish(const uint32_t (&acc)[5], uint32_t diff, uint32_t lane, MleSubPartial* p) {
+    const bool odd = (lane & 1u) != 0u;
+    Acc<9> s;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        s.l[i] = odd ? 0u : acc[i];
+        s.l[4 + i] = odd ? acc[i] : (i == 0 ? acc[4] : 0u);
+    }
+    s.l[8] = odd ? acc[4] : 0u;
+    s = wave_sum(s);
+    const uint32_t dep = __any(diff != 0u) ? 1u : 0u;
+    if (lane == 0) {
+        p->sum = s;
+        p->dep = dep;
+    }
+}
+
+// The rolling form (option pass0_stream = 3): the same contract and the same pieces, ONE buffer of U pieces per lane.  A piece is
+// loaded again, U steps ahead, the moment it has been added, so the wait before every step is vmcnt(U - 1): U - 1 or U loads of
+// 1 KiB per wave in flight at every point of the loop, where the two-set form swings between U and U / 2 (the first fold's read
+// loop, mfma_fold.h "the rolling form").  The reloads run through the wave's range in order, so ONE wave-uniform pointer walks it
+// -- a scalar pair, a 32-bit lane offset and immediates up to 3 KiB (the empty asm keeps it scalar) -- and the loop carries no
+// vector address.  Loads pinned in the order they are waited for, the prologue's too; the last round peeled, the "partial
+// ended" branch (PPW > 1) after the round's loads: no load behind a branch.
+// XCD: which range a block takes.  Blocks are handed to the eight XCDs in turn, so in the grid's own order every XCD reads every
+// eighth 32 KiB of the tables; with XCD set, block L takes the (L >> 3)-th range of the (L & 7)-th of eight contiguous runs of the
+// grid, so the blocks that share an XCD read one contiguous eighth of the launch.  The partials do not depend on it, only where
+// each block's lie; the placement of blocks is no contract of the hardware, so this is a choice for speed alone, and it is what
+// the form gains: measured (profiles/r25) the rolling buffer by itself reads at the two-set form's rate, with the runs 2 - 3 % faster.
+// grid = (nblk / (W PPW), batch), block = 64 W threads, W = 1, 2 or 4 waves (nothing ties a block's waves together: no LDS, no
+// barrier); chunk % (32 U) == 0; never publishes.  launch_mle_sub_sums takes <16, 1, true> in blocks of four waves.
+template <int U, int PPW, bool XCD>
+__global__ void __launch_bounds__(256) k_mle_sub_sums_roll(const Fr* __restrict__ tables, size_t table_stride, uint32_t chunk, uint32_t nblk,
+                                                           MleSubPartial* __restrict__ partials) {
+    static_assert(U >= 4 && U % 4 == 0, "the pointer moves once per four pieces");
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint32_t bx = blockIdx.x, by = blockIdx.y;
+    if constexpr (XCD) {
+        // block L of the grid's linear order becomes the (L >> 3)-th block of the (L & 7)-th of eight runs of the grid (the
+        // bijective form: the first nwg % 8 runs are one block longer)
+        const uint32_t nwg = gridDim.x * gridDim.y, L = by * gridDim.x + bx, q = nwg >> 3, r = nwg & 7u, run = L & 7u;
+        const uint32_t M = (run < r ? run * (q + 1u) : r * (q + 1u) + (run - r) * q) + (L >> 3);
+        by = M / gridDim.x;
+        bx = M - by * gridDim.x;
+    }
+    const uint32_t p0 = (bx * (blockDim.x >> 6) + wave) * (uint32_t)PPW;   // the wave's first partial
+    const uint32_t rpp = chunk / (32u * U);                                // rounds of U steps per partial
+    MleSubPartial* out = partials + (size_t)by * nblk + p0;
+    const uint32_t voff = lane * 16u;
+    uint64_t next = reinterpret_cast<uint64_t>(tables + (size_t)by * table_stride + (size_t)p0 * chunk);
+
+    mf_v4u x[U];
+    uint32_t acc[5] = {0u, 0u, 0u, 0u, 0u}, diff = 0u;
+    auto load_step = [&](int u) {
+        asm volatile("" : "+s"(next));
+        // (an integer has no address space: said here, or the loads are flat ones, which the compiler waits for one by one)
+        typedef const __attribute__((address_space(1))) mf_v4u* GlobalPiece;
+        x[u] = __builtin_nontemporal_load(reinterpret_cast<GlobalPiece>(next + voff) + 64 * (u & 3));
+        if ((u & 3) == 3) next += 4096u;
+    };
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        load_step(u);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    [[maybe_unused]] uint32_t left = rpp;
+    for (uint32_t r = (uint32_t)PPW * rpp - 1u; r != 0u; --r) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            half_piece_eat(acc, diff, x[u]);
+            load_step(u);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if constexpr (PPW > 1) {
+            if (--left == 0u) {
+                half_sums_finish(acc, diff, lane, out++);
+#pragma unroll
+                for (int i = 0; i < 5; ++i) acc[i] = 0u;
+                diff = 0u;
+                left = rpp;
+            }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) half_piece_eat(acc, diff, x[u]);
+    half_sums_finish(acc, diff, lane, out);
+}
+
 // one pass: bind JIN variables with the weights w[0 .. 2^JIN) (Montgomery, wave-uniform), write the
 // folded table of S entries, accumulate its sub-block sums.  grid = (nblk, batch), chunk = S / nblk.
 template <int JIN>
@@ -2810,19 +2911,26 @@ uint32_t mle_pass_blocks(uint32_t items, uint32_t jout, uint32_t batch) {
 // and launches of few tables, which the deeper form would put on fewer blocks than the chip has CUs).  Only the headline's launch
 // (128 tables x 1024 partials) was measured: there the deeper form is ahead; the threshold and the choice below it are reasoned, small
 // launches were not tuned (a lone 2^20-point table runs the shallow form as 256 blocks).  0: k_mle_sub_sums.
-// Option pass0_stream = 1 keeps k_mle_sub_sums everywhere, 2 asks for the pipelined form wherever it applies.
+// Option pass0_stream = 1 keeps k_mle_sub_sums everywhere, 2 asks for the pipelined form wherever it applies, 3 (the default,
+// kernels.h kMlePass0Stream) gives the launches of the deeper form to the rolling form instead: k_mle_sub_sums_roll<16, 1, true>, a
+// partial per wave, blocks of four waves, every XCD on its own eighth of the launch -- the variant that won in the step
+// (profiles/r25; <16, 2> in blocks of two waves was level with it and stretched the side stream's kernels).  The other launches are
+// what option 2 makes them.
 static int mle_sub_sums_stream_form(uint32_t len, uint32_t batch, uint32_t nblk, bool publishes) {
-    const long long want = opt(OPT_pass0_stream) == 1 || opt(OPT_pass0_stream) == 2 ? opt(OPT_pass0_stream) : kMlePass0Stream;
-    if (want != 2 || publishes || nblk == 0 || len % nblk != 0) return 0;
+    const long long o = opt(OPT_pass0_stream);
+    const long long want = o >= 1 && o <= 3 ? o : kMlePass0Stream;
+    if (want < 2 || publishes || nblk == 0 || len % nblk != 0) return 0;
     const uint32_t chunk = len / nblk;
-    if (chunk % 512u == 0 && nblk % 8u == 0 && (uint64_t)batch * nblk >= kMlePass0DeepMinPartials) return 2;
+    if (chunk % 512u == 0 && nblk % 8u == 0 && (uint64_t)batch * nblk >= kMlePass0DeepMinPartials) return want == 3 ? 3 : 2;
     return chunk % 256u == 0 && nblk % 4u == 0 ? 1 : 0;
 }
 
 void launch_mle_sub_sums(const Fr* tables, size_t stride, uint32_t len, uint32_t batch, uint32_t nblk, MleSubPartial* partials,
                          hipStream_t s, const MlePublish* publish) {
     const int form = mle_sub_sums_stream_form(len, batch, nblk, publish != nullptr);
-    if (form == 2)
+    if (form == 3)
+        hipLaunchKernelGGL((k_mle_sub_sums_roll<16, 1, true>), dim3(nblk / 4u, batch), dim3(256), 0, s, tables, stride, len / nblk, nblk, partials);
+    else if (form == 2)
         hipLaunchKernelGGL((k_mle_sub_sums_stream<16, 2>), dim3(nblk / 8u, batch), dim3(256), 0, s, tables, stride, len / nblk, nblk, partials);
     else if (form == 1)
         hipLaunchKernelGGL((k_mle_sub_sums_stream<8, 1>), dim3(nblk / 4u, batch), dim3(256), 0, s, tables, stride, len / nblk, nblk, partials);

@@ -287,7 +287,8 @@ int  gkr_sumcheck_mle(gkr_ctx *ctx, const gkr_fr *table, int n, gkr_fr *out_coef
  * contiguous (table b starts at d_tables + b * 2^n elements).  Inputs are not
  * modified.  Outputs are host arrays of batch x n rows.  Kernel forms behind it, the same bytes whichever is chosen: option
  * first_fold_levels (ten variables bound in the first fold's one read, 18 <= n <= 24) and option pass0_stream (pass 0 of a
- * streaming launch as a pipelined read: 1 a block per partial sum, 2 a wave per partial with its loads kept in flight); option
+ * streaming launch as a pipelined read: 1 a block per partial sum, 2 a wave per partial with its loads kept in flight, 3 the
+ * same through one rolling load buffer on the large launches, the default); option
  * fold2_tiles (64-entry tiles a block of that first fold takes: 0 one, k at most k). */
 int  gkr_sumcheck_mle_batch_device(gkr_ctx *ctx, const void *d_tables, int n, int batch,
                                    gkr_fr *out_coeffs, uint32_t *out_len, gkr_fr *out_r);
