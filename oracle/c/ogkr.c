@@ -473,6 +473,136 @@ static void eq_table(int k, const ogkr_fr *z, u64 (*e)[4]) {
     }
 }
 
+/* prove_sumcheck on g = sum_k c_k prod_f T_t(k,f) (tests/sop_model.py restates the rules), in ogkr_sumcheck_product's way: per
+ * index EVERY term is multiplied out into its degree + 1 coefficients and scaled by c_k, the scaled coefficients are summed
+ * exponent by exponent over the terms and the indices, every sum and product reduced at once.  No evaluation points, no
+ * interpolation, no division.  The length rule is BY VALUE in every round, the last included: leading zero coefficients are
+ * dropped, one is kept at least, so g == 0 gives [0].  Every table folds once per round, whatever number of terms name it.
+ * t: the M working tables of `len` entries each in Montgomery form, overwritten; cm: the coefficients in Montgomery form. */
+static void sop_on(u64 (*t)[4], size_t len, int n, int M, const ogkr_sop_term *terms, u64 (*cm)[4], int n_terms, int D,
+                   ogkr_fr *out_coeffs, uint32_t *out_len, ogkr_fr *out_r, ogkr_fr *out_evals, int nt) {
+    const ogkr_fr zero = {{0, 0, 0, 0}};
+    for (int j = 0; j < n; ++j) {
+        const size_t h = len >> (j + 1);
+        u64 c[4][4];   /* c[e]: coefficient of X^e, Montgomery form */
+        memset(c, 0, sizeof c);
+#pragma omp parallel num_threads(nt)
+        {
+            u64 local[4][4];
+            memset(local, 0, sizeof local);
+#pragma omp for schedule(static) nowait
+            for (size_t i = 0; i < h; ++i) {
+                for (int k = 0; k < n_terms; ++k) {
+                    const int dk = terms[k].degree;
+                    u64 poly[4][4], nxt[4][4], diff[4], a[4], b[4];
+                    size_t at = (size_t)terms[k].table[0] * len + i;
+                    memcpy(poly[0], t[at], 32);
+                    fr_sub(t[at + h], t[at], poly[1]);
+                    for (int f = 1; f < dk; ++f) {   /* poly (degree f) times (lo + X diff) */
+                        at = (size_t)terms[k].table[f] * len + i;
+                        const u64 *lo = t[at];
+                        fr_sub(t[at + h], lo, diff);
+                        mont_mul(poly[0], lo, nxt[0]);
+                        for (int e = 1; e <= f; ++e) {
+                            mont_mul(poly[e], lo, a);
+                            mont_mul(poly[e - 1], diff, b);
+                            fr_add(a, b, nxt[e]);
+                        }
+                        mont_mul(poly[f], diff, nxt[f + 1]);
+                        memcpy(poly, nxt, (size_t)(f + 2) * 32);
+                    }
+                    for (int e = 0; e <= dk; ++e) {
+                        mont_mul(poly[e], cm[k], a);
+                        fr_add(local[e], a, local[e]);
+                    }
+                }
+            }
+#pragma omp critical(ogkr_sop)
+            for (int e = 0; e <= D; ++e) fr_add(c[e], local[e], c[e]);
+        }
+        ogkr_fr *row = out_coeffs + (size_t)j * (D + 1);   /* highest degree first */
+        for (int e = 0; e <= D; ++e) from_mont(c[D - e], row[e].l);
+        int length = D + 1;
+        while (length > 1 && !(row[D + 1 - length].l[0] | row[D + 1 - length].l[1] | row[D + 1 - length].l[2] | row[D + 1 - length].l[3]))
+            --length;
+        out_len[j] = (uint32_t)length;
+        ogkr_multi_hash(row + (D + 1 - length), (size_t)length, &zero, &out_r[j]);
+        u64 rm[4];
+        to_mont(out_r[j].l, rm);
+        for (int m = 0; m < M; ++m) fold_table(t + (size_t)m * len, h, rm, nt);
+    }
+    for (int m = 0; m < M; ++m) from_mont(t[(size_t)m * len], out_evals[m].l);
+}
+
+/* the largest term degree, or 0 for a term list sop_on must not see */
+static int sop_check_terms(int n_tables, const ogkr_sop_term *terms, const ogkr_fr *term_coeffs, int n_terms, int max_degree) {
+    if (!terms || !term_coeffs || n_terms < 1 || n_terms > OGKR_SOP_MAX_TERMS) return 0;
+    int D = 0;
+    for (int k = 0; k < n_terms; ++k) {
+        if (terms[k].degree < 1 || terms[k].degree > max_degree || geq_mod(term_coeffs[k].l)) return 0;
+        for (int f = 0; f < terms[k].degree; ++f)
+            if (terms[k].table[f] >= n_tables) return 0;
+        if (terms[k].degree > D) D = terms[k].degree;
+    }
+    return D;
+}
+
+int ogkr_sumcheck_sop(const ogkr_fr *tables, int n, int n_tables, const ogkr_sop_term *terms, const ogkr_fr *term_coeffs,
+                      int n_terms, ogkr_fr *out_coeffs, uint32_t *out_len, ogkr_fr *out_r, ogkr_fr *out_evals, int threads) {
+    if (n < 2 || n > 40 || n_tables < 1 || n_tables > OGKR_SOP_MAX_TABLES) return -1;
+    const int D = sop_check_terms(n_tables, terms, term_coeffs, n_terms, 3);
+    if (!D) return -1;
+    if (!cts_ready) init_constants();
+    const int nt = set_threads(threads);
+    const size_t len = (size_t)1 << n;
+    u64(*t)[4] = malloc((size_t)n_tables * len * 32);
+    if (!t) return -2;
+#pragma omp parallel for schedule(static) num_threads(nt)
+    for (size_t i = 0; i < (size_t)n_tables * len; ++i) to_mont(tables[i].l, t[i]);
+    u64 cm[OGKR_SOP_MAX_TERMS][4];
+    for (int k = 0; k < n_terms; ++k) to_mont(term_coeffs[k].l, cm[k]);
+    sop_on(t, len, n, n_tables, terms, cm, n_terms, D, out_coeffs, out_len, out_r, out_evals, nt);
+    free(t);
+    return 0;
+}
+
+/* The zero-check sum_x eq(z, x) g(x) in its EXPLICIT form: eq(z, .) is written out as a table of 2^n entries (eq_table above),
+ * put in front of the caller's tables, and ogkr_sumcheck_sop's rounds run on the M + 1 tables with table 0 in front of every
+ * term.  (The library and tests/zerocheck_model.py never hold that table; holding it is what makes this an oracle for them.) */
+int ogkr_sumcheck_zerocheck(const ogkr_fr *tables, int n, int n_tables, const ogkr_sop_term *terms, const ogkr_fr *term_coeffs,
+                            int n_terms, const ogkr_fr *z, ogkr_fr *out_coeffs, uint32_t *out_len, ogkr_fr *out_r,
+                            ogkr_fr *out_evals, ogkr_fr *out_eq, int threads) {
+    if (n < 2 || n > 40 || n_tables < 1 || n_tables > OGKR_SOP_MAX_TABLES || !z) return -1;
+    const int d = sop_check_terms(n_tables, terms, term_coeffs, n_terms, 2);
+    if (!d) return -1;
+    for (int j = 0; j < n; ++j)
+        if (geq_mod(z[j].l)) return -1;
+    if (!cts_ready) init_constants();
+    const int nt = set_threads(threads), M = n_tables + 1;
+    const size_t len = (size_t)1 << n;
+    u64(*t)[4] = malloc((size_t)M * len * 32);
+    if (!t) return -2;
+    eq_table(n, z, t);   /* canonical values */
+#pragma omp parallel for schedule(static) num_threads(nt)
+    for (size_t i = 0; i < len; ++i) to_mont(t[i], t[i]);
+#pragma omp parallel for schedule(static) num_threads(nt)
+    for (size_t i = 0; i < (size_t)n_tables * len; ++i) to_mont(tables[i].l, t[len + i]);
+    ogkr_sop_term lifted[OGKR_SOP_MAX_TERMS];
+    u64 cm[OGKR_SOP_MAX_TERMS][4];
+    for (int k = 0; k < n_terms; ++k) {
+        lifted[k].degree = (uint8_t)(terms[k].degree + 1);
+        lifted[k].table[0] = 0;
+        for (int f = 0; f < terms[k].degree; ++f) lifted[k].table[f + 1] = (uint8_t)(terms[k].table[f] + 1);
+        to_mont(term_coeffs[k].l, cm[k]);
+    }
+    ogkr_fr evals[OGKR_SOP_MAX_TABLES + 1];
+    sop_on(t, len, n, M, lifted, cm, n_terms, d + 1, out_coeffs, out_len, out_r, evals, nt);
+    *out_eq = evals[0];
+    memcpy(out_evals, evals + 1, (size_t)n_tables * sizeof(ogkr_fr));
+    free(t);
+    return 0;
+}
+
 int ogkr_predicate_tables(int k_i, int k_next, const uint8_t *gate_type, const uint32_t *left,
                           const uint32_t *right, const ogkr_fr *z, ogkr_fr *A, ogkr_fr *M) {
     if (k_i < 0 || k_i > 30 || k_next < 1 || k_next > 15) return -1;

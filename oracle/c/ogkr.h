@@ -63,6 +63,26 @@ int ogkr_sumcheck_mle_inplace(ogkr_fr *table, int n, ogkr_fr *out_coeffs, uint32
 int ogkr_sumcheck_product(const ogkr_fr *tables, int n, int degree, ogkr_fr *out_coeffs, uint32_t *out_len,
                           ogkr_fr *out_r, ogkr_fr *out_evals, int threads);
 
+/* prove_sumcheck on g = sum_k c_k prod_f T_t(k,f) over n_tables (1 .. 8) multilinear tables of 2^n evaluations, table m at
+ * tables + m * 2^n: the C twin of tests/sop_model.py (its docstring has the rules).  Term k is the product of `degree`
+ * (1 .. 3) tables table[0 .. degree - 1], scaled by the canonical term_coeffs[k]; 1 .. 8 terms.  Per index every term is
+ * multiplied out and scaled, the sums are taken coefficient by coefficient; the length rule is by value in every round.
+ * out_coeffs: n rows of D + 1 slots (D the largest term degree), right-aligned, highest degree first, unused slots
+ * zero; out_evals: the n_tables entries left after the last fold.  -1: a bad shape, term or coefficient; -2: no memory. */
+#define OGKR_SOP_MAX_TABLES 8
+#define OGKR_SOP_MAX_TERMS  8
+typedef struct { uint8_t degree; uint8_t table[3]; } ogkr_sop_term;
+int ogkr_sumcheck_sop(const ogkr_fr *tables, int n, int n_tables, const ogkr_sop_term *terms, const ogkr_fr *term_coeffs,
+                      int n_terms, ogkr_fr *out_coeffs, uint32_t *out_len, ogkr_fr *out_r, ogkr_fr *out_evals, int threads);
+
+/* The zero-check sum_x eq(z, x) g(x), g as above with term degrees 1 .. 2, in the EXPLICIT form: eq(z, .) is materialised
+ * (2^n entries) and ogkr_sumcheck_sop's rounds run on {eq, T_0 ..} with every term prefixed by table 0.  z: n canonical
+ * elements, variable 1 = the most significant index bit.  out_coeffs: n rows of D + 2 slots (D the largest term degree);
+ * out_evals: the n_tables tables' entries left; out_eq: the eq table's.  Errors as above. */
+int ogkr_sumcheck_zerocheck(const ogkr_fr *tables, int n, int n_tables, const ogkr_sop_term *terms, const ogkr_fr *term_coeffs,
+                            int n_terms, const ogkr_fr *z, ogkr_fr *out_coeffs, uint32_t *out_len, ogkr_fr *out_r,
+                            ogkr_fr *out_evals, ogkr_fr *out_eq, int threads);
+
 /* prove_sumcheck_opt for one layer: gates g = 0..2^k_i-1 of type gate_type[g]
  * (0 add, 1 mult) with operands left[g], right[g] in [0, 2^k_next); z has k_i
  * entries; W has 2^k_next evaluations.  out_coeffs: 2*k_next rows of 3 slots,

@@ -148,6 +148,67 @@ def sumcheck_product_raw(tables_limbs, n, degree, threads=0):
     return C, L, R, E
 
 
+class _SopTerm(ctypes.Structure):
+    _fields_ = [("degree", ctypes.c_uint8), ("table", ctypes.c_uint8 * 3)]
+
+
+def _sop_terms(terms, max_degree):
+    """[(coeff, (table indices ..)), ..] -> (ogkr_sop_term array, coefficients (n_terms, 4), the largest term degree)."""
+    terms = list(terms)
+    if not terms or any(not 1 <= len(idx) <= max_degree or any(not 0 <= i < 256 for i in idx) for _, idx in terms):
+        raise ValueError("1 or more terms of 1 .. %d table indices expected" % max_degree)
+    arr = (_SopTerm * len(terms))()
+    for k, (_, idx) in enumerate(terms):
+        arr[k].degree = len(idx)
+        for f, i in enumerate(idx):
+            arr[k].table[f] = i
+    return arr, to_limbs([c for c, _ in terms]), max(len(idx) for _, idx in terms)
+
+
+def sumcheck_sop_raw(tables_limbs, n, n_tables, terms, threads=0):
+    """ogkr_sumcheck_sop on n_tables tables of 2^n entries, one after the other, terms [(coeff, (table indices ..)), ..]
+    -> (coeffs (n, D + 1, 4) uint64 right-aligned, lens (n,) uint32, r (n, 4) uint64, evals (n_tables, 4) uint64), D the largest
+    term degree: one sumcheck's slice of what gkr_sumcheck_sop_batch_device returns."""
+    tables_limbs = np.ascontiguousarray(tables_limbs, dtype=np.uint64)
+    if n_tables < 1 or tables_limbs.size != (n_tables << n) * 4:
+        raise ValueError("n_tables tables of 2^n entries expected")
+    arr, coeffs, D = _sop_terms(terms, 3)
+    C = np.zeros((n, D + 1, 4), dtype=np.uint64)
+    L = np.zeros(n, dtype=np.uint32)
+    R = np.zeros((n, 4), dtype=np.uint64)
+    E = np.zeros((n_tables, 4), dtype=np.uint64)
+    fn = lib().ogkr_sumcheck_sop
+    fn.restype = ctypes.c_int
+    rc = fn(_p(tables_limbs), ctypes.c_int(n), ctypes.c_int(n_tables), ctypes.cast(arr, ctypes.c_void_p), _p(coeffs), ctypes.c_int(len(arr)),
+            _p(C), _p(L), _p(R), _p(E), ctypes.c_int(threads if threads > 0 else usable_threads()))
+    if rc:
+        raise ValueError("ogkr_sumcheck_sop rc=%d" % rc)
+    return C, L, R, E
+
+
+def sumcheck_zerocheck_raw(tables_limbs, n, n_tables, terms, z_limbs, threads=0):
+    """ogkr_sumcheck_zerocheck (the eq table materialised) on n_tables tables of 2^n entries, terms of 1 or 2 indices, z (n, 4)
+    -> (coeffs (n, D + 2, 4), lens (n,), r (n, 4), evals (n_tables, 4), eq_r (4,)), D the largest term degree: one sumcheck's slice
+    of what gkr_sumcheck_zerocheck_batch_device returns."""
+    tables_limbs = np.ascontiguousarray(tables_limbs, dtype=np.uint64)
+    z_limbs = np.ascontiguousarray(z_limbs, dtype=np.uint64)
+    if n_tables < 1 or tables_limbs.size != (n_tables << n) * 4 or z_limbs.size != 4 * n:
+        raise ValueError("n_tables tables of 2^n entries and a point of n entries expected")
+    arr, coeffs, d = _sop_terms(terms, 2)
+    C = np.zeros((n, d + 2, 4), dtype=np.uint64)
+    L = np.zeros(n, dtype=np.uint32)
+    R = np.zeros((n, 4), dtype=np.uint64)
+    E = np.zeros((n_tables, 4), dtype=np.uint64)
+    Q = np.zeros(4, dtype=np.uint64)
+    fn = lib().ogkr_sumcheck_zerocheck
+    fn.restype = ctypes.c_int
+    rc = fn(_p(tables_limbs), ctypes.c_int(n), ctypes.c_int(n_tables), ctypes.cast(arr, ctypes.c_void_p), _p(coeffs), ctypes.c_int(len(arr)),
+            _p(z_limbs), _p(C), _p(L), _p(R), _p(E), _p(Q), ctypes.c_int(threads if threads > 0 else usable_threads()))
+    if rc:
+        raise ValueError("ogkr_sumcheck_zerocheck rc=%d" % rc)
+    return C, L, R, E, Q
+
+
 def sumcheck_mle(table, n, threads=0):
     C, L, R = sumcheck_mle_raw(to_limbs(table), n, threads)
     proof = [from_limbs(C[j])[2 - int(L[j]):] for j in range(n)]

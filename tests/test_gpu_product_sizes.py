@@ -13,8 +13,6 @@ the per-factor flags when only a far block sets them.
 
 Tables are built with numpy on limb arrays; the oracle is called once per sumcheck and its results are kept."""
 
-import ctypes
-
 import numpy as np
 import pytest
 
@@ -24,6 +22,7 @@ from oracle import cdense
 from oracle.field import P
 from product_model import SPECIALS
 from product_shapes import PRODUCT_GEOMETRY, product_geometry
+from resident_tables import Resident, assert_same as _assert_same
 
 pytestmark = pytest.mark.gpu
 
@@ -38,37 +37,6 @@ def ctx():
     c = Context(0)
     yield c
     c.close()
-
-
-def _free_bytes():
-    import torch
-    return torch.cuda.mem_get_info()[0]
-
-
-class Resident:
-    """A limb array in device memory for the length of a `with` (skips when the device has no room for it and the workspace)."""
-
-    def __init__(self, ctx, T):
-        self.ctx, self.T = ctx, np.ascontiguousarray(T)
-
-    def __enter__(self):
-        if _free_bytes() < int(1.75 * self.T.nbytes):
-            pytest.skip("not enough free device memory for %d MiB of tables" % (self.T.nbytes >> 20))
-        self.d = self.ctx.alloc(self.T.nbytes)
-        try:
-            self.ctx.upload(self.d, self.T)
-        except Exception:
-            self.ctx.free(self.d)
-            raise
-        return self
-
-    def __exit__(self, *a):
-        self.ctx.free(self.d)
-
-    def set_entry(self, flat_index, limbs):
-        """One entry, in the host copy and on the device."""
-        self.T.reshape(-1, 4)[flat_index] = limbs
-        self.ctx.upload(ctypes.c_void_p(self.d.value + 32 * flat_index), np.ascontiguousarray(limbs, dtype=np.uint64).reshape(1, 4))
 
 
 def _value(limbs):
@@ -115,16 +83,6 @@ def _oracle(key, T):
         outs = [cdense.sumcheck_product_raw(T[b], n, degree) for b in range(batch)]
         _oracle_cache[key] = tuple(np.stack([o[k] for o in outs]) for k in range(4))
     return _oracle_cache[key]
-
-
-def _assert_same(got, want, what):
-    """(C, L, R, E) of the device against the oracle's; the first differing (sumcheck, round, slot) on a mismatch."""
-    for name, g, w in zip(("lengths", "coefficients", "challenges", "evals"), (got[1], got[0], got[2], got[3]), (want[1], want[0], want[2], want[3])):
-        assert g.shape == w.shape and g.dtype == w.dtype, (what, name, g.shape, w.shape)
-        if not np.array_equal(g, w):
-            differ = (g != w) if name == "lengths" else (g != w).any(axis=-1)
-            at = tuple(int(x) for x in np.argwhere(differ)[0])               # (sumcheck, round[, slot]) or (sumcheck, factor)
-            pytest.fail("%s: %s differ first at %s: got %s, want %s (%d places in all)" % (what, name, at, g[at], w[at], int(differ.sum())))
 
 
 # ---- a. the shape matrix ----------------------------------------------------------------------------------------------------------------

@@ -27,6 +27,7 @@ from product_model import factor, product_sumcheck
 from product_shapes import PRODUCT_GEOMETRY, product_geometry
 from sop_model import (STRUCTURES, constant_tables_transcript, limbs_to_object, sop_claim_np, sop_degree, sop_eval, sop_sumcheck,
                        sop_sumcheck_np)
+from sop_terms import BOOKKEEPING
 
 pytestmark = pytest.mark.gpu
 
@@ -172,16 +173,6 @@ def test_a_zero_table_in_the_middle_sumcheck_in_both_transcript_modes():
 
 
 # ---- d. bookkeeping ---------------------------------------------------------------------------------------------------------------------
-BOOKKEEPING = {
-    "mixed degrees under D = 3": (3, [(1, (0, 1, 2)), (3, (1, 2)), (P - 5, (0,))]),
-    "square, cube, a table in three terms": (2, [(1, (0, 0)), (2, (0, 0, 0)), (3, (0, 1)), (4, (1,))]),
-    "cube alone": (1, [(7, (0, 0, 0))]),
-    "eight terms over eight tables": (8, [((0, 1, P - 1, 0x1234567890ABCDEF << 180, 2, P - 2, 1, 5)[k], (k, (k + 1) % 8, (k + 3) % 8)[:1 + k % 3])
-                                          for k in range(8)]),
-    "zero and one and r - 1": (3, [(0, (0, 1)), (1, (1, 2)), (P - 1, (0,))]),
-}
-
-
 @pytest.mark.parametrize("n", [4, 10])
 @pytest.mark.parametrize("name", list(BOOKKEEPING))
 def test_bookkeeping(ctx, name, n):
