@@ -16,7 +16,11 @@ Contents
   dense.py     dense-table algorithm (pure Python ints), shown equal to
                termlist.py by tests/test_oracle_equivalence.py
   c/           plain-C dense oracle (gcc), used for 2^16..2^20 sizes and as the
-               timed CPU baseline ("port")
+               timed CPU baseline ("port"); its R1CS tables (ogkr_r1cs_rows,
+               ogkr_r1cs_cols, ogkr_r1cs_matrix_evals: loops over the flat records)
+               are pinned by tests/test_oracle_r1cs_c.py to the Python models of
+               tests/r1cs_rows_model.py, tests/r1cs_cols_model.py and
+               verifier.r1cs_matrix_evals
 
 Pinning status (see DESIGN.md "Oracle"):
   * termlist.py / dense.py are pinned against golden vectors produced by

@@ -603,6 +603,178 @@ int ogkr_sumcheck_zerocheck(const ogkr_fr *tables, int n, int n_tables, const og
     return 0;
 }
 
+/* ------------------------------------------------------------------ R1CS tables
+ * The tables of the R1CS zero-check and inner sumcheck (tests/r1cs_rows_model.py, tests/r1cs_cols_model.py and
+ * verifier.r1cs_matrix_evals restate the rules) on the flat records as they stand: counts[3 i + m] records for the combination
+ * of constraint i in matrix m (A, B, C), one after the other in wires[] / coeffs[].  No row pointers, no column-major form, no
+ * coefficient pool, no case for 1 or r - 1; a zero coefficient adds zero and a repeated wire adds twice by itself.  The modular
+ * sums are exact, so no result depends on how the constraints are dealt over the threads. */
+
+void ogkr_fr_mul_many(const ogkr_fr *a, const ogkr_fr *b, ogkr_fr *out, size_t count) {
+#pragma omp parallel for schedule(static)
+    for (size_t i = 0; i < count; ++i) fr_mul(a[i].l, b[i].l, out[i].l);
+}
+
+void ogkr_fr_add_many(const ogkr_fr *a, const ogkr_fr *b, ogkr_fr *out, size_t count) {
+#pragma omp parallel for schedule(static)
+    for (size_t i = 0; i < count; ++i) fr_add(a[i].l, b[i].l, out[i].l);
+}
+
+/* every wire below n_wires, every coefficient canonical: the number of records, or (size_t)-1 */
+static size_t r1cs_check(size_t n_constraints, uint32_t n_wires, const uint32_t *counts, const uint32_t *wires, const ogkr_fr *coeffs) {
+    size_t total = 0;
+    for (size_t i = 0; i < 3 * n_constraints; ++i) total += counts[i];
+    int bad = 0;
+#pragma omp parallel for schedule(static) reduction(| : bad)
+    for (size_t t = 0; t < total; ++t) bad |= wires[t] >= n_wires || geq_mod(coeffs[t].l);
+    return bad ? (size_t)-1 : total;
+}
+
+static int all_canonical(const ogkr_fr *v, size_t count) {
+    for (size_t i = 0; i < count; ++i)
+        if (geq_mod(v[i].l)) return 0;
+    return 1;
+}
+
+/* thread `id` of `nt` takes the constraints [*first, *last); *pos is the index of its first record */
+static void r1cs_share(size_t n_constraints, const uint32_t *counts, int id, int nt, size_t *first, size_t *last, size_t *pos) {
+    *first = n_constraints * (size_t)id / (size_t)nt;
+    *last = n_constraints * ((size_t)id + 1) / (size_t)nt;
+    size_t p = 0;
+    for (size_t i = 0; i < 3 * *first; ++i) p += counts[i];
+    *pos = p;
+}
+
+int ogkr_r1cs_rows(size_t n_constraints, uint32_t n_wires, const uint32_t *counts, const uint32_t *wires, const ogkr_fr *coeffs,
+                   const ogkr_fr *witness, int n, ogkr_fr *out, int threads) {
+    if (n < 0 || n > 40 || n_constraints > (size_t)1 << n) return -1;
+    if (r1cs_check(n_constraints, n_wires, counts, wires, coeffs) == (size_t)-1 || !all_canonical(witness, n_wires)) return -1;
+    const int nt = set_threads(threads);
+    const size_t len = (size_t)1 << n;
+    u64(*wm)[4] = malloc(((size_t)n_wires + 1) * 32);
+    if (!wm) return -2;
+    for (size_t y = 0; y < n_wires; ++y) to_mont(witness[y].l, wm[y]);
+    memset(out, 0, 3 * len * 32);
+#pragma omp parallel num_threads(nt)
+    {
+#ifdef _OPENMP
+        const int id = omp_get_thread_num(), team = omp_get_num_threads();
+#else
+        const int id = 0, team = 1;
+#endif
+        size_t first, last, pos;
+        r1cs_share(n_constraints, counts, id, team, &first, &last, &pos);
+        for (size_t i = first; i < last; ++i)
+            for (int m = 0; m < 3; ++m) {
+                u64 *dst = out[(size_t)m * len + i].l, p[4];
+                for (uint32_t t = 0; t < counts[3 * i + m]; ++t, ++pos) {
+                    mont_mul(coeffs[pos].l, wm[wires[pos]], p);   /* c (w R) / R = c w */
+                    fr_add(dst, p, dst);
+                }
+            }
+    }
+    free(wm);
+    return 0;
+}
+
+int ogkr_r1cs_cols(size_t n_constraints, uint32_t n_wires, const uint32_t *counts, const uint32_t *wires, const ogkr_fr *coeffs,
+                   const ogkr_fr *x, int n_x, const ogkr_fr *rho, int n_y, ogkr_fr *out, int threads) {
+    if (n_x < 0 || n_x > 40 || n_y < 0 || n_y > 40 || n_constraints > (size_t)1 << n_x || n_wires > (size_t)1 << n_y) return -1;
+    if (r1cs_check(n_constraints, n_wires, counts, wires, coeffs) == (size_t)-1 || !all_canonical(x, (size_t)n_x) || !all_canonical(rho, 3))
+        return -1;
+    const int nt = set_threads(threads);
+    const size_t len = (size_t)1 << n_y;
+    u64(*e)[4] = malloc(((size_t)1 << n_x) * 32);
+    if (!e) return -2;
+    eq_table(n_x, x, e);
+    u64 rm[3][4];
+    for (int m = 0; m < 3; ++m) to_mont(rho[m].l, rm[m]);
+    memset(out, 0, len * 32);
+    int no_memory = 0;
+#pragma omp parallel num_threads(nt)
+    {
+#ifdef _OPENMP
+        const int id = omp_get_thread_num(), team = omp_get_num_threads();
+#else
+        const int id = 0, team = 1;
+#endif
+        /* a table per thread (the cells collide), added into out one thread at a time */
+        u64(*mine)[4] = calloc(len, 32);
+        if (!mine) {
+#pragma omp atomic write
+            no_memory = 1;
+        } else {
+            size_t first, last, pos;
+            r1cs_share(n_constraints, counts, id, team, &first, &last, &pos);
+            for (size_t i = first; i < last; ++i)
+                for (int m = 0; m < 3; ++m) {
+                    u64 f[4], fm[4], p[4];
+                    mont_mul(e[i], rm[m], f);                     /* rho_m eq(x, i) */
+                    to_mont(f, fm);
+                    for (uint32_t t = 0; t < counts[3 * i + m]; ++t, ++pos) {
+                        mont_mul(coeffs[pos].l, fm, p);
+                        fr_add(mine[wires[pos]], p, mine[wires[pos]]);
+                    }
+                }
+#pragma omp critical(ogkr_r1cs_cols)
+            for (size_t y = 0; y < n_wires; ++y) fr_add(out[y].l, mine[y], out[y].l);
+            free(mine);
+        }
+    }
+    free(e);
+    return no_memory ? -2 : 0;
+}
+
+int ogkr_r1cs_matrix_evals(size_t n_constraints, uint32_t n_wires, const uint32_t *counts, const uint32_t *wires, const ogkr_fr *coeffs,
+                           const ogkr_fr *x, int n_x, const ogkr_fr *y, int n_y, ogkr_fr *out, int threads) {
+    if (n_x < 0 || n_x > 40 || n_y < 0 || n_y > 40 || n_constraints > (size_t)1 << n_x || n_wires > (size_t)1 << n_y) return -1;
+    if (r1cs_check(n_constraints, n_wires, counts, wires, coeffs) == (size_t)-1 || !all_canonical(x, (size_t)n_x) ||
+        !all_canonical(y, (size_t)n_y))
+        return -1;
+    const int nt = set_threads(threads);
+    const size_t len_x = (size_t)1 << n_x, len_y = (size_t)1 << n_y;
+    u64(*ex)[4] = malloc(len_x * 32), (*ey)[4] = malloc(len_y * 32);
+    if (!ex || !ey) {
+        free(ex);
+        free(ey);
+        return -2;
+    }
+    eq_table(n_x, x, ex);
+    eq_table(n_y, y, ey);
+#pragma omp parallel for schedule(static) num_threads(nt)
+    for (size_t i = 0; i < len_x; ++i) to_mont(ex[i], ex[i]);
+#pragma omp parallel for schedule(static) num_threads(nt)
+    for (size_t w = 0; w < len_y; ++w) to_mont(ey[w], ey[w]);
+    u64 acc[3][4];
+    memset(acc, 0, sizeof acc);
+#pragma omp parallel num_threads(nt)
+    {
+#ifdef _OPENMP
+        const int id = omp_get_thread_num(), team = omp_get_num_threads();
+#else
+        const int id = 0, team = 1;
+#endif
+        u64 local[3][4];
+        memset(local, 0, sizeof local);
+        size_t first, last, pos;
+        r1cs_share(n_constraints, counts, id, team, &first, &last, &pos);
+        for (size_t i = first; i < last; ++i)
+            for (int m = 0; m < 3; ++m)
+                for (uint32_t t = 0; t < counts[3 * i + m]; ++t, ++pos) {
+                    u64 p[4], q[4];
+                    mont_mul(ex[i], ey[wires[pos]], p);           /* (ex R)(ey R) / R = ex ey R */
+                    mont_mul(coeffs[pos].l, p, q);                /* c ex ey */
+                    fr_add(local[m], q, local[m]);
+                }
+#pragma omp critical(ogkr_r1cs_mat)
+        for (int m = 0; m < 3; ++m) fr_add(acc[m], local[m], acc[m]);
+    }
+    for (int m = 0; m < 3; ++m) memcpy(out[m].l, acc[m], 32);
+    free(ex);
+    free(ey);
+    return 0;
+}
+
 int ogkr_predicate_tables(int k_i, int k_next, const uint8_t *gate_type, const uint32_t *left,
                           const uint32_t *right, const ogkr_fr *z, ogkr_fr *A, ogkr_fr *M) {
     if (k_i < 0 || k_i > 30 || k_next < 1 || k_next > 15) return -1;

@@ -83,6 +83,29 @@ int ogkr_sumcheck_zerocheck(const ogkr_fr *tables, int n, int n_tables, const og
                             int n_terms, const ogkr_fr *z, ogkr_fr *out_coeffs, uint32_t *out_len, ogkr_fr *out_r,
                             ogkr_fr *out_evals, ogkr_fr *out_eq, int threads);
 
+/* The tables of the R1CS zero-check and inner sumcheck on the flat form of an R1CS: counts[3 * n_constraints] (the records of A,
+ * B, C per constraint), wires[] and canonical coeffs[], one record after the other -- the C twins of tests/r1cs_rows_model.rows,
+ * tests/r1cs_cols_model.cols_table and verifier.r1cs_matrix_evals, as loops over the records as they stand.  A zero coefficient
+ * contributes nothing, a repeated wire adds; variable 1 of a point is the most significant index bit.
+ *   rows:          out[m * 2^n + i] = sum coeff * witness[wire] over the combination of constraint i in matrix m, zero for
+ *                  i >= n_constraints; witness: n_wires canonical elements; out: 3 * 2^n.
+ *   cols:          out[y] = sum_m rho[m] sum_i M_m[i][y] eq(x, i), eq(x, .) written out as a table of 2^n_x entries and the
+ *                  records scattered one by one; zero for y >= n_wires; out: 2^n_y.
+ *   matrix_evals:  out[m] = sum over the records (c, wire w) of constraint i in matrix m of c eq(x, i) eq(y, w), both eq tables
+ *                  written out; out: 3.
+ * -1: a wire >= n_wires, n_constraints > 2^n (2^n_x), n_wires > 2^n_y, or an element that is not canonical; -2: no memory. */
+int ogkr_r1cs_rows(size_t n_constraints, uint32_t n_wires, const uint32_t *counts, const uint32_t *wires, const ogkr_fr *coeffs,
+                   const ogkr_fr *witness, int n, ogkr_fr *out, int threads);
+int ogkr_r1cs_cols(size_t n_constraints, uint32_t n_wires, const uint32_t *counts, const uint32_t *wires, const ogkr_fr *coeffs,
+                   const ogkr_fr *x, int n_x, const ogkr_fr *rho, int n_y, ogkr_fr *out, int threads);
+int ogkr_r1cs_matrix_evals(size_t n_constraints, uint32_t n_wires, const uint32_t *counts, const uint32_t *wires, const ogkr_fr *coeffs,
+                           const ogkr_fr *x, int n_x, const ogkr_fr *y, int n_y, ogkr_fr *out, int threads);
+
+/* out[i] = a[i] * b[i], a[i] + b[i] for i < count (out may be a or b): for witnesses and first_bad at sizes where a Python
+ * integer per entry costs too much */
+void ogkr_fr_mul_many(const ogkr_fr *a, const ogkr_fr *b, ogkr_fr *out, size_t count);
+void ogkr_fr_add_many(const ogkr_fr *a, const ogkr_fr *b, ogkr_fr *out, size_t count);
+
 /* prove_sumcheck_opt for one layer: gates g = 0..2^k_i-1 of type gate_type[g]
  * (0 add, 1 mult) with operands left[g], right[g] in [0, 2^k_next); z has k_i
  * entries; W has 2^k_next evaluations.  out_coeffs: 2*k_next rows of 3 slots,

@@ -209,6 +209,94 @@ def sumcheck_zerocheck_raw(tables_limbs, n, n_tables, terms, z_limbs, threads=0)
     return C, L, R, E, Q
 
 
+def _r1cs_flat(counts, wires, coeffs):
+    """The flat form of an R1CS (what gkr_r1cs_export writes): counts (3 * n_constraints,) uint32, wires (records,) uint32, coeffs
+    (records, 4) uint64, checked against each other -> (n_constraints, counts, wires, coeffs)."""
+    counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+    wires = np.ascontiguousarray(wires, dtype=np.uint32).reshape(-1)
+    coeffs = np.ascontiguousarray(coeffs, dtype=np.uint64).reshape(-1, 4)
+    if counts.size % 3 or int(counts.sum(dtype=np.uint64)) != wires.size or coeffs.shape[0] != wires.size:
+        raise ValueError("counts of A, B, C per constraint and one wire and one coefficient per record expected")
+    return counts.size // 3, counts, wires, coeffs
+
+
+def _threads(threads):
+    return ctypes.c_int(threads if threads > 0 else usable_threads())
+
+
+def r1cs_rows_raw(counts, wires, coeffs, n_wires, witness_limbs, n, threads=0):
+    """ogkr_r1cs_rows -> (3, 2^n, 4) uint64: Az, Bz, Cz of the witness ((n_wires, 4) limbs), rows past the constraints zero."""
+    n_constraints, counts, wires, coeffs = _r1cs_flat(counts, wires, coeffs)
+    witness_limbs = np.ascontiguousarray(witness_limbs, dtype=np.uint64)
+    if witness_limbs.shape != (n_wires, 4) or not 0 <= n <= 40:
+        raise ValueError("a witness of n_wires entries and 0 <= n <= 40 expected")
+    out = np.zeros((3, 1 << n, 4), dtype=np.uint64)
+    fn = lib().ogkr_r1cs_rows
+    fn.restype = ctypes.c_int
+    rc = fn(ctypes.c_size_t(n_constraints), ctypes.c_uint32(n_wires), _p(counts), _p(wires), _p(coeffs), _p(witness_limbs), ctypes.c_int(n),
+            _p(out), _threads(threads))
+    if rc:
+        raise ValueError("ogkr_r1cs_rows rc=%d" % rc)
+    return out
+
+
+def r1cs_cols_raw(counts, wires, coeffs, n_wires, x_limbs, rho_limbs, n_y, threads=0):
+    """ogkr_r1cs_cols -> (2^n_y, 4) uint64: T[y] = sum_m rho_m sum_i M_m[i][y] eq(x, i); x (n_x, 4) limbs, rho (3, 4) limbs."""
+    n_constraints, counts, wires, coeffs = _r1cs_flat(counts, wires, coeffs)
+    x_limbs = np.ascontiguousarray(x_limbs, dtype=np.uint64).reshape(-1, 4)
+    rho_limbs = np.ascontiguousarray(rho_limbs, dtype=np.uint64)
+    n_x = x_limbs.shape[0]
+    if rho_limbs.shape != (3, 4) or not 0 <= n_y <= 40 or n_x > 40:
+        raise ValueError("three weights, at most 40 coordinates and 0 <= n_y <= 40 expected")
+    out = np.zeros((1 << n_y, 4), dtype=np.uint64)
+    fn = lib().ogkr_r1cs_cols
+    fn.restype = ctypes.c_int
+    rc = fn(ctypes.c_size_t(n_constraints), ctypes.c_uint32(n_wires), _p(counts), _p(wires), _p(coeffs), _p(x_limbs), ctypes.c_int(n_x),
+            _p(rho_limbs), ctypes.c_int(n_y), _p(out), _threads(threads))
+    if rc:
+        raise ValueError("ogkr_r1cs_cols rc=%d" % rc)
+    return out
+
+
+def r1cs_matrix_evals_raw(counts, wires, coeffs, n_wires, x_limbs, y_limbs, threads=0):
+    """ogkr_r1cs_matrix_evals -> (3, 4) uint64: [A~, B~, C~](x, y); x (n_x, 4) and y (n_y, 4) limbs."""
+    n_constraints, counts, wires, coeffs = _r1cs_flat(counts, wires, coeffs)
+    x_limbs = np.ascontiguousarray(x_limbs, dtype=np.uint64).reshape(-1, 4)
+    y_limbs = np.ascontiguousarray(y_limbs, dtype=np.uint64).reshape(-1, 4)
+    if x_limbs.shape[0] > 40 or y_limbs.shape[0] > 40:
+        raise ValueError("at most 40 coordinates expected")
+    out = np.zeros((3, 4), dtype=np.uint64)
+    fn = lib().ogkr_r1cs_matrix_evals
+    fn.restype = ctypes.c_int
+    rc = fn(ctypes.c_size_t(n_constraints), ctypes.c_uint32(n_wires), _p(counts), _p(wires), _p(coeffs), _p(x_limbs),
+            ctypes.c_int(x_limbs.shape[0]), _p(y_limbs), ctypes.c_int(y_limbs.shape[0]), _p(out), _threads(threads))
+    if rc:
+        raise ValueError("ogkr_r1cs_matrix_evals rc=%d" % rc)
+    return out
+
+
+def _many(name, a_limbs, b_limbs):
+    a_limbs = np.ascontiguousarray(a_limbs, dtype=np.uint64)
+    b_limbs = np.ascontiguousarray(b_limbs, dtype=np.uint64)
+    if a_limbs.shape != b_limbs.shape or a_limbs.shape[-1:] != (4,):
+        raise ValueError("two limb arrays of one shape expected")
+    out = np.zeros_like(a_limbs)
+    fn = getattr(lib(), name)
+    fn.restype = None
+    fn(_p(a_limbs), _p(b_limbs), _p(out), ctypes.c_size_t(a_limbs.size // 4))
+    return out
+
+
+def fr_mul_many(a_limbs, b_limbs):
+    """ogkr_fr_mul_many: the entrywise product of two limb arrays of one shape (canonical in, canonical out)."""
+    return _many("ogkr_fr_mul_many", a_limbs, b_limbs)
+
+
+def fr_add_many(a_limbs, b_limbs):
+    """ogkr_fr_add_many: the entrywise sum."""
+    return _many("ogkr_fr_add_many", a_limbs, b_limbs)
+
+
 def sumcheck_mle(table, n, threads=0):
     C, L, R = sumcheck_mle_raw(to_limbs(table), n, threads)
     proof = [from_limbs(C[j])[2 - int(L[j]):] for j in range(n)]
