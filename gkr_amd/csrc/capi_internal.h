@@ -278,6 +278,7 @@ struct gkr_ctx {
     hipStream_t late = nullptr;                // separate stream for a group's small late passes (lazy), see late_stream()
     hipStream_t chain = nullptr;               // the device-hashed sumchecks' chain of kernels (lazy), see chain_stream()
     std::vector<hipEvent_t> aux_events;        // one per group of a batch: "the side kernel of this group is done"
+    std::vector<hipEvent_t> ended_events;      // one per group: "the group's publishing streaming kernel has ended", see stream_end_events()
     Fr* d_cts = nullptr;
     int transcript = GKR_TRANSCRIPT_HOST;
     std::string err;
@@ -385,6 +386,19 @@ struct gkr_ctx {
             hipError_t rc = hipEventCreateWithFlags(&e, hipEventDisableTiming);
             if (rc != hipSuccess) return rc;
             aux_events.push_back(e);
+        }
+        return hipSuccess;
+    }
+
+    // Events that a kernel on the main stream fires for the context's OTHER streams on the same device and for nobody else: no system-scope
+    // fence.  An event with the default fence makes the kernel it follows write back and invalidate the caches for the host as well,
+    // which costs the launch behind it ~5 us (profiles/r26).
+    hipError_t stream_end_events(int events) {
+        while ((int)ended_events.size() < events) {
+            hipEvent_t e;
+            hipError_t rc = hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventDisableSystemFence);
+            if (rc != hipSuccess) return rc;
+            ended_events.push_back(e);
         }
         return hipSuccess;
     }

@@ -68,6 +68,10 @@ struct MlePassTables {
     gkr::MleHostRecSub* rec = nullptr;     // the records the passes publish to: h_rec, or device records on their way through an exchange
     uint32_t* arrivals = nullptr;          // zeroed counters of passes that publish from their last block; null: no pass does
     Fr* h_tail = nullptr;                  // pinned: the host tail's tables, 2^kMleTailLog2 entries apart; null: no host tail
+    // pinned: flag-in-word records (flagged_rec.h), kFlagRecsPerTable per sumcheck, which the blocks of a publishing streaming pass
+    // write and the hashing threads total into h_rec; null: every streaming pass publishes through k_mle_sub_reduce
+    uint64_t* h_flag = nullptr;
+    uint64_t* flag_rec(int b) const { return h_flag + (size_t)b * gkr::kFlagRecsPerTable * gkr::kFlagRecWords; }
 };
 // (slots `prefix`.work / .partials / .plans / .rec / .w: the context caches the allocations by these names)
 static int mle_pass_tables(gkr_ctx* ctx, const std::string& prefix, const Fr* input, size_t len, size_t work_len, int batch, MlePassTables& T) {
@@ -117,6 +121,7 @@ struct MlePassPolicy {
     Fr* export_tail = nullptr;   // a one-block fold leaves its tables here as well (the host tail's slice of h_tail)
     int blocks_jout = 0;         // pass 0, > 0: blocks per table as for 2^blocks_jout sub-blocks (the two-level first fold's fine sums)
     uint32_t src_planes = 1;     // a one-block fold: its source is the sum of this many planes, 2^m_src entries apart
+    bool flagged = false;        // pass 0: its blocks may publish flag-in-word records (T.h_flag) instead of a reduce launch
 };
 // pass 0's blocks per table; ahead of a two-level first fold a multiple of 1024 (every fine sum a run of partials) of whole 256-entry chunks
 static uint32_t pass0_blocks(size_t len, int jout, int nb, const MlePassPolicy& P) {
@@ -128,24 +133,28 @@ static void queue_sub_reduce(gkr_ctx* ctx, const MlePassTables& T, int b0, int n
     Timed t(ctx, "mle_sub_reduce", 0.0, st, true);
     gkr::launch_mle_sub_reduce(T.partials + (size_t)b0 * gkr::kMaxBlocksPerTable, nblk, (uint32_t)jout, nb, T.rec + b0, ticket, st);
 }
-// pass 0 of the sumchecks [b0, b0 + nb): the 2^jout sub-block sums of the input tables
-static void queue_pass0(gkr_ctx* ctx, const MlePassTables& T, int b0, int nb, int jout, uint32_t ticket, hipStream_t st, const MlePassPolicy& P) {
+// pass 0 of the sumchecks [b0, b0 + nb): the 2^jout sub-block sums of the input tables.  true: its blocks publish flag-in-word
+// records (P.flagged and a launch that takes the publishing kernel), which the host totals -- no reduce launch was queued
+static bool queue_pass0(gkr_ctx* ctx, const MlePassTables& T, int b0, int nb, int jout, uint32_t ticket, hipStream_t st, const MlePassPolicy& P) {
     const size_t len = T.in_stride;
     const Fr* src = T.input + (size_t)b0 * len;
     const double bytes = (double)nb * len * 32.0;
     if (len <= gkr::kSmallPassEntries) {
         Timed t(ctx, "mle_pass_small", bytes, st, true);
         gkr::launch_mle_multifold_small(0, src, len, nullptr, 0, (uint32_t)len, (uint32_t)jout, nb, T.h_w + (size_t)b0 * gkr::kMleMaxSub, T.rec + b0, ticket, st);
-        return;
+        return false;
     }
     const uint32_t nblk = pass0_blocks(len, jout, nb, P);
     gkr::MlePublish pub;
     const bool fused = fused_publish(T, b0, nb, nblk, bytes, ticket, jout, pub);
+    bool flagged;
     {
         Timed t(ctx, P.row, bytes, st, fused);
-        gkr::launch_mle_sub_sums(src, len, (uint32_t)len, nb, nblk, T.partials + (size_t)b0 * gkr::kMaxBlocksPerTable, st, fused ? &pub : nullptr);
+        flagged = gkr::launch_mle_sub_sums(src, len, (uint32_t)len, nb, nblk, T.partials + (size_t)b0 * gkr::kMaxBlocksPerTable, st, fused ? &pub : nullptr,
+                                           P.flagged && !fused ? T.flag_rec(b0) : nullptr, ticket);
     }
-    if (!fused) queue_sub_reduce(ctx, T, b0, nb, nblk, jout, ticket, st);
+    if (!fused && !flagged) queue_sub_reduce(ctx, T, b0, nb, nblk, jout, ticket, st);
+    return flagged;
 }
 // a fold pass: bind the jin variables just hashed of tables of 2^m_src entries (the input, or work), produce the sums of the next jout rounds
 static void queue_fold(gkr_ctx* ctx, const MlePassTables& T, int b0, int nb, bool from_input, int m_src, int jin, int jout, uint32_t ticket,
@@ -283,6 +292,18 @@ struct PassGroup : GroupHandoff {   // (generation of the hand-off = pass number
     // the two-level first fold: rounds 1-5 hashed -> launch_fine_sums -> (mid) its record landed, rounds 6-10 hashed ->
     // launch_fold2, which leaves the table in planes for the one pass after it
     bool mid = false, planes = false;
+    // the pass in flight published flag-in-word records under this ticket, and its tables are still being totalled by the hashing
+    // threads (try_total); 0: nothing to total.  Set by the driving thread with the launch, cleared by whoever totals the last table.
+    std::atomic<uint32_t> flag_ticket{0};
+    std::atomic<int> flag_left{0};   // tables of that pass not totalled yet
+    int pub_index = -1;              // ... as launch pubs[pub_index] of the main stream, until what depends on its end is queued (after_stream_pass)
+    bool end_bound = false;          // that launch fires the group's end event with its completion
+};
+// a table's records while a hashing thread looks at them: one thread at a time (busy), from where the last look stopped
+struct FlagScan {
+    std::atomic<uint32_t> busy{0};
+    std::atomic<uint32_t> done{0};   // the ticket whose records were totalled last
+    std::atomic<uint32_t> cursor{0}, cursor_ticket{0};   // written by the owner, under busy; read by anyone as a hint of where to peek
 };
 // GKR_DEBUG_TIMING: the phases of a call on the host clock
 struct MlePassClock {
@@ -313,6 +334,15 @@ struct MlePassRun {
     std::vector<PassGroup> grp;
     std::vector<uint32_t> dep_last;
     int next_first = 0;   // groups [next_first, groups): pass 0 still to launch
+    int folds_queued = 0;   // two-level first folds launched so far
+    struct PubLaunch {
+        int b0;
+        uint32_t ticket;
+    };
+    std::vector<PubLaunch> pubs;   // the main stream's publishing launches, in order ...
+    int pubs_started = -1;         // ... the last of them that is known to have started
+    hipError_t order_err = hipSuccess;   // the first failure of an event record / wait that orders a dependent launch (after_stream_pass)
+    std::unique_ptr<FlagScan[]> scan;   // per sumcheck; null: no pass of this call publishes flag-in-word records
     gkr_fr *stage_c = nullptr, *stage_r = nullptr;   // pinned: the device-hashed sumchecks' outputs, in the caller's layout
     uint32_t* stage_len = nullptr;
     MlePassClock clock;
@@ -322,15 +352,54 @@ struct MlePassRun {
         G.m -= jin;
         G.round0 += jin;
         G.j = rounds_for(G.m);
-        G.ticket = ++ctx->ticket;
+        G.ticket = gkr::next_ticket(ctx->ticket);
+    }
+    // the group's pass in flight published flag-in-word records: its tables are the hashing threads' to total from here on
+    void arm_totals(PassGroup& G, bool end_bound) {
+        G.pub_index = (int)pubs.size();
+        G.end_bound = end_bound;
+        pubs.push_back({G.b0, G.ticket});
+        G.flag_left.store(G.nb, std::memory_order_relaxed);
+        G.flag_ticket.store(G.ticket, std::memory_order_release);
+    }
+    // The records say that every block of a publishing kernel has stored its sums, not that the kernel has ENDED: what it left in device
+    // memory (pass 0's partials, the fold's planes) is another stream's to read only behind its end.  The host settles that too, without
+    // a packet on the main stream: the stream runs its kernels in order, so the kernel has ended -- and its writes are out of the caches
+    // -- once a LATER publishing launch of the main stream has started, which the first word of that launch's first record shows
+    // (a block of the first wave of blocks writes it, ~30 us into the kernel; the dependent launch comes J hashes, 100 us and more,
+    // behind the records).  ASSUMED, as the single-copy-atomic store is (flagged_rec.h): the runtime queues every kernel of a stream with
+    // the AQL barrier bit, so no wave of a kernel runs before the kernel ahead of it on the stream has completed, its end-of-kernel
+    // write-back included -- what the parent relied on too, through the reduce launch's record.  Where no later launch shows (none queued: pass_queue_depth 1; the one behind it is the call's last, which
+    // does not publish), the dependent stream waits for an event: the one bound to the kernel's completion (end_bound; it costs the
+    // launch behind it ~5 us, so only the fold ahead of the call's last one gets it), or, if the main stream is not already empty, one
+    // recorded now behind whatever the main stream holds.
+    hipEvent_t ended_event(const PassGroup& G) const { return ctx->ended_events[G.index]; }
+    bool later_launch_started(int index) {
+        for (int q = (int)pubs.size() - 1; q > index && q > pubs_started; --q)
+            if ((uint32_t)(__atomic_load_n(T.flag_rec(pubs[q].b0), __ATOMIC_RELAXED) >> 32) == pubs[q].ticket) pubs_started = q;
+        return pubs_started > index;
+    }
+    void after_stream_pass(PassGroup& G, hipStream_t st) {
+        const int index = G.pub_index;
+        G.pub_index = -1;
+        if (index < 0 || st == s) return;   // (no publishing pass in flight; or the same stream, which orders it)
+        // (a failure here would leave the dependent launch unordered: it ends the call -- loop())
+        hipError_t e = hipSuccess;
+        if (!G.end_bound) {
+            if (later_launch_started(index) || hipStreamQuery(s) == hipSuccess) return;
+            e = hipEventRecord(ended_event(G), s);
+        }
+        if (e == hipSuccess) e = hipStreamWaitEvent(st, ended_event(G), 0);
+        if (e != hipSuccess && order_err == hipSuccess) order_err = e;
     }
     // pass 0: sub-block sums of the input tables
     void launch_first(PassGroup& G) {
-        G.ticket = ++ctx->ticket;
+        G.ticket = gkr::next_ticket(ctx->ticket);
         MlePassPolicy P;
         P.row = G.chain ? "mle_sub_sums_dev" : "mle_sub_sums";
         if (two_level(G)) P.blocks_jout = kMleTwoLevelRounds;
-        queue_pass0(ctx, T, G.b0, G.nb, G.j, G.ticket, G.chain ? G.chain : s, P);
+        P.flagged = scan && two_level(G) && G.j == gkr::kMlePassMaxRounds;
+        if (queue_pass0(ctx, T, G.b0, G.nb, G.j, G.ticket, G.chain ? G.chain : s, P)) arm_totals(G, false);
     }
     void launch_next_first() {
         if (next_first < sc.groups) launch_first(grp[next_first++]);
@@ -341,6 +410,7 @@ struct MlePassRun {
         const bool from_input = m_src == n;
         // small source tables: a latency-bound late pass, not to be queued behind other groups' streaming passes
         hipStream_t st = G.chain ? G.chain : ((!from_input && m_src <= 16) ? late : s);
+        after_stream_pass(G, st);
         advance(G, jin);
         MlePassPolicy P;
         // late passes run beside other groups' streaming passes: their elapsed time is not their own cost, so they
@@ -366,12 +436,13 @@ struct MlePassRun {
         const int J = G.j;
         G.mid = true;
         G.round0 += J;
-        G.ticket = ++ctx->ticket;
+        G.ticket = gkr::next_ticket(ctx->ticket);
         hipStream_t side = side_launches() ? ctx->aux : s;
         MlePassPolicy P0;
         P0.blocks_jout = kMleTwoLevelRounds;
         const uint32_t nblk0 = pass0_blocks(T.in_stride, J, G.nb, P0);
         const Fr* w = T.h_w + (size_t)G.b0 * gkr::kMleMaxSub;
+        after_stream_pass(G, side);
         Timed t(ctx, "mle_fold_plan", 0.0, side, true);
         // (the sums first: the host waits for them, the fold for the matrices only five hashes later)
         gkr::launch_mle_fine_sums(T.partials + (size_t)G.b0 * gkr::kMaxBlocksPerTable, nblk0, w, G.nb, T.rec + G.b0, G.ticket, side);
@@ -396,14 +467,70 @@ struct MlePassRun {
         G.m = n - kMleTwoLevelRounds;
         G.round0 += G.j;
         G.j = gkr::kMlePassMaxRounds;   // (the fold's partials are fine enough at every n it takes, whatever rounds_for says of a streaming fold)
-        G.ticket = ++ctx->ticket;
+        G.ticket = gkr::next_ticket(ctx->ticket);
+        // The LAST streaming launch of the call (every pass 0 is queued and this is the last group's fold) keeps its reduce launch:
+        // nothing is queued behind it on the main stream, and the 11 us kernel is shorter than a host scan on the critical path.
+        ++folds_queued;
+        const bool last_streaming = next_first == sc.groups && folds_queued == sc.groups;
+        const bool before_last = scan && folds_queued == sc.groups - 1;   // (what is launched behind it will not show its start: after_stream_pass)
+        bool flagged;
         {
             Timed t(ctx, "mle_multifold", (double)G.nb * ((double)T.in_stride + (double)(gkr::kMleFold2Planes * (S >> gkr::kMlePassMaxRounds))) * 32.0, s);
-            gkr::launch_mle_multifold2(T.input + (size_t)G.b0 * T.in_stride, T.in_stride, T.work + (size_t)G.b0 * T.work_len, T.work_len, S, G.nb,
-                                       T.plans + (size_t)G.b0 * gkr::mle_fold_plan_bytes(), T.d_w2 + (size_t)G.b0 * gkr::kMleMaxSub,
-                                       T.partials + (size_t)G.b0 * gkr::kMaxBlocksPerTable, s);
+            flagged = gkr::launch_mle_multifold2(T.input + (size_t)G.b0 * T.in_stride, T.in_stride, T.work + (size_t)G.b0 * T.work_len, T.work_len, S, G.nb,
+                                                 T.plans + (size_t)G.b0 * gkr::mle_fold_plan_bytes(), T.d_w2 + (size_t)G.b0 * gkr::kMleMaxSub,
+                                                 T.partials + (size_t)G.b0 * gkr::kMaxBlocksPerTable, s, scan && !last_streaming ? T.flag_rec(G.b0) : nullptr,
+                                                 G.ticket, before_last ? ended_event(G) : nullptr);
         }
-        queue_sub_reduce(ctx, T, G.b0, G.nb, npart, G.j, G.ticket, s);
+        if (flagged)
+            arm_totals(G, before_last);
+        else
+            queue_sub_reduce(ctx, T, G.b0, G.nb, npart, G.j, G.ticket, s);
+    }
+    // A hashing thread (or the driving one, when it has nothing to launch): one look at the tables of the passes that published
+    // flag-in-word records; true: it totalled one -- its record in h_rec is what k_mle_sub_reduce would have written, seq last.
+    // A table whose records have not all landed keeps its cursor and is looked at again, by whoever comes next.
+    bool try_total() {
+        if (!scan) return false;
+        constexpr uint32_t kWords = gkr::kFlagRecsPerTable * gkr::kFlagRecWords;
+        for (int g = 0; g < sc.groups; ++g) {
+            PassGroup& G = grp[g];
+            const uint32_t t = G.flag_ticket.load(std::memory_order_acquire);
+            if (!t) continue;
+            for (int b = G.b0; b < G.b0 + G.nb; ++b) {
+                FlagScan& F = scan[b];
+                if (F.done.load(std::memory_order_relaxed) == t || F.busy.load(std::memory_order_relaxed)) continue;
+                // (a peek before the claim: the word the last look stopped at.  An idle thread's poll then only READS lines that stay
+                // shared until the device writes them; claiming every table on every poll made the threads' hashing 17 % slower)
+                const uint32_t at = F.cursor_ticket.load(std::memory_order_relaxed) == t ? F.cursor.load(std::memory_order_relaxed) : 0u;
+                if (at < kWords && (uint32_t)(__atomic_load_n(T.flag_rec(b) + at, __ATOMIC_RELAXED) >> 32) != t) continue;
+                if (F.busy.exchange(1u, std::memory_order_acquire)) continue;
+                bool totalled = false;
+                if (F.done.load(std::memory_order_relaxed) != t) {
+                    uint32_t cursor = F.cursor_ticket.load(std::memory_order_relaxed) == t ? F.cursor.load(std::memory_order_relaxed) : 0u;
+                    gkr::MleHostRecSub& R = T.h_rec[b];
+                    uint32_t dep = 0;
+                    static_assert(sizeof(R.sums) == gkr::kMleMaxSub * 32, "a sum is four 64-bit words");
+                    const bool landed = gkr::flagged_scan(T.flag_rec(b), kWords, t, &cursor);
+                    F.cursor.store(cursor, std::memory_order_relaxed);
+                    F.cursor_ticket.store(t, std::memory_order_relaxed);
+                    if (landed &&
+                        gkr::flagged_total(T.flag_rec(b), gkr::kFlagRecsPerTable, gkr::kMleMaxSub, t, reinterpret_cast<uint64_t*>(R.sums), &dep)) {
+                        R.dep = dep;
+                        __atomic_store_n(&R.seq, t, __ATOMIC_RELEASE);
+                        F.done.store(t, std::memory_order_relaxed);
+                        totalled = true;
+                    }
+                }
+                F.busy.store(0u, std::memory_order_release);
+                if (!totalled) continue;
+                if (G.flag_left.fetch_sub(1, std::memory_order_acq_rel) == 1) {
+                    uint32_t expect = t;   // (the group's next publishing pass is launched only after these records were read)
+                    G.flag_ticket.compare_exchange_strong(expect, 0u, std::memory_order_acq_rel);
+                }
+                return true;
+            }
+        }
+        return false;
     }
     // the same pass on the host (the group's tables are in h_tail): T'[i] = sum_t w_t T[t S + i], then the sub-block sums of the
     // next rounds into the record the device pass would have written
@@ -458,7 +585,7 @@ struct MlePassRun {
             uint32_t best_gen = 0;
             for (int g = 0; g < sc.groups; ++g)
                 if (const uint32_t gen = grp[g].open_generation(); gen && (best < 0 || gen < best_gen)) best = g, best_gen = gen;
-            if (best < 0) return false;
+            if (best < 0) return try_total();   // (hashes first: they release the next launch)
             PassGroup& G = grp[best];
             uint32_t first, take;
             if (!G.try_claim(sc.chunk[best], &first, &take)) continue;   // the others took the rest meanwhile: look again
@@ -532,7 +659,9 @@ struct MlePassRun {
         while (active > 0 && rc == GKR_OK) {
             bool progress = false;
             for (int g = 0; g < next_first; ++g) progress |= step(grp[g], active);
-            if (progress)
+            if (order_err != hipSuccess)
+                rc = ctx->hip_fail(order_err, "ordering a launch behind a publishing pass");
+            else if (progress)
                 rc = watch.progressed();
             else if (!try_work())
                 rc = watch.idled();
@@ -563,7 +692,14 @@ int run_mle_batch_passes(gkr_ctx* ctx, const Fr* d_tables, int n, int batch, gkr
         HIP_TRY(ctx, ctx->pinned_host("mlep.w2", sizeof(Fr) * gkr::kMleMaxSub * batch, reinterpret_cast<void**>(&R.T.h_w2)));
         WS(ctx, "mlep.d_w2", Fr, (size_t)batch * gkr::kMleMaxSub, R.T.d_w2);
     }
+    // Flag-in-word records (option stream_publish): where another group's launch waits behind a streaming pass's reduce -- several
+    // host-hashed groups on the two-level schedule -- the pass's blocks publish their sums themselves and the hashing threads total them
+    if (gkr::opt(gkr::OPT_stream_publish) != 1 && sc.two_level && sc.groups > 1) {
+        HIP_TRY(ctx, ctx->pinned_host("mlep.flag", sizeof(uint64_t) * gkr::kFlagRecWords * gkr::kFlagRecsPerTable * batch, reinterpret_cast<void**>(&R.T.h_flag)));
+        R.scan.reset(new FlagScan[batch]);
+    }
     HIP_TRY(ctx, ctx->aux_stream(sc.groups));
+    if (R.scan) HIP_TRY(ctx, ctx->stream_end_events(sc.groups));
     if (sc.tail_on) HIP_TRY(ctx, ctx->pinned_host("mlep.tail", sizeof(Fr) * ((size_t)batch << kMleTailLog2), reinterpret_cast<void**>(&R.T.h_tail)));
     if (!gkr::opt(gkr::OPT_no_late_stream) && sc.groups > 1) HIP_TRY(ctx, ctx->late_stream(&R.late));
     R.dep_last = std::vector<uint32_t>(batch, 0);
@@ -678,7 +814,7 @@ struct MleShardRun {
     }
     // one pass (its launches only while this rank is well), its exchange, its rounds
     void pass(bool pass0, bool from_input, int m_src, int jin, int J, int round0) {
-        const uint32_t ticket = ++ctx->ticket;
+        const uint32_t ticket = gkr::next_ticket(ctx->ticket);
         if (!rc) {
             MlePassPolicy P;   // (no pass publishes from its last block: arrivals == nullptr; the plan on the pass's own stream)
             P.row = pass0 ? "mle_sub_sums" : "mle_multifold";
@@ -767,7 +903,7 @@ int gkr_sumcheck_mle_sharded_dev(gkr_ctx* ctx, const void* d_shards, int n, int 
     if (folded) {
         MlePassPolicy P;
         P.row = "mle_multifold";
-        queue_fold(ctx, T, 0, batch, round0 == jin, m + jin, jin, 1, ++ctx->ticket, s, P);   // (one pass so far: its sums came from the input shards)
+        queue_fold(ctx, T, 0, batch, round0 == jin, m + jin, jin, 1, gkr::next_ticket(ctx->ticket), s, P);   // (one pass so far: its sums came from the input shards)
         if (hipError_t le = hipGetLastError(); le != hipSuccess) R.rc = ctx->hip_fail(le, "launch of the last rank-local fold");
     }
     R.gather_tail(folded ? T.work : T.input, folded ? T.work_len : len, m, lp, shard, d_tail);

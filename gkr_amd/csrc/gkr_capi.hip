@@ -98,6 +98,7 @@ void gkr_ctx_destroy(gkr_ctx* ctx) {
     ctx->release_buffers();
     if (ctx->d_cts) (void)hipFree(ctx->d_cts);
     for (hipEvent_t e : ctx->aux_events) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ctx->ended_events) (void)hipEventDestroy(e);
     if (ctx->aux) (void)hipStreamDestroy(ctx->aux);
     if (ctx->late) (void)hipStreamDestroy(ctx->late);
     if (ctx->chain) (void)hipStreamDestroy(ctx->chain);

@@ -1,10 +1,12 @@
 // Launchers of the CDNA4 kernels (kernels.hip).  Internal to the library; the
 // public surface is include/gkr_amd.h.
 #pragma once
+#include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
+#include "flagged_rec.h"
 #include "fr32.h"
 
 namespace gkr {
@@ -129,8 +131,10 @@ constexpr int kMlePass0Stream = 3;   // what option pass0_stream = 0 means: 1 k_
 // (profiles/r22); what smaller launches take is a guess that keeps their block count at the chip's size or above
 constexpr uint64_t kMlePass0DeepMinPartials = 2u * 12u * 256u * 4u;
 // Every pass: per-block partial sums, then a reduce kernel that writes the pinned host record.
-void launch_mle_sub_sums(const Fr* tables, size_t stride, uint32_t len, uint32_t batch, uint32_t nblk, MleSubPartial* partials,
-                         hipStream_t s, const MlePublish* publish = nullptr);
+// flagged != nullptr (pinned: batch x kFlagRecsPerTable flag-in-word records, flagged_rec.h): the rolling form with kFlagRecsPerTable
+// blocks per table publishes its blocks' sums there under flag_ticket and returns true -- the host totals them, no reduce launch
+bool launch_mle_sub_sums(const Fr* tables, size_t stride, uint32_t len, uint32_t batch, uint32_t nblk, MleSubPartial* partials,
+                         hipStream_t s, const MlePublish* publish = nullptr, uint64_t* flagged = nullptr, uint32_t flag_ticket = 0);
 void launch_mle_sub_reduce(const MleSubPartial* partials, uint32_t nblk, uint32_t jout, uint32_t batch, MleHostRecSub* host_rec,
                            uint32_t ticket, hipStream_t s);
 size_t mle_fold_plan_bytes();
@@ -158,8 +162,10 @@ uint32_t mle_multifold2_tiles(uint32_t S);
 void launch_mle_fine_sums(const MleSubPartial* partials, uint32_t nblk, const Fr* weights, uint32_t batch, MleHostRecSub* host_rec, uint32_t ticket,
                           hipStream_t s);
 void launch_mle_copy_weights(const Fr* src, Fr* dst, uint32_t batch, hipStream_t s);
-void launch_mle_multifold2(const Fr* src, size_t src_stride, Fr* dst, size_t dst_stride, uint32_t S, uint32_t batch, const void* plans, const Fr* w2,
-                           MleSubPartial* partials, hipStream_t s);
+// (flagged, flag_ticket, return value: as launch_mle_sub_sums', for launches of kFlagRecsPerTable partials of >= 16 entries per table; ended,
+// may be null: fired by a publishing kernel's completion)
+bool launch_mle_multifold2(const Fr* src, size_t src_stride, Fr* dst, size_t dst_stride, uint32_t S, uint32_t batch, const void* plans, const Fr* w2,
+                           MleSubPartial* partials, hipStream_t s, uint64_t* flagged = nullptr, uint32_t flag_ticket = 0, hipEvent_t ended = nullptr);
 void launch_layer_round_reduce(const LayerPartial* partials, uint32_t nblk, LayerHostRec* host_rec, uint32_t ticket,
                                LayerBatch lb, hipStream_t s);
 void launch_fold_small(Fr* W, uint32_t hw, const FixedMul* rtab, LayerBatch lb, hipStream_t s);

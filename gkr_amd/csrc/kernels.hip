@@ -483,6 +483,26 @@ __device__ __forceinline__ void half_sums_finish(const uint32_t (&acc)[5], uint3
         p->dep = dep;
     }
 }
+// (the same for the publishing kernel, which goes on with the wave's total -- s: lane 0's; dep: wave-uniform.  Its own text:
+// half_sums_finish through this function compiles to other instructions in the kernels that do not publish)
+__device__ __forceinline__ void half_sums_total(const uint32_t (&acc)[5], uint32_t diff, uint32_t lane, Acc<9>& s, uint32_t& dep) {
+    const bool odd = (lane & 1u) != 0u;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        s.l[i] = odd ? 0u : acc[i];
+        s.l[4 + i] = odd ? acc[i] : (i == 0 ? acc[4] : 0u);
+    }
+    s.l[8] = odd ? acc[4] : 0u;
+    s = wave_sum(s);
+    dep = __any(diff != 0u) ? 1u : 0u;
+}
+
+// One word of a flag-in-word record (flagged_rec.h): data and the pass's ticket in ONE relaxed 8-byte store to pinned host memory.
+// No fence, no counter, no order between the stores: the host takes a word only when its high half is the ticket it expects.
+// ASSUMED, not verified: the aligned 8-byte store reaches host memory as one write (what RCCL's LL protocol relies on).
+__device__ __forceinline__ void mle_flag_store(uint64_t* p, uint32_t data, uint32_t ticket) {
+    __hip_atomic_store(p, ((uint64_t)ticket << 32) | data, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
 
 // The rolling form (option pass0_stream = 3): the same contract and the same pieces, ONE buffer of U pieces per lane.  A piece is
 // loaded again, U steps ahead, the moment it has been added, so the wait before every step is vmcnt(U - 1): U - 1 or U loads of
@@ -554,6 +574,83 @@ __global__ void __launch_bounds__(256) k_mle_sub_sums_roll(const Fr* __restrict_
 #pragma unroll
     for (int u = 0; u < U; ++u) half_piece_eat(acc, diff, x[u]);
     half_sums_finish(acc, diff, lane, out);
+}
+
+// The publishing instance of the rolling form, one partial per wave (option stream_publish): the same loop -- its own text, so that
+// k_mle_sub_sums_roll stays instruction for instruction what it was -- and at the block's end the block ALSO publishes the sum of its four
+// waves' partials and the OR of their dep bits as one flag-in-word record (flagged_rec.h) in slot by * (nblk / 4) + bx of `flagged`, the
+// partials' own order whatever XCD does to the blocks: 36 + 4 bytes of LDS per wave and one barrier at the block's end, nothing in the
+// loop.  The host totals the records; no reduce launch follows.  grid = (nblk / 4, batch), block = 256 (FOUR waves: s_pub)
+template <int U, bool XCD>
+__global__ void __launch_bounds__(256) k_mle_sub_sums_roll_pub(const Fr* __restrict__ tables, size_t table_stride, uint32_t chunk, uint32_t nblk,
+                                                               MleSubPartial* __restrict__ partials, uint64_t* __restrict__ flagged, uint32_t ticket) {
+    static_assert(U >= 4 && U % 4 == 0, "the pointer moves once per four pieces");
+    __shared__ uint32_t s_pub[4][kFlagRecWords];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint32_t bx = blockIdx.x, by = blockIdx.y;
+    if constexpr (XCD) {   // (as in k_mle_sub_sums_roll)
+        const uint32_t nwg = gridDim.x * gridDim.y, L = by * gridDim.x + bx, q = nwg >> 3, r = nwg & 7u, run = L & 7u;
+        const uint32_t M = (run < r ? run * (q + 1u) : r * (q + 1u) + (run - r) * q) + (L >> 3);
+        by = M / gridDim.x;
+        bx = M - by * gridDim.x;
+    }
+    const uint32_t p0 = bx * 4u + wave;        // the wave's partial
+    const uint32_t rpp = chunk / (32u * U);    // rounds of U steps per partial
+    MleSubPartial* out = partials + (size_t)by * nblk + p0;
+    const uint32_t voff = lane * 16u;
+    uint64_t next = reinterpret_cast<uint64_t>(tables + (size_t)by * table_stride + (size_t)p0 * chunk);
+
+    mf_v4u x[U];
+    uint32_t acc[5] = {0u, 0u, 0u, 0u, 0u}, diff = 0u;
+    auto load_step = [&](int u) {
+        asm volatile("" : "+s"(next));
+        typedef const __attribute__((address_space(1))) mf_v4u* GlobalPiece;
+        x[u] = __builtin_nontemporal_load(reinterpret_cast<GlobalPiece>(next + voff) + 64 * (u & 3));
+        if ((u & 3) == 3) next += 4096u;
+    };
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        load_step(u);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    for (uint32_t r = rpp - 1u; r != 0u; --r) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            half_piece_eat(acc, diff, x[u]);
+            load_step(u);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) half_piece_eat(acc, diff, x[u]);
+    Acc<9> s;
+    uint32_t dep;
+    half_sums_total(acc, diff, lane, s, dep);
+    if (lane == 0) {
+        out->sum = s;
+        out->dep = dep;
+#pragma unroll
+        for (int l = 0; l < 9; ++l) s_pub[wave][l] = s.l[l];
+        s_pub[wave][9] = dep;
+    }
+    __syncthreads();
+    if (wave == 0 && lane < kFlagRecWords) {
+        // (every one of the ten lanes adds the block's four partials -- LDS broadcasts -- and keeps its own word)
+        Acc<9> tot = acc_zero<9>();
+        uint32_t d = 0;
+        for (uint32_t w = 0; w < 4u; ++w) {
+            Acc<9> o;
+#pragma unroll
+            for (int l = 0; l < 9; ++l) o.l[l] = s_pub[w][l];
+            acc_add_acc(tot, o);
+            d |= s_pub[w][9];
+        }
+        uint32_t word = d;
+#pragma unroll
+        for (int l = 0; l < 9; ++l) word = lane == (uint32_t)l ? tot.l[l] : word;
+        mle_flag_store(flagged + ((size_t)by * (nblk / 4u) + bx) * kFlagRecWords + lane, word, ticket);
+    }
 }
 
 // one pass: bind JIN variables with the weights w[0 .. 2^JIN) (Montgomery, wave-uniform), write the
@@ -681,9 +778,14 @@ __global__ void __launch_bounds__(256) k_mle_copy_weights(const uint32_t* __rest
 // canonical values, stores 64 entries and leaves the tile's partials: one barrier per tile, the slots alternate by tile parity.
 // T = 1 is what every launch takes (mle_multifold2_tiles: more tiles per block read slower); the option fold2_tiles forces more.
 // grid = (I / (8 T), batch): block x = (c >> 2) * (I / (64 T)) + it / T; block = 256
+// PUB: every partial is ALSO stored as a flag-in-word record (flagged_rec.h) in the partial's own slot of `flagged`, by ten lanes of the
+// finishing wave, for launches of kFlagRecsPerTable partials per table of g >= 16 entries; the host totals them and no reduce launch follows.  The device-memory partials
+// stay: the last streaming launch of a call publishes through k_mle_sub_reduce (capi_mle_passes.hip).
+template <bool PUB>
 __global__ void __launch_bounds__(256, 3) k_mle_multifold2_mfma(const Fr* __restrict__ src, size_t src_stride, Fr* __restrict__ dst, size_t dst_stride,
                                                              uint32_t S, const MfmaFoldPlan* __restrict__ plans, const Fr* __restrict__ w2,
-                                                             MleSubPartial* __restrict__ partials, uint32_t T) {
+                                                             MleSubPartial* __restrict__ partials, uint32_t T, uint64_t* __restrict__ flagged,
+                                                             uint32_t ticket) {
     __shared__ Fr s_prod[2][3][64];   // [tile parity][wave behind the finishing one][lane]
     __shared__ __attribute__((aligned(16))) unsigned char digits[32 * 32 * (1 << kMfmaMaxJ) + 128];   // (+ the accumulators' start values)
     const Fr* s = src + (size_t)blockIdx.y * src_stride;
@@ -725,6 +827,20 @@ __global__ void __launch_bounds__(256, 3) k_mle_multifold2_mfma(const Fr* __rest
                     MleSubPartial* p = part + (size_t)((64u * it + lane) / g) * 8u;
                     p->sum = acc;
                     p->dep = 0;
+                }
+                if constexpr (PUB) {
+                    // lanes [r g, r g + 10) take the ten words of partial r from lane r g (g >= 16): ONE store instruction of 80
+                    // contiguous bytes per record.  (A lane storing its record word by word made ten 8-byte writes to host memory
+                    // of each, and the fold ran seven to thirty times as long: profiles/r26.)
+                    const uint32_t from = lane & ~(g - 1u), wl = lane & (g - 1u);
+                    uint32_t word = 0u;   // (the tenth word: a fold's partials carry no dep bit)
+#pragma unroll
+                    for (int l = 0; l < 9; ++l) {
+                        const uint32_t v = __shfl(acc.l[l], from, 64);
+                        word = wl == (uint32_t)l ? v : word;
+                    }
+                    if (wl < kFlagRecWords)
+                        mle_flag_store(flagged + ((size_t)blockIdx.y * kFlagRecsPerTable + ((64u * it + from) / g) * 8u + cq) * kFlagRecWords + wl, word, ticket);
                 }
             }
             ++it;
@@ -2925,9 +3041,17 @@ static int mle_sub_sums_stream_form(uint32_t len, uint32_t batch, uint32_t nblk,
     return chunk % 256u == 0 && nblk % 4u == 0 ? 1 : 0;
 }
 
-void launch_mle_sub_sums(const Fr* tables, size_t stride, uint32_t len, uint32_t batch, uint32_t nblk, MleSubPartial* partials,
-                         hipStream_t s, const MlePublish* publish) {
+// flagged (may be null; pinned, batch x kFlagRecsPerTable records): where the launch takes the rolling form with kFlagRecsPerTable
+// blocks per table, its blocks publish there under flag_ticket and the return value is true -- NO reduce launch is to follow.  Every
+// other launch ignores it and returns false.
+bool launch_mle_sub_sums(const Fr* tables, size_t stride, uint32_t len, uint32_t batch, uint32_t nblk, MleSubPartial* partials,
+                         hipStream_t s, const MlePublish* publish, uint64_t* flagged, uint32_t flag_ticket) {
     const int form = mle_sub_sums_stream_form(len, batch, nblk, publish != nullptr);
+    if (form == 3 && flagged && nblk == 4u * kFlagRecsPerTable) {
+        hipLaunchKernelGGL((k_mle_sub_sums_roll_pub<16, true>), dim3(nblk / 4u, batch), dim3(256), 0, s, tables, stride, len / nblk, nblk, partials, flagged,
+                           flag_ticket);
+        return true;
+    }
     if (form == 3)
         hipLaunchKernelGGL((k_mle_sub_sums_roll<16, 1, true>), dim3(nblk / 4u, batch), dim3(256), 0, s, tables, stride, len / nblk, nblk, partials);
     else if (form == 2)
@@ -2936,6 +3060,7 @@ void launch_mle_sub_sums(const Fr* tables, size_t stride, uint32_t len, uint32_t
         hipLaunchKernelGGL((k_mle_sub_sums_stream<8, 1>), dim3(nblk / 4u, batch), dim3(256), 0, s, tables, stride, len / nblk, nblk, partials);
     else
         hipLaunchKernelGGL(k_mle_sub_sums, dim3(nblk, batch), dim3(256), 0, s, tables, stride, len, partials, publish ? *publish : MlePublish{});
+    return false;
 }
 
 void launch_mle_sub_reduce(const MleSubPartial* partials, uint32_t nblk, uint32_t jout, uint32_t batch, MleHostRecSub* host_rec,
@@ -3060,11 +3185,22 @@ uint32_t mle_multifold2_tiles(uint32_t S) {
 }
 
 // S = 2^(n-5) with 2^13 <= S <= 2^19; dst: eight planes of S / 32 entries per table; w2: device memory
-void launch_mle_multifold2(const Fr* src, size_t src_stride, Fr* dst, size_t dst_stride, uint32_t S, uint32_t batch, const void* plans, const Fr* w2,
-                           MleSubPartial* partials, hipStream_t s) {
+// flagged / flag_ticket / return value: as launch_mle_sub_sums' (here for launches of kFlagRecsPerTable partials per table, each of at
+// least sixteen entries: 2^19 <= table <= 2^21).  `ended` (may be null; with a publishing launch): an event the kernel's own completion
+// fires -- hipExtLaunchKernelGGL's stop event, bound to the dispatch, not a packet of its own behind it; it still costs the launch
+// behind it ~5 us (profiles/r26), so the driver asks for it once per call
+bool launch_mle_multifold2(const Fr* src, size_t src_stride, Fr* dst, size_t dst_stride, uint32_t S, uint32_t batch, const void* plans, const Fr* w2,
+                           MleSubPartial* partials, hipStream_t s, uint64_t* flagged, uint32_t flag_ticket, hipEvent_t ended) {
     const uint32_t T = mle_multifold2_tiles(S);
-    hipLaunchKernelGGL(k_mle_multifold2_mfma, dim3((S >> 8) / T, batch), dim3(256), 0, s, src, src_stride, dst, dst_stride, S,
-                       static_cast<const MfmaFoldPlan*>(plans), w2, partials, T);
+    const bool pub = flagged && mle_multifold2_partials(S) == kFlagRecsPerTable && (S >> (2 * kMfmaMaxJ)) >= 16u;   // (g = min(I / 32, 64))
+    const MfmaFoldPlan* pl = static_cast<const MfmaFoldPlan*>(plans);
+    if (pub)
+        hipExtLaunchKernelGGL(k_mle_multifold2_mfma<true>, dim3((S >> 8) / T, batch), dim3(256), 0, s, nullptr, ended, 0, src, src_stride, dst, dst_stride, S, pl,
+                              w2, partials, T, flagged, flag_ticket);
+    else
+        hipLaunchKernelGGL(k_mle_multifold2_mfma<false>, dim3((S >> 8) / T, batch), dim3(256), 0, s, src, src_stride, dst, dst_stride, S, pl, w2, partials, T,
+                           (uint64_t*)nullptr, 0u);
+    return pub;
 }
 
 void launch_mle_round_reduce(const MlePartial* partials, uint32_t nblk, uint32_t batch, MleHostRec* host_rec,

@@ -24,6 +24,7 @@ namespace gkr {
     X(first_fold_levels, "first_fold_levels", "GKR_FIRST_FOLD_LEVELS", 0, "variables the first fold of a host-hashed 2^18 .. 2^24-point sumcheck binds: 1 five, 2 ten in the one read (0: the default, capi_internal.h kMleFirstFoldLevels)") \
     X(pass0_stream, "pass0_stream", "GKR_PASS0_STREAM", 0, "pass 0 of a streaming launch of the plain sumcheck: 1 k_mle_sub_sums (a block per partial), 2 its pipelined form (a wave per one or two partials, 16-byte loads kept in flight in two sets) where it applies, 3 as 2 with the rolling form (a wave per partial, ONE buffer of sixteen loads, every XCD on a contiguous eighth of the launch) in place of the form of two partials per wave (0: the default, kernels.h kMlePass0Stream)") \
     X(fold2_tiles, "fold2_tiles", "GKR_FOLD2_TILES", 0, "64-entry tiles a block of the two-level first fold takes: k forces min(k, 2^(n-16)), a power of two (0: one, which is fastest where measured)") \
+    X(stream_publish, "stream_publish", "GKR_STREAM_PUBLISH", 0, "streaming passes of a batch in several groups on the two-level schedule (the rolling pass 0, the two-level first fold; not the call's last streaming launch): 1 every pass publishes through k_mle_sub_reduce, 2 their blocks publish flag-in-word records to pinned memory, which the hashing threads total -- no reduce launch between two streaming launches (0: the default, 2)") \
     X(no_fused_reduce, "no_fused_reduce", "GKR_NO_FUSED_REDUCE", 0, "latency-bound passes publish through k_mle_sub_reduce instead of from their last block") \
     X(hash_chunk, "hash_chunk", "GKR_HASH_CHUNK", 0, "8 or 16: sumchecks per host hash call (0: 16 when host threads are scarce)")    \
     X(device_hash_percent, "device_hash_percent", "GKR_DEVICE_HASH_PERCENT", 0, "share of a batch of >= 64 plain sumchecks hashed on the device (0..90)") \

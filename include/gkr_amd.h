@@ -289,7 +289,9 @@ int  gkr_sumcheck_mle(gkr_ctx *ctx, const gkr_fr *table, int n, gkr_fr *out_coef
  * first_fold_levels (ten variables bound in the first fold's one read, 18 <= n <= 24) and option pass0_stream (pass 0 of a
  * streaming launch as a pipelined read: 1 a block per partial sum, 2 a wave per partial with its loads kept in flight, 3 the
  * same through one rolling load buffer on the large launches, the default); option
- * fold2_tiles (64-entry tiles a block of that first fold takes: 0 one, k at most k). */
+ * fold2_tiles (64-entry tiles a block of that first fold takes: 0 one, k at most k); option stream_publish (how the streaming
+ * passes of a batch in several groups hand their sums to the host: 1 through a reduce launch behind every pass, 2 -- the default --
+ * as flag-in-word records the blocks store to pinned memory themselves and the hashing threads total, where that applies). */
 int  gkr_sumcheck_mle_batch_device(gkr_ctx *ctx, const void *d_tables, int n, int batch,
                                    gkr_fr *out_coeffs, uint32_t *out_len, gkr_fr *out_r);
 

@@ -6,7 +6,9 @@
 //   tools/bin/ubench_pass0 [n] [batch] [reps] [nblk]
 // Variants: the two-set form <16, 2> (the baseline); the rolling form (U, PPW) = (16, 1), (16, 2), (16, 4), (32, 2) as blocks of four
 // waves, (16, 2) as blocks of two and of ONE wave; the same with every XCD's blocks on a contiguous eighth of the launch ("runs");
-// U = 8 for the launches of few tables.  Only variants whose conditions the shape meets are run.
+// U = 8 for the launches of few tables; and <16, 1> with runs as the PUBLISHING instance (k_mle_sub_sums_roll_pub: every block also stores
+// a flag-in-word record to pinned host memory, whose words are checked against the sum of the block's four reference partials).
+// Only variants whose conditions the shape meets are run.
 #include "../gkr_amd/csrc/kernels.hip"
 
 #include <algorithm>
@@ -47,6 +49,7 @@ struct Variant {
     const char* name;
     void (*kernel)(const Fr*, size_t, uint32_t, uint32_t, MleSubPartial*);
     uint32_t u, ppw, waves;   // loads per lane, partials per wave, waves per block
+    bool pub = false;         // the publishing instance (kernel == nullptr: it has two more arguments)
 };
 
 int main(int argc, char** argv) {
@@ -68,6 +71,7 @@ int main(int argc, char** argv) {
         {"rolling  <16, 2>, 2 waves, runs", k_mle_sub_sums_roll<16, 2, true>, 16, 2, 2},
         {"rolling  <16, 2>, 1 wave,  runs", k_mle_sub_sums_roll<16, 2, true>, 16, 2, 1},
         {"rolling  <16, 1>, 4 waves, runs", k_mle_sub_sums_roll<16, 1, true>, 16, 1, 4},
+        {"rolling  <16, 1>, 4 w, runs, PUB", nullptr, 16, 1, 4, true},
         {"rolling  <32, 2>, 4 waves, runs", k_mle_sub_sums_roll<32, 2, true>, 32, 2, 4},
         {"rolling  <8, 1>,  4 waves      ", k_mle_sub_sums_roll<8, 1, false>, 8, 1, 4},
         {"rolling  <8, 1>,  4 waves, runs", k_mle_sub_sums_roll<8, 1, true>, 8, 1, 4},
@@ -91,8 +95,28 @@ int main(int argc, char** argv) {
     const size_t npart = (size_t)batch * nblk, part_bytes = npart * sizeof(MleSubPartial);
     CK(hipMalloc(&partials, part_bytes));
     CK(hipDeviceSynchronize());
+    uint64_t* flagged;   // nblk / 4 records per table
+    const size_t nrec = npart / 4u;
+    CK(hipHostMalloc(&flagged, nrec * kFlagRecWords * sizeof(uint64_t), hipHostMallocCoherent | hipHostMallocMapped));
+    memset(flagged, 0, nrec * kFlagRecWords * sizeof(uint64_t));
+    uint32_t ticket = 0;
     auto launch = [&](const Variant& v, int set) {
-        hipLaunchKernelGGL(v.kernel, dim3(nblk / (v.ppw * v.waves), batch), dim3(64u * v.waves), 0, 0, tables[set], len, chunk, nblk, partials);
+        if (v.pub)
+            hipLaunchKernelGGL((k_mle_sub_sums_roll_pub<16, true>), dim3(nblk / 4u, batch), dim3(256), 0, 0, tables[set], len, chunk, nblk, partials, flagged,
+                               next_ticket(ticket));
+        else
+            hipLaunchKernelGGL(v.kernel, dim3(nblk / (v.ppw * v.waves), batch), dim3(64u * v.waves), 0, 0, tables[set], len, chunk, nblk, partials);
+    };
+    // every word of every record: the ticket, and the limb of the sum of the block's four reference partials (the OR of their flags)
+    auto records_same = [&](const std::vector<MleSubPartial>& ref) {
+        for (size_t r = 0; r < nrec; ++r) {
+            Acc<9> tot = acc_zero<9>();
+            uint32_t dep = 0;
+            for (int w = 0; w < 4; ++w) acc_add_acc(tot, ref[4 * r + w].sum), dep |= ref[4 * r + w].dep;
+            for (uint32_t l = 0; l < kFlagRecWords; ++l)
+                if (flagged[r * kFlagRecWords + l] != flag_word(l < 9u ? tot.l[l] : dep, ticket)) return false;
+        }
+        return true;
     };
 
     // ---- the same partials as k_mle_sub_sums, flags included
@@ -115,7 +139,7 @@ int main(int argc, char** argv) {
             launch(v, set);
             CK(hipDeviceSynchronize());
             CK(hipMemcpy(got.data(), partials, part_bytes, hipMemcpyDeviceToHost));
-            const bool ok = same();
+            const bool ok = same() && (!v.pub || records_same(ref));
             if (set == 0 || !ok) printf("%s: partials and flags %s k_mle_sub_sums'\n", v.name, ok ? "identical to" : "DIFFER from");
             if (!ok) return 1;
         }
