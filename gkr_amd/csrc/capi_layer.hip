@@ -658,6 +658,54 @@ int gkr_sumcheck_layer(gkr_ctx* ctx, int k_i, int k_next, const uint8_t* gate_ty
     return run_layer_batch(ctx, 1, k_i, k_next, dgt.p, dl.p, dr.p, z, dW.p, &out_coeffs, &out_len, &out_r);
 }
 
+// What the list build of a whole layer decides (tests pin the thresholds of the gate passes on it): the build that
+// run_layer_gates queues, into lists of their own as a circuit's cache holds them, and the counts it left.
+int gkr_devtest_gate_plan(gkr_ctx* ctx, int k_i, int k_next, const uint8_t* gate_type, const uint32_t* left, const uint32_t* right,
+                          uint32_t* form, uint32_t* counts) {
+    if (!ctx) return GKR_ERR_INVALID;
+    if (!gate_type || !left || !right || !form || !counts) return ctx->fail(GKR_ERR_INVALID, "null pointer");
+    if (k_i < 0 || k_i > kMaxLayerKi || k_next < 1 || k_next > kMaxLayerK)
+        return ctx->fail(GKR_ERR_INVALID, "k_next must be in [1, GKR_MAX_K_NEXT], k_i in [0, GKR_MAX_K_I]");
+    GKR_ENTER(ctx);
+    DevBuf<uint8_t> dgt;
+    DevBuf<uint32_t> dl, dr;
+    int rc = upload_gates(ctx, (size_t)1 << k_i, gate_type, left, right, dgt, dl, dr);
+    if (rc) return rc;
+    const gkr::GateSpan span{0, (uint64_t)1 << k_i};
+    const bool wide = layer_is_wide(span, k_i, k_next);
+    GateLists g;
+    uint32_t* bad = nullptr;
+    uint32_t seg_items[2] = {0, 0};
+    rc = queue_gate_lists(ctx, span, k_i, k_next, dgt.p, dl.p, dr.p, wide, &g, true, &bad);
+    if (!rc) rc = validate_gate_lists(ctx, span, k_next, wide, bad, &g, true);
+    if (!rc && g.segs.shift) {
+        uint32_t ends[2] = {0, 0};   // the items before the second half's first bucket, and all of them
+        const hipError_t e0 = hipMemcpy(&ends[0], g.segs.bucket_begin() + g.segs.nb, 4, hipMemcpyDeviceToHost);
+        const hipError_t e1 = hipMemcpy(&ends[1], g.segs.bucket_begin() + 2 * (size_t)g.segs.nb, 4, hipMemcpyDeviceToHost);
+        if (e0 != hipSuccess || e1 != hipSuccess) rc = ctx->hip_fail(e0 != hipSuccess ? e0 : e1, "reading the segments' item counts");
+        seg_items[0] = ends[0];
+        seg_items[1] = ends[1] - ends[0];
+    }
+    memset(counts, 0, 16 * sizeof(uint32_t));
+    if (!rc) {
+        *form = g.segs.shift ? 2u : wide ? 1u : 0u;
+        for (int half = 0; half < 2; ++half) {
+            uint32_t* c = counts + 8 * half;
+            if (g.segs.shift) {
+                c[0] = g.segs.shift;
+                c[1] = g.segs.runs;
+                c[2] = (uint32_t)((((uint64_t)1 << g.segs.shift) * gkr::gate_lists_lds_blocks(span.count, (uint32_t)k_next)) >> k_i);
+                c[3] = seg_items[half];
+            } else if (wide) {
+                for (int w = 0; w < 6; ++w) c[w] = g.plan_counts.hdr[half][w];
+            }
+        }
+    }
+    (void)hipStreamSynchronize(ctx->stream);
+    g.release();
+    return rc;
+}
+
 int gkr_sumcheck_layer_sharded(gkr_ctx* ctx, int k_i, int k_next, uint64_t gate_first, uint64_t gate_count,
                                const uint8_t* gate_type, const uint32_t* left, const uint32_t* right, const gkr_fr* z,
                                const gkr_fr* W, gkr_allreduce_fn allreduce, void* user, gkr_fr* out_coeffs, uint32_t* out_len,

@@ -276,6 +276,14 @@ int  gkr_devtest_field(gkr_ctx *ctx, int op, const gkr_fr *a, const gkr_fr *b, c
 int  gkr_devtest_lazy(gkr_ctx *ctx, int op, int red, const gkr_fr *a, const gkr_fr *b, size_t rows, size_t len, gkr_fr *out);
 int  gkr_devtest_reduce(gkr_ctx *ctx, int op, const uint32_t *limbs, size_t n, uint32_t *out);
 int  gkr_devtest_lanes(gkr_ctx *ctx, int op, const gkr_fr *x, const gkr_fr *y, const gkr_fr *z, size_t n, gkr_fr *out);
+/* The gate lists of one layer (2^k_i gates over 2^k_next values, host arrays) as the layer sumcheck builds them under the
+ * context's options, and what the build decided: *form = 0 the bucket kernels, 1 the item plan of wide layers, 2 segments.
+ * counts: 2 x 8 words, left-operand half then right-operand half.  Form 1: the half's plan header words 0 .. 5 (items, groups,
+ * buckets of 2 .. 64 items, buckets of more, groups of two and more steps, chunks of the long buckets).  Form 2: shift (log2
+ * gates per run), runs, m (sort blocks per run), items of the half.  Unused words are 0.  Nothing is proven.
+ * GKR_ERR_INVALID: NULL pointer, k_i outside 0 .. GKR_MAX_K_I, k_next outside 1 .. GKR_MAX_K_NEXT, a gate out of range. */
+int  gkr_devtest_gate_plan(gkr_ctx *ctx, int k_i, int k_next, const uint8_t *gate_type, const uint32_t *left, const uint32_t *right,
+                           uint32_t *form, uint32_t *counts);
 
 /* ---- plain multilinear sumcheck: prove_sumcheck(g, v), sumcheck.rs:158-161 --- */
 /* table: 2^n canonical evaluations on the host.  out_coeffs: n rows x 2 slots;

@@ -416,6 +416,18 @@ def test_launch_geometry_of_the_product_sumcheck():
     assert not out.any()
 
 
+def test_gate_plan_devtest_refuses_a_missing_context():
+    """gkr_devtest_gate_plan builds a layer's gate lists on the device, so it needs a context: without one it returns
+    GKR_ERR_INVALID before it reads an argument (its other argument checks need a device: tests/test_gpu_gate_profiles.py)."""
+    assert "gkr_devtest_gate_plan" in N.SYMBOLS
+    lib = N.lib()
+    gt, l, r = np.zeros(4, dtype=np.uint8), np.zeros(4, dtype=np.uint32), np.zeros(4, dtype=np.uint32)
+    form, counts = np.full(1, 7, dtype=np.uint32), np.full(16, 7, dtype=np.uint32)
+    assert lib.gkr_devtest_gate_plan(None, 2, 1, _p(gt), _p(l), _p(r), _p(form), _p(counts)) == N.GKR_ERR_INVALID
+    assert lib.gkr_devtest_gate_plan(None, 2, 1, None, None, None, None, None) == N.GKR_ERR_INVALID
+    assert form[0] == 7 and (counts == 7).all()
+
+
 def test_limb_widening_for_the_modular_all_reduce():
     """gkr_fr_widen / gkr_fr_narrow (host only): field elements as eight 32-bit limbs in int64, so that an ordinary
     integer SUM all-reduce followed by narrow is the modular sum over ranks (RCCL has no modular sum)."""
