@@ -181,6 +181,56 @@ int gkr_predicate_tables(gkr_ctx* ctx, int k_i, int k_next, const uint8_t* gate_
     return GKR_OK;
 }
 
+// build_predicates with its shard arguments and a copy-back: one shard's tables of 2^(2 k_next - log_p) entries, as
+// gkr_layer_session_open builds them (the tests hold every shard to the whole layer's tables sliced by the cell rule)
+int gkr_devtest_predicates(gkr_ctx* ctx, int k_i, int k_next, const uint8_t* gate_type, const uint32_t* left, const uint32_t* right,
+                           const gkr_fr* z, uint32_t log_p, uint32_t shard, gkr_fr* out_A, gkr_fr* out_M) {
+    if (!ctx) return GKR_ERR_INVALID;
+    if (!out_A || !out_M) return ctx->fail(GKR_ERR_INVALID, "null pointer");
+    int rc = check_layer_args(ctx, k_i, k_next, gate_type, left, right, z);
+    if (rc) return rc;
+    if (k_next > kMaxDenseK || log_p > (uint32_t)k_next || shard >= (1u << log_p))
+        return ctx->fail(GKR_ERR_INVALID, "k_next <= GKR_MAX_K_NEXT_DEVICE_TRANSCRIPT, log_p <= k_next and shard < 2^log_p");
+    GKR_ENTER(ctx);
+    const size_t N = (size_t)1 << (2 * k_next - (int)log_p);
+    DevBuf<uint8_t> dgt;
+    DevBuf<uint32_t> dl, dr;
+    DevBuf<Fr> A, M;
+    rc = upload_gates(ctx, (size_t)1 << k_i, gate_type, left, right, dgt, dl, dr);
+    if (rc) return rc;
+    HIP_TRY(ctx, A.alloc(N));
+    HIP_TRY(ctx, M.alloc(N));
+    rc = build_predicates(ctx, k_i, k_next, dgt.p, dl.p, dr.p, z, A.p, M.p, log_p, shard);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(out_A, A.p, N * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(out_M, M.p, N * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->drain_events();
+    return GKR_OK;
+}
+
+// The launch geometry of the dense layer forms at one round, from the functions the launches call (host logic only).
+int gkr_selftest_layer_dense_geometry(int k_next, int log_p, int round, uint32_t out[8]) {
+    if (!out || k_next < 1 || k_next > kMaxDenseK || log_p < 0 || log_p > k_next || round < 0 || round >= 2 * k_next - log_p)
+        return GKR_ERR_INVALID;
+    memset(out, 0, 8 * sizeof(uint32_t));
+    const size_t N = (size_t)1 << (2 * k_next - log_p);
+    const uint32_t h = (uint32_t)(N >> (round + 1));
+    if (log_p == 0 && round < k_next) {   // run_layer_dense_proof's fused b-phase round: hb = h >> k row pairs, one proof
+        const gkr::LayerRoundBGrid g = gkr::layer_round_b_grid(h >> k_next, (uint32_t)k_next, 1u);
+        out[0] = g.col_blocks;
+        out[1] = g.chunks;
+        out[2] = g.rows_per_chunk;
+        out[3] = g.partials;
+    }
+    // gkr_layer_session_sums / _bind of a shard at this round (log_p = 0: also the device transcript's unfused round)
+    out[4] = gkr::layer_blocks(h) | (round < k_next ? 0u : 1u << 31);
+    out[5] = gkr::layer_fold_blocks(h, 1u);
+    out[6] = gkr::pred_scan_blocks(2 * N);
+    out[7] = gkr::pred_sum_blocks(2 * N);
+    return GKR_OK;
+}
+
 // ---- step-wise sessions: one sumcheck split across GPUs ------------------------
 //
 // The hypercube is partitioned by its TRAILING log2(P) variables: rank p owns the entries whose

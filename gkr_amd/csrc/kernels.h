@@ -566,6 +566,26 @@ void launch_r1cs_matrix_evals(const R1csCsr& csr, const Fr* ex_mont, const Fr* e
                               hipStream_t s);
 
 uint32_t layer_blocks(uint32_t h);
+// The grid of the fused b-phase round (launch_layer_round_b) over hb row pairs of 2^kc columns: ~1024 blocks per table over the
+// whole batch, every block at least one row pair.  grid = (col_blocks, chunks * batch, 2); partials = the slots one proof writes.
+// Host arithmetic only: the launch and gkr_selftest_layer_dense_geometry both call it.
+struct LayerRoundBGrid {
+    uint32_t col_blocks, chunks, rows_per_chunk, partials;
+};
+inline LayerRoundBGrid layer_round_b_grid(uint32_t hb, uint32_t kc, uint32_t batch) {
+    LayerRoundBGrid g;
+    g.col_blocks = ((1u << kc) + 255u) / 256u;
+    uint32_t chunks = 1024u / (g.col_blocks * batch);
+    if (chunks < 1) chunks = 1;
+    if (chunks > hb) chunks = hb;
+    g.rows_per_chunk = (hb + chunks - 1) / chunks;
+    g.chunks = (hb + g.rows_per_chunk - 1) / g.rows_per_chunk;
+    g.partials = g.col_blocks * g.chunks * 2;
+    return g;
+}
+uint32_t layer_fold_blocks(uint32_t h, uint32_t batch);   // blocks per proof of k_layer_fold over h pairs
+uint32_t pred_scan_blocks(size_t n);                      // blocks of k_scan_blocks / k_scan_add over n counters (launch_predicate_sorted)
+uint32_t pred_sum_blocks(size_t n);                       // blocks per proof of k_pred_sum over n cells
 void launch_layer_round(const Fr* A, const Fr* M, uint32_t h, uint32_t k, uint32_t phase, uint32_t hb, const Fr* Wb,
                         const Fr* Wc, uint32_t nblk, LayerPartial* partials, LayerBatch lb, hipStream_t s);
 uint32_t launch_layer_round_b(bool fold, const Fr* A_src, const Fr* M_src, Fr* A_dst, Fr* M_dst, uint32_t hb, uint32_t kc,

@@ -2737,6 +2737,9 @@ void launch_predicate_scatter(uint32_t k_i, uint32_t k_next, const uint8_t* gate
                        gate_type, left, right, e_hi, e_lo_mont, kl, wideA, wideM, bad, log_p, shard);
 }
 
+uint32_t pred_scan_blocks(size_t n) { return (uint32_t)((n + kScanPerBlock - 1) / kScanPerBlock); }
+uint32_t pred_sum_blocks(size_t n) { return blocks_for(n, 8192); }
+
 // counting-sort predicate build; counts/offsets/cursor: 2 * ncells u32 each, block_sums: ceil(2 ncells / 2048),
 // list: 2^k_i u32.  All scratch is caller-provided.
 void launch_predicate_sorted(uint32_t k_i, uint32_t k_next, const uint8_t* gate_type, const uint32_t* left,
@@ -2746,7 +2749,7 @@ void launch_predicate_sorted(uint32_t k_i, uint32_t k_next, const uint8_t* gate_
                              hipStream_t s) {
     const size_t n = 2 * ncells;
     const uint32_t gblocks = blocks_for(1ull << k_i, 4096);
-    const uint32_t sblocks = (uint32_t)((n + kScanPerBlock - 1) / kScanPerBlock);
+    const uint32_t sblocks = pred_scan_blocks(n);
     hipLaunchKernelGGL(k_pred_count, dim3(gblocks), dim3(256), 0, s, k_i, k_next, gate_type, left, right, log_p, shard, ncells,
                        counts, bad);
     hipLaunchKernelGGL(k_scan_blocks, dim3(sblocks), dim3(256), 0, s, counts, offsets, block_sums, n);
@@ -2754,7 +2757,7 @@ void launch_predicate_sorted(uint32_t k_i, uint32_t k_next, const uint8_t* gate_
     hipLaunchKernelGGL(k_scan_add, dim3(sblocks), dim3(256), 0, s, offsets, cursor, block_sums, n);
     hipLaunchKernelGGL(k_pred_fill, dim3(gblocks), dim3(256), 0, s, k_i, k_next, gate_type, left, right, log_p, shard, ncells,
                        cursor, list, bad);
-    hipLaunchKernelGGL(k_pred_sum, dim3(blocks_for(n, 8192), batch), dim3(256), 0, s, ncells, offsets, cursor, list, e_hi,
+    hipLaunchKernelGGL(k_pred_sum, dim3(pred_sum_blocks(n), batch), dim3(256), 0, s, ncells, offsets, cursor, list, e_hi,
                        e_lo_mont, kl, k_i - kl, out_A, out_M);
 }
 

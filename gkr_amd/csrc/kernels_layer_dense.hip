@@ -354,25 +354,22 @@ void launch_layer_round(const Fr* A, const Fr* M, uint32_t h, uint32_t k, uint32
 uint32_t launch_layer_round_b(bool fold, const Fr* A_src, const Fr* M_src, Fr* A_dst, Fr* M_dst, uint32_t hb, uint32_t kc,
                               const FixedMul* rtab, const Fr* Wb, const Fr* Wc, LayerPartial* partials, LayerBatch lb,
                               hipStream_t s) {
-    const uint32_t col_blocks = ((1u << kc) + 255u) / 256u;
-    // ~1024 blocks per table over the whole batch; every block gets at least one row pair
-    uint32_t chunks = 1024u / (col_blocks * lb.batch);
-    if (chunks < 1) chunks = 1;
-    if (chunks > hb) chunks = hb;
-    const uint32_t rows_per_chunk = (hb + chunks - 1) / chunks;
-    chunks = (hb + rows_per_chunk - 1) / rows_per_chunk;
-    dim3 grid(col_blocks, chunks * lb.batch, 2);
+    const LayerRoundBGrid g = layer_round_b_grid(hb, kc, lb.batch);
+    const uint32_t chunks = g.chunks, rows_per_chunk = g.rows_per_chunk;
+    dim3 grid(g.col_blocks, chunks * lb.batch, 2);
     if (fold)
         hipLaunchKernelGGL(k_layer_round_b<true>, grid, dim3(256), 0, s, A_src, M_src, A_dst, M_dst, hb, kc, rows_per_chunk,
                            rtab, Wb, Wc, partials, lb, chunks);
     else
         hipLaunchKernelGGL(k_layer_round_b<false>, grid, dim3(256), 0, s, A_src, M_src, A_dst, M_dst, hb, kc, rows_per_chunk,
                            rtab, Wb, Wc, partials, lb, chunks);
-    return col_blocks * chunks * 2;   // partials per proof
+    return g.partials;   // partials per proof
 }
 
+uint32_t layer_fold_blocks(uint32_t h, uint32_t batch) { return blocks_for(h, 4096 / batch + 1); }
+
 void launch_layer_fold(Fr* A, Fr* M, uint32_t h, const FixedMul* rtab, LayerBatch lb, hipStream_t s) {
-    hipLaunchKernelGGL(k_layer_fold, dim3(blocks_for(h, 4096 / lb.batch + 1), lb.batch), dim3(256), 0, s, A, M, h, rtab, lb);
+    hipLaunchKernelGGL(k_layer_fold, dim3(layer_fold_blocks(h, lb.batch), lb.batch), dim3(256), 0, s, A, M, h, rtab, lb);
 }
 
 void launch_layer_round_hash(const LayerPartial* partials, uint32_t nblk, uint32_t round, uint32_t k,

@@ -214,6 +214,15 @@ int  gkr_selftest_pass_schedule(int n, int mfma, uint32_t *rounds, size_t capaci
  * chunk[j] = the entries a block walks, as the kernels derive it: ((items + nblk - 1) / nblk + 255) & ~255 with items = 2^(n-1-j).
  * GKR_ERR_INVALID: NULL pointer, batch outside 1 .. 65535, n outside 2 .. GKR_MAX_MLE_N, batch * 2^n above 2^30. */
 int  gkr_selftest_product_geometry(int n, int batch, uint32_t *nblk, uint32_t *chunk);
+/* the launch geometry of the dense layer forms (host logic, from the functions the launches call) at round `round` (0-based) of a
+ * layer over 2^k_next values cut into 2^log_p trailing-variable shards, N = 2^(2 k_next - log_p) cells per table, h = N >> (round + 1):
+ * out[0 .. 3] = column blocks, row chunks, rows per chunk and partials of the device transcript's fused b-phase round (log_p = 0 and
+ * round < k_next; otherwise 0); out[4] = the blocks of the session's (and the unfused device transcript's) round kernel over h pairs,
+ * bit 31 set in the c-phase (round >= k_next); out[5] = the blocks of the table fold over h pairs; out[6] = the scan blocks of the
+ * predicate build, ceil(2 N / 2048); out[7] = the blocks of its sum kernel over 2 N cells.
+ * GKR_ERR_INVALID: NULL pointer, k_next outside 1 .. GKR_MAX_K_NEXT_DEVICE_TRANSCRIPT, log_p outside 0 .. k_next, round outside
+ * 0 .. 2 k_next - log_p - 1. */
+int  gkr_selftest_layer_dense_geometry(int k_next, int log_p, int round, uint32_t out[8]);
 /* q(t) = W(b + t (c - b)) (reduce_multiple_polynomial, poly.rs:469-500) as gkr_prove computes it on the host: W = 2^k
  * evaluations; out = k + 1 slots right-aligned, highest degree first; *out_len = 1 + largest monomial degree of W */
 int  gkr_selftest_line_restriction(int k, const gkr_fr *W, const gkr_fr *b, const gkr_fr *c, gkr_fr *out, uint32_t *out_len);
@@ -284,6 +293,12 @@ int  gkr_devtest_lanes(gkr_ctx *ctx, int op, const gkr_fr *x, const gkr_fr *y, c
  * GKR_ERR_INVALID: NULL pointer, k_i outside 0 .. GKR_MAX_K_I, k_next outside 1 .. GKR_MAX_K_NEXT, a gate out of range. */
 int  gkr_devtest_gate_plan(gkr_ctx *ctx, int k_i, int k_next, const uint8_t *gate_type, const uint32_t *left, const uint32_t *right,
                            uint32_t *form, uint32_t *counts);
+/* One shard's dense predicate tables as gkr_layer_session_open builds them under the context's options: shard `shard` of 2^log_p
+ * keeps the gates whose right operand has low bits `shard`; out_A, out_M: 2^(2 k_next - log_p) canonical values each, cell
+ * (l << (k_next - log_p)) | (r >> log_p).  log_p = 0: gkr_predicate_tables.  GKR_ERR_INVALID: NULL pointer, k_next above
+ * GKR_MAX_K_NEXT_DEVICE_TRANSCRIPT, log_p > k_next, shard >= 2^log_p, a gate out of range. */
+int  gkr_devtest_predicates(gkr_ctx *ctx, int k_i, int k_next, const uint8_t *gate_type, const uint32_t *left, const uint32_t *right,
+                            const gkr_fr *z, uint32_t log_p, uint32_t shard, gkr_fr *out_A, gkr_fr *out_M);
 
 /* ---- plain multilinear sumcheck: prove_sumcheck(g, v), sumcheck.rs:158-161 --- */
 /* table: 2^n canonical evaluations on the host.  out_coeffs: n rows x 2 slots;
