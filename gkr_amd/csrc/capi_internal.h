@@ -4,7 +4,7 @@
 // its dense form; capi_prove.hip: whole proofs; capi_product.hip: the sumcheck over a product of resident tables; capi_sop.hip: over a sum of
 // such products; capi_zerocheck.hip: the zero-check -- the entry points and shape checks of the three, whose one driver is
 // capi_resident.hip; capi_r1cs.hip: an R1CS's tables in front of it; capi_r1cs_verify.hip: the verifier of that pair of
-// sumchecks): the context,
+// sumchecks; capi_grand_product.hip: the grand product, a product tree and a zero-check per layer, and its verifier): the context,
 // its caches and workspaces, profiling brackets, the host transcript's helpers, the hand-off wait, the plain sumcheck's group
 // hand-off.  Not a public header.
 #pragma once

@@ -341,6 +341,14 @@ void launch_zc_round(const SopTerms& ts, const SopCoeffs& cf, const ProductParti
                      uint32_t batch, const Fr* cts, const Fr* z, Fr* s_slot, const Fr* work, size_t work_stride, Fr* out_coeffs,
                      uint32_t* out_len, Fr* out_r, FixedMul* rtab, Fr* evals, Fr* eq_out, hipStream_t s);
 
+// ---- the grand product's tree (kernels_grand_product.hip): L_k[i] = L_{k+1}[i] * L_{k+1}[i + 2^k], every level stored ----
+// One launch per level k = n-1 .. 0, gp_level_blocks(k) = ceil(2^k / 256) blocks of 256 threads per table, a thread per product.
+uint32_t gp_level_blocks(uint32_t k);
+// level k (2^k entries per table) of a batch's trees starts at this element of `layers`, table b at + b * 2^k
+__host__ __device__ inline size_t gp_layer_offset(uint32_t level, uint32_t batch) { return (size_t)batch * (((size_t)1 << level) - 1); }
+// tables: batch x 2^n canonical values, table b at + b * 2^n, not modified; layers: batch * (2^n - 1) elements, levels 0 .. n-1
+void launch_gp_tree(const Fr* tables, uint32_t n, uint32_t batch, Fr* layers, hipStream_t s);
+
 void launch_layer_eval(uint32_t gates, const uint8_t* gate_type, const uint32_t* left, const uint32_t* right,
                        const Fr* prev, Fr* out, uint32_t batch, uint32_t prev_stride, hipStream_t s, const GateSet* sets = nullptr);
 // words 32-bit words src -> dst (16-byte aligned when words >= 4); either side may be pinned host memory

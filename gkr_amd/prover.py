@@ -579,6 +579,104 @@ class Context:
         pts = self._points(z, batch, n)
         self._check(N.lib().gkr_eq_table_device(self._h, _ptr(pts), n, batch, d_out, (1 << n) if stride is None else int(stride)))
 
+    # -- the grand product P = prod_i V[i]: the product tree on the device, a zero-check per layer, chained by Fiat-Shamir
+    @staticmethod
+    def grand_product_rounds(n):
+        """R = n (n - 1) / 2 - 1: the rounds of the layers k = 2 .. n - 1 of a grand product over 2^n values; layer k's rows start
+        at k (k - 1) / 2 - 1."""
+        return n * (n - 1) // 2 - 1
+
+    def grand_product_batch_device(self, d_tables, n, batch, out=None):
+        """gkr_grand_product_batch_device: `batch` grand products over resident tables of 2^n canonical values (table b at
+        d_tables + b * 2^n elements; not modified), n >= 3.  -> (P, H, C, L, R, E, Z, K): P (batch, 4) the products; H (batch, 4, 4)
+        the heads L_2; C (batch, R, 4, 4) the layers' right-aligned round vectors, layers k = 2 .. n - 1 in order,
+        R = grand_product_rounds(n); L (batch, R); R (batch, R, 4) the challenges; E (batch, n - 2, 2, 4) the layers' values
+        (a_k, b_k); Z (batch, n, 4) the final point z^(n); K (batch, 4) the final claim c_n = V~(z^(n)).  Each layer is byte for
+        byte sumcheck_zerocheck_batch_device on the two halves of the level below.  out: the eight arrays of an earlier call."""
+        rounds = self.grand_product_rounds(n)
+        shapes = [((batch, 4), np.uint64), ((batch, 4, 4), np.uint64), ((batch, rounds, 4, 4), np.uint64), ((batch, rounds), np.uint32),
+                  ((batch, rounds, 4), np.uint64), ((batch, n - 2, 2, 4), np.uint64), ((batch, n, 4), np.uint64), ((batch, 4), np.uint64)]
+        if n < 3 or batch < 1:
+            raise GkrError(N.GKR_ERR_INVALID, "n >= 3 and batch >= 1 expected")
+        if out is not None:
+            if len(out) != 8 or any(a.shape != s or a.dtype != d for a, (s, d) in zip(out, shapes)):
+                raise GkrError(N.GKR_ERR_INVALID, "output arrays do not match (batch, n)")
+        else:
+            out = tuple(np.zeros(s, dtype=d) for s, d in shapes)
+        self._check(N.lib().gkr_grand_product_batch_device(self._h, d_tables, n, batch, *(_ptr(a) for a in out)))
+        return out
+
+    def prove_grand_product(self, table, v):
+        """The grand product of a table of 2^v values (v >= 3) with its GKR proof.  -> (product, head, layers, point, claim):
+        head = L_2 (four values, product = their product); layers[k - 2] = (proof, r, (a_k, b_k)) of the zero-check of layer
+        k = 2 .. v - 1 (proof[j] the round vector's used slots, highest degree first); point = z^(v) and claim = c_v, the
+        evaluation of the table the proof leaves.  verifier.verify_grand_product checks it on plain integers."""
+        limbs = as_limbs(table)
+        if v < 3 or limbs.shape[0] != 1 << v:
+            raise GkrError(N.GKR_ERR_INVALID, "a table of 2^v values, v >= 3, expected")
+        rounds = self.grand_product_rounds(v)
+        P, H = np.zeros((1, 4), dtype=np.uint64), np.zeros((4, 4), dtype=np.uint64)
+        C, L, R = np.zeros((rounds, 4, 4), dtype=np.uint64), np.zeros(rounds, dtype=np.uint32), np.zeros((rounds, 4), dtype=np.uint64)
+        E, Z, K = np.zeros((v - 2, 2, 4), dtype=np.uint64), np.zeros((v, 4), dtype=np.uint64), np.zeros((1, 4), dtype=np.uint64)
+        self._check(N.lib().gkr_grand_product(self._h, _ptr(limbs), v, _ptr(P), _ptr(H), _ptr(C), _ptr(L), _ptr(R), _ptr(E), _ptr(Z), _ptr(K)))
+        rs, layers = from_limbs(R), []
+        for k in range(2, v):
+            row = k * (k - 1) // 2 - 1
+            layers.append(([from_limbs(C[row + j])[4 - int(L[row + j]):] for j in range(k)], rs[row:row + k], tuple(from_limbs(E[k - 2]))))
+        return from_limbs(P)[0], from_limbs(H), layers, from_limbs(Z), from_limbs(K)[0]
+
+    def verify_grand_product_batch_device(self, d_tables, n, batch, H, C, L, R, E, products=None):
+        """gkr_grand_product_verify_batch_device on the resident tables and the arrays grand_product_batch_device returned (its H,
+        C, L, R, E); products: (batch, 4) limbs of claimed products or None.  -> (accept (batch,) bool, failed_layer, failed_round,
+        failed_check (batch,) uint32, products (batch, 4): the heads' own products).  verifier.verify_grand_product is the same
+        verdict on plain integers."""
+        rounds = self.grand_product_rounds(n)
+        H, C, R, E = (np.ascontiguousarray(a, dtype=np.uint64) for a in (H, C, R, E))
+        L = np.ascontiguousarray(L, dtype=np.uint32)
+        if (H.shape != (batch, 4, 4) or C.shape != (batch, rounds, 4, 4) or L.shape != (batch, rounds) or R.shape != (batch, rounds, 4)
+                or E.shape != (batch, n - 2, 2, 4)):
+            raise GkrError(N.GKR_ERR_INVALID, "proof arrays do not match (batch, n)")
+        if products is not None:
+            products = np.ascontiguousarray(products, dtype=np.uint64)
+            if products.shape != (batch, 4):
+                raise GkrError(N.GKR_ERR_INVALID, "products of shape (batch, 4) expected")
+        accept = np.zeros(batch, dtype=np.int32)
+        layer, rnd, check = (np.zeros(batch, dtype=np.uint32) for _ in range(3))
+        out = np.zeros((batch, 4), dtype=np.uint64)
+        self._check(N.lib().gkr_grand_product_verify_batch_device(self._h, d_tables, n, batch, _ptr(products) if products is not None else None,
+                                                                  _ptr(H), _ptr(C), _ptr(L), _ptr(R), _ptr(E), _ptr(accept), _ptr(layer), _ptr(rnd),
+                                                                  _ptr(check), _ptr(out)))
+        return accept.astype(bool), layer, rnd, check, out
+
+    def verify_grand_product(self, table, head, layers, product=None):
+        """gkr_grand_product_verify on a host table and what prove_grand_product returned (its head and layers; product: the claimed
+        product or None).  -> (check, layer, round), (0, 0, 0) for an accepted proof: verifier.verify_grand_product's verdict."""
+        limbs = as_limbs(table)
+        n = len(layers) + 2
+        if limbs.shape[0] != 1 << n or len(head) != 4:
+            raise GkrError(N.GKR_ERR_INVALID, "a table of 2^n values, four head values and n - 2 layers expected")
+        rounds = self.grand_product_rounds(n)
+        C, L, R = np.zeros((rounds, 4, 4), dtype=np.uint64), np.zeros(rounds, dtype=np.uint32), np.zeros((rounds, 4), dtype=np.uint64)
+        E = np.zeros((n - 2, 2, 4), dtype=np.uint64)
+        for k, (proof, r, ab) in enumerate(layers, start=2):
+            row = k * (k - 1) // 2 - 1
+            if len(proof) != k or len(r) != k or len(ab) != 2:
+                raise GkrError(N.GKR_ERR_INVALID, "layer k has k round vectors, k challenges and two values")
+            for j, g in enumerate(proof):
+                L[row + j] = len(g)
+                if 1 <= len(g) <= 4:                                       # (another length: SHAPE, the slots are not read)
+                    C[row + j, 4 - len(g):] = to_limbs([int(c) for c in g])
+            R[row:row + k] = to_limbs([int(x) for x in r])
+            E[k - 2] = to_limbs([int(x) for x in ab])
+        H = to_limbs([int(x) for x in head])
+        pl = to_limbs([int(product)]) if product is not None else None
+        accept = ctypes.c_int(0)
+        layer, rnd, check = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+        self._check(N.lib().gkr_grand_product_verify(self._h, _ptr(limbs), n, _ptr(pl) if pl is not None else None, _ptr(H), _ptr(C), _ptr(L),
+                                                     _ptr(R), _ptr(E), ctypes.byref(accept), ctypes.byref(layer), ctypes.byref(rnd),
+                                                     ctypes.byref(check)))
+        return int(check.value), int(layer.value), int(rnd.value)
+
     # -- the R1CS zero-check: Az, Bz, Cz of resident witnesses built on the device, then eq(z, .) (A B - C)
     def r1cs_rows(self, r1cs) -> R1csRows:
         """gkr_r1cs_rows_prepare: the CSR form of `r1cs` (convert.R1cs) resident on this context's device."""
@@ -1170,6 +1268,10 @@ def prove_sumcheck_sop(tables, terms, v):
 
 def prove_zerocheck(tables, terms, z, v):
     return default_context().prove_zerocheck(tables, terms, z, v)
+
+
+def prove_grand_product(table, v):
+    return default_context().prove_grand_product(table, v)
 
 
 def prove_r1cs_zerocheck(r1cs, witness, z):

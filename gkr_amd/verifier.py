@@ -320,6 +320,56 @@ def verify_r1cs(constraints, z: List[int], rho: List[int], zc_rounds: List[List[
     return 0, 0, 0
 
 
+def verify_grand_product(head: List[int], layers, table=None, product=None):
+    """The verifier of a grand product proof (Context.prove_grand_product) on plain integers: what
+    Context.verify_grand_product_batch_device decides on the device.  head: L_2, four values; layers[k - 2] = (rounds, challenges,
+    (a_k, b_k)) of the zero-check of layer k = 2 .. n - 1; table: the 2^n values V, or None (the last claim c_n = V~(z^(n)) is then
+    the caller's to settle); product: the claimed product, or None.  Proof elements are taken as they are: one outside
+    0 .. r - 1 is NON_CANONICAL.  -> (check, layer, round) of the first failure, (0, 0, 0) for an accepted proof:
+      SHAPE          a round vector of layer k, round j, with a length outside 1 .. 4: at (k, j);
+      NON_CANONICAL  a head entry or the claimed product at (0, 0); else the first layer k with a round's coefficients or
+                     challenge at (k, j), or its a_k, b_k at (k, k);
+      PRODUCT        product != head[0] head[1] head[2] head[3]: at (0, 0);
+      per layer k, with zeta_1 = multi_hash(head, 0), zeta_2 = multi_hash([zeta_1], 0), z^(2) = (zeta_1, zeta_2), c_2 = L_2~(z^(2)):
+                     ROUND_SUM then CHALLENGE round by round against c_k at (k, j); FINAL_CLAIM at (k, k) for
+                     g_k(r_k) != eq(z^(k), r^(k)) a_k b_k; then tau_k = multi_hash([a_k, b_k], 0), c_{k+1} = a_k + tau_k (b_k - a_k),
+                     z^(k+1) = (tau_k, r^(k)_1 .. r^(k)_k);
+      EVALUATION     with a table: c_n != V~(z^(n)): at (n, n)."""
+    n = len(layers) + 2
+    if len(head) != 4 or any(len(lay) != 3 or len(lay[0]) != k or len(lay[1]) != k or len(lay[2]) != 2 for k, lay in enumerate(layers, start=2)):
+        raise ValueError("four head values and, for layer k = 2 .., k round vectors, k challenges and two values expected")
+    for k, (rounds, _, _) in enumerate(layers, start=2):
+        for j, g in enumerate(rounds):
+            if not 1 <= len(g) <= 4:
+                return N.GKR_VERIFY_SHAPE, k, j
+    if any(not 0 <= h < P for h in head) or (product is not None and not 0 <= product < P):
+        return N.GKR_VERIFY_NON_CANONICAL, 0, 0
+    for k, (rounds, challenges, ab) in enumerate(layers, start=2):
+        bad = _transcript_form(rounds, challenges, 4, ab)
+        if bad is not None:
+            return bad[1], k, bad[0]
+    if product is not None and product != head[0] * head[1] % P * head[2] % P * head[3] % P:
+        return N.GKR_VERIFY_PRODUCT, 0, 0
+    z = [multi_hash(head, 0)]
+    z.append(multi_hash([z[0]], 0))
+    claim = mle_eval(head, z)
+    for k, (rounds, challenges, (a, b)) in enumerate(layers, start=2):
+        bad, last = _transcript_rounds(rounds, challenges, claim)
+        if bad is not None:
+            return bad[1], k, bad[0]
+        eq_r = 1
+        for zj, rj in zip(z, challenges):
+            eq_r = eq_r * (zj * rj + (1 - zj) * (1 - rj)) % P
+        if last != eq_r * a % P * b % P:
+            return N.GKR_VERIFY_FINAL_CLAIM, k, k
+        tau = multi_hash([a, b], 0)
+        claim = (a + tau * (b - a)) % P
+        z = [tau] + list(challenges)
+    if table is not None and claim != mle_eval(table, z):
+        return N.GKR_VERIFY_EVALUATION, n, n
+    return 0, 0, 0
+
+
 def verify(proof: Proof, circuit: GKRCircuit) -> bool:
     """python/gkr.py:202-231 on the Rust-shaped proof."""
     L = circuit.depth()

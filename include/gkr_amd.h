@@ -536,6 +536,82 @@ int gkr_sumcheck_mle_verify_batch_device(gkr_ctx *ctx, const void *d_tables, int
 int gkr_sumcheck_mle_verify(gkr_ctx *ctx, const gkr_fr *table, int n, const gkr_fr *claim, const gkr_fr *coeffs,
                             const uint32_t *len, const gkr_fr *r, int *accept, uint32_t *failed_round, uint32_t *failed_check);
 
+/* ---- GRAND PRODUCT: P = prod_i V[i] over a resident table, proven as GKR on the binary tree of multiplication gates ----
+ * Permutation, multiset-equality, memory-checking and lookup arguments rest on it.  `batch` independent tables of 2^n canonical
+ * values, table b at d_tables + b * 2^n elements, variable 1 = the most significant index bit; 3 <= n <= GKR_MAX_MLE_N,
+ * batch in 1 .. 65535, batch * 2^n <= 2^30.  The reference has no such argument; the protocol is the library's own:
+ *   tree     L_n = V;  L_k[i] = L_{k+1}[i] * L_{k+1}[i + 2^k] mod r  for k = n-1 .. 0, i < 2^k;  P = L_0[0].  One launch per level
+ *            (csrc/kernels_grand_product.hip) stores every level, canonical, in context workspace; the halves of a level are the
+ *            two contiguous tables the zero-check of the layer below reads in place: nothing is gathered or copied.
+ *   head     the proof opens with L_2 (four values) and P = their product.  zeta_1 = multi_hash(L_2[0..3], key 0),
+ *            zeta_2 = multi_hash([zeta_1], key 0), z^(2) = (zeta_1, zeta_2), c_2 = L_2~(z^(2)).
+ *   layer k  = 2 .. n-1:  gkr_sumcheck_zerocheck_batch_device with n = k on the tables L_{k+1}[0 .. 2^k), L_{k+1}[2^k .. 2^(k+1)),
+ *            the one term {2, {0, 1}} with coefficient 1 and the point z^(k); its claimed sum is c_k.  It yields k round vectors
+ *            in rows of 4 slots, their lengths, the challenges r^(k), the values (a_k, b_k) and eq(z^(k), r^(k)) -- byte for byte
+ *            that call's on that layer.  Then tau_k = multi_hash([a_k, b_k], key 0), c_{k+1} = a_k + tau_k (b_k - a_k),
+ *            z^(k+1) = (tau_k, r^(k)_1 .. r^(k)_k): tau in front, the new variable being the top index bit.
+ *   end      c_n = V~(z^(n)), which the verifier evaluates itself (no commitment to V, as elsewhere in the library).
+ * R = n (n - 1) / 2 - 1 rounds in all, layer k's rows from row k (k - 1) / 2 - 1 on.  Every message is hashed on its own.
+ *   out_products  batch values P                                  out_head    batch x 4 values L_2
+ *   out_coeffs    batch x R rows of 4 slots, layers k = 2 .. n-1   out_len     batch x R values in 1 .. 4
+ *   out_r         batch x R challenges                            out_evals   batch x (n - 2) x 2 values (a_k, b_k), or NULL
+ *   out_point     batch x n coordinates z^(n), or NULL            out_claim   batch values c_n, or NULL
+ * tau, z and c are formed on the host between the layers.  A table with a zero entry has P = 0 and zero levels from some k
+ * down; a zero-check whose g vanishes identically returns every vector as [0] with length 1 (the zero-check's own rule).
+ * Inputs are not modified.  The tree (batch * (2^n - 1) elements) lives in context workspace under slot names of this path's
+ * own; the layers run through the zero-check's driver and share ITS workspace: a zero-check, SOP or product call on the same
+ * context is unaffected.  Hashed on the device by the zero-check's round kernel; the result does not depend on the transcript mode.
+ * GKR_ERR_INVALID before a device or the context is touched (plain returns): NULL ctx or pointer (the three optional outputs
+ * excepted), batch outside 1 .. 65535, n outside 3 .. GKR_MAX_MLE_N, batch * 2^n above 2^30 values. */
+int  gkr_grand_product_batch_device(gkr_ctx *ctx, const void *d_tables, int n, int batch, gkr_fr *out_products, gkr_fr *out_head,
+                                    gkr_fr *out_coeffs, uint32_t *out_len, gkr_fr *out_r, gkr_fr *out_evals /* or NULL */,
+                                    gkr_fr *out_point /* or NULL */, gkr_fr *out_claim /* or NULL */);
+
+/* one table of 2^n values in host memory: upload + the call above with batch 1.  GKR_ERR_NON_CANONICAL (through the context)
+ * for a table entry >= r. */
+int  gkr_grand_product(gkr_ctx *ctx, const gkr_fr *table, int n, gkr_fr *out_product, gkr_fr *out_head, gkr_fr *out_coeffs,
+                       uint32_t *out_len, gkr_fr *out_r, gkr_fr *out_evals, gkr_fr *out_point, gkr_fr *out_claim);
+
+/* Verifier of gkr_grand_product_batch_device's proofs against the resident tables.  head / coeffs / len / r / evals: exactly the
+ * arrays and layout of the prover (evals is required here); products: batch claimed values of P, or NULL (the head's own product
+ * is then what the proof proves; out_products returns it).  The round relations of every layer run on host threads
+ * (csrc/verify_rounds.h, csrc/grand_product_rounds.h), the round vectors' hashes where the sumcheck verifiers' run (on the
+ * device from verify_device_hash_min round vectors on, else on the host threads; zeta and tau always on the host), and V is
+ * read ONCE on the device, at z^(n) (gkr_mle_eval_batch_device's kernels).
+ * accept[batch] required; failed_layer / failed_round / failed_check / out_products (batch each) may be NULL.
+ * Per proof, in this order, the first failure reported (failed_check, at failed_layer, failed_round):
+ *   1. GKR_VERIFY_SHAPE           some len outside 1 .. 4; at (k, j) of the first such row
+ *   2. GKR_VERIFY_NON_CANONICAL   an element >= r (unused slots are never read): a head entry or the claimed product at (0, 0);
+ *                                 else the first layer k with such an element: a used slot or a challenge of row j at (k, j),
+ *                                 else a_k or b_k at (k, k)
+ *   3. GKR_VERIFY_PRODUCT         with products: the claim != head[0] head[1] head[2] head[3]; at (0, 0)
+ *   4. for k = 2 .. n-1, with the running claim c_k:  for j = 0 .. k-1  GKR_VERIFY_ROUND_SUM  g_j(0) + g_j(1) != the running
+ *      claim, GKR_VERIFY_CHALLENGE  r_j != multi_hash(used slots of row j, key 0), at (k, j), in the order of the sumcheck
+ *      verifiers (the challenges of the rounds before the first failed sum first);  then  GKR_VERIFY_FINAL_CLAIM
+ *      g_k(r_k) != eq(z^(k), r^(k)) a_k b_k  at (k, k)
+ *   5. GKR_VERIFY_EVALUATION      c_n != V~(z^(n)); at (n, n)
+ * An accepted proof reports (0, 0, 0).  out_products[b]: the head's product for every proof that passes checks 1 and 2, zero
+ * for the others.  Table entries are read as integers modulo r.  The return value is the status of the CALL, not the verdict;
+ * GKR_ERR_INVALID before a device or the context is touched (plain returns): NULL ctx or required pointer and every shape the
+ * prover refuses.  Verdicts depend neither on verify_workspace_mb nor on verify_device_hash_min. */
+int  gkr_grand_product_verify_batch_device(gkr_ctx *ctx, const void *d_tables, int n, int batch, const gkr_fr *products /* or NULL */,
+                                           const gkr_fr *head, const gkr_fr *coeffs, const uint32_t *len, const gkr_fr *r,
+                                           const gkr_fr *evals, int *accept, uint32_t *failed_layer, uint32_t *failed_round,
+                                           uint32_t *failed_check, gkr_fr *out_products /* or NULL */);
+
+/* one table in host memory: upload + the call above with batch 1.  GKR_ERR_NON_CANONICAL for a table entry >= r. */
+int  gkr_grand_product_verify(gkr_ctx *ctx, const gkr_fr *table, int n, const gkr_fr *product /* or NULL */, const gkr_fr *head,
+                              const gkr_fr *coeffs, const uint32_t *len, const gkr_fr *r, const gkr_fr *evals, int *accept,
+                              uint32_t *failed_layer, uint32_t *failed_round, uint32_t *failed_check);
+
+/* the launch geometry of the tree (host logic, from the function the launches call): one launch per level k = n-1 .. 0,
+ * blocks[k] = its blocks of 256 threads per table, ceil(2^k / 256), a thread per product (k = 0 .. n-1: n words).
+ * GKR_ERR_INVALID: NULL pointer, n outside 3 .. GKR_MAX_MLE_N. */
+int  gkr_selftest_grand_product_geometry(int n, uint32_t *blocks);
+/* The tree alone, into the CALLER's device buffer instead of the context's workspace: d_layers takes batch * (2^n - 1) elements,
+ * level k of table b at batch * (2^k - 1) + b * 2^k.  The argument checks of gkr_grand_product_batch_device. */
+int  gkr_devtest_grand_product_tree(gkr_ctx *ctx, const void *d_tables, int n, int batch, void *d_layers);
+
 /* ---- GKR layer sumcheck: prove_sumcheck_opt, sumcheck.rs:36-44 ----------- */
 /* Layer i has 2^k_i gates; gate g is add (0) or mult (1) of entries left[g],
  * right[g] of layer i+1, which has 2^k_next entries W.  z: k_i challenges.
@@ -837,7 +913,8 @@ enum {
                                       values at r combined as the sumcheck combines them: T~(r), prod_f T_f~(r), sum_k c_k prod_j T_t(k,j)~(r);
                                       gkr_r1cs_verify*: g_n(r_n) != the transcript's own evaluations combined */
     GKR_VERIFY_MATRIX = 11,        /* gkr_r1cs_verify*: e_T != sum_m rho_m M_m~(r_x, r_y) from the public matrices */
-    GKR_VERIFY_WITNESS = 12        /* gkr_r1cs_verify* with a witness: e_w != w~(r_y) */
+    GKR_VERIFY_WITNESS = 12,       /* gkr_r1cs_verify* with a witness: e_w != w~(r_y) */
+    GKR_VERIFY_PRODUCT = 13        /* gkr_grand_product_verify* with claimed products: a claim != the product of the proof's head */
 };
 int  gkr_verify(const gkr_circuit_desc *circuit, const gkr_proof_buf *proof, int threads, int *accept, uint32_t *failed_layer,
                 uint32_t *failed_check);
