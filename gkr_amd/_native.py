@@ -54,7 +54,7 @@ SYMBOLS = [
     "gkr_sumcheck_sop_verify_batch_device", "gkr_sumcheck_sop_verify",
     "gkr_sumcheck_zerocheck_batch_device", "gkr_sumcheck_zerocheck", "gkr_eq_table_device",
     "gkr_grand_product_batch_device", "gkr_grand_product", "gkr_grand_product_verify_batch_device", "gkr_grand_product_verify",
-    "gkr_selftest_grand_product_geometry", "gkr_devtest_grand_product_tree",
+    "gkr_selftest_grand_product_geometry", "gkr_devtest_grand_product_tree", "gkr_devtest_grand_product_chunk",
     "gkr_mle_eval_batch_device", "gkr_sumcheck_mle_verify_batch_device", "gkr_sumcheck_mle_verify",
     "gkr_sumcheck_layer", "gkr_sumcheck_layer_sharded", "gkr_sumcheck_layer_device", "gkr_resident_layer_create", "gkr_resident_layer_sumcheck", "gkr_resident_layer_sumcheck_wdev", "gkr_resident_layer_free", "gkr_exchange_limbs", "gkr_resident_layer_sumcheck_dev", "gkr_exchange_limbs_mle", "gkr_sumcheck_mle_sharded_dev", "gkr_exchange_rccl_unique_id", "gkr_exchange_rccl_create", "gkr_exchange_rccl_dev",
     "gkr_exchange_rccl_calls", "gkr_exchange_rccl_destroy", "gkr_exchange_rccl_error", "gkr_fr_widen", "gkr_fr_narrow", "gkr_predicate_tables", "gkr_layer_eval", "gkr_proof_sizes", "gkr_prove", "gkr_prove_batch",
@@ -210,11 +210,13 @@ def lib():
         L.gkr_grand_product_verify_batch_device.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 11
         L.gkr_grand_product_verify.restype = ctypes.c_int
         L.gkr_grand_product_verify.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 10
-        # (n, blocks[n]); (ctx, tables, n, batch, d_layers)
+        # (n, blocks[n]); (ctx, tables, n, batch, d_layers); (ctx, n, batch, out)
         L.gkr_selftest_grand_product_geometry.restype = ctypes.c_int
         L.gkr_selftest_grand_product_geometry.argtypes = [ctypes.c_int, ctypes.c_void_p]
         L.gkr_devtest_grand_product_tree.restype = ctypes.c_int
         L.gkr_devtest_grand_product_tree.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p]
+        L.gkr_devtest_grand_product_chunk.restype = ctypes.c_int
+        L.gkr_devtest_grand_product_chunk.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 2 + [ctypes.c_void_p]
         # the R1CS zero-check: the CSR form (host only), the resident handle, the rows, the zero-check on them
         L.gkr_r1cs_csr_info.restype = ctypes.c_int
         L.gkr_r1cs_csr_info.argtypes = [ctypes.c_void_p] * 2

@@ -281,4 +281,11 @@ int gkr_devtest_grand_product_tree(gkr_ctx* ctx, const void* d_tables, int n, in
     return GKR_OK;
 }
 
+int gkr_devtest_grand_product_chunk(gkr_ctx* ctx, int n, int batch, uint32_t* out) {
+    if (!ctx || !out || !gp_shape(n, batch)) return GKR_ERR_INVALID;
+    GKR_ENTER(ctx);
+    *out = (uint32_t)chunk_proofs(n, batch);
+    return GKR_OK;
+}
+
 }  // extern "C"

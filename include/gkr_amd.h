@@ -611,6 +611,10 @@ int  gkr_selftest_grand_product_geometry(int n, uint32_t *blocks);
 /* The tree alone, into the CALLER's device buffer instead of the context's workspace: d_layers takes batch * (2^n - 1) elements,
  * level k of table b at batch * (2^k - 1) + b * 2^k.  The argument checks of gkr_grand_product_batch_device. */
 int  gkr_devtest_grand_product_tree(gkr_ctx *ctx, const void *d_tables, int n, int batch, void *d_layers);
+/* The proofs per chunk gkr_grand_product_verify_batch_device works through for (n, batch) under the context's options
+ * (verify_workspace_mb, and mle_eval_mfma_min_n through the evaluation's workspace): *out = min(what fits, 32768, batch), at
+ * least 1; the last chunk takes what is left.  No device work.  The argument checks of gkr_grand_product_verify_batch_device. */
+int  gkr_devtest_grand_product_chunk(gkr_ctx *ctx, int n, int batch, uint32_t *out);
 
 /* ---- GKR layer sumcheck: prove_sumcheck_opt, sumcheck.rs:36-44 ----------- */
 /* Layer i has 2^k_i gates; gate g is add (0) or mult (1) of entries left[g],

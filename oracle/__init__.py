@@ -20,7 +20,10 @@ Contents
                ogkr_r1cs_cols, ogkr_r1cs_matrix_evals: loops over the flat records)
                are pinned by tests/test_oracle_r1cs_c.py to the Python models of
                tests/r1cs_rows_model.py, tests/r1cs_cols_model.py and
-               verifier.r1cs_matrix_evals
+               verifier.r1cs_matrix_evals; its grand product
+               (ogkr_grand_product: a loop of products per level, the explicit
+               zero-check per layer) by tests/test_oracle_grand_product_c.py to
+               tests/grand_product_model.py and both integer verifiers
 
 Pinning status (see DESIGN.md "Oracle"):
   * termlist.py / dense.py are pinned against golden vectors produced by

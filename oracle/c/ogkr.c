@@ -603,6 +603,55 @@ int ogkr_sumcheck_zerocheck(const ogkr_fr *tables, int n, int n_tables, const og
     return 0;
 }
 
+/* The grand product argument (include/gkr_amd.h, gkr_grand_product*; tests/grand_product_model.py restates the rules) from its
+ * parts above: the tree is a loop of ogkr_fr_mul over every level, L_k[i] = L_{k+1}[i] L_{k+1}[i + 2^k]; the head is L_2 with
+ * zeta_1 = multi_hash(L_2), zeta_2 = multi_hash([zeta_1]); layer k = 2 .. n - 1 is ogkr_sumcheck_zerocheck (the EXPLICIT form)
+ * with the one term 1 * T_0 T_1 on the two halves of level k + 1 at z^(k); tau_k = multi_hash([a_k, b_k]),
+ * c_{k+1} = a_k + tau_k (b_k - a_k), z^(k+1) = (tau_k, r^(k)).  The levels are kept in one buffer, level k at 2^k - 1: the
+ * library's layout for one table, so that level k + 1 IS the layer's two tables one after the other. */
+int ogkr_grand_product(const ogkr_fr *table, int n, ogkr_fr *out_product, ogkr_fr *out_head, ogkr_fr *out_coeffs, uint32_t *out_len,
+                       ogkr_fr *out_r, ogkr_fr *out_evals, ogkr_fr *out_point, ogkr_fr *out_claim, ogkr_fr *out_levels, int threads) {
+    if (n < 3 || n > 30 || !table || !out_product || !out_head || !out_coeffs || !out_len || !out_r || !out_evals || !out_point ||
+        !out_claim)
+        return -1;
+    const ogkr_fr zero = {{0, 0, 0, 0}}, one = {{1, 0, 0, 0}};
+    const int nt = set_threads(threads);
+    (void)nt;
+    const size_t size = (size_t)1 << n;
+    ogkr_fr *levels = out_levels ? out_levels : malloc((size - 1) * sizeof(ogkr_fr));
+    if (!levels) return -2;
+    for (int k = n - 1; k >= 0; --k) {
+        const size_t h = (size_t)1 << k;
+        const ogkr_fr *up = k + 1 == n ? table : levels + (2 * h - 1);
+        ogkr_fr *lvl = levels + (h - 1);
+#pragma omp parallel for schedule(static) num_threads(nt)
+        for (size_t i = 0; i < h; ++i) ogkr_fr_mul(&up[i], &up[i + h], &lvl[i]);
+    }
+    *out_product = levels[0];
+    memcpy(out_head, levels + 3, 4 * sizeof(ogkr_fr));
+    ogkr_fr z[31], eq;
+    ogkr_multi_hash(out_head, 4, &zero, &z[0]);
+    ogkr_multi_hash(&z[0], 1, &zero, &z[1]);
+    const ogkr_sop_term term = {2, {0, 1, 0}};
+    int rc = 0;
+    for (int k = 2; k < n && !rc; ++k) {
+        const size_t row = (size_t)k * (size_t)(k - 1) / 2 - 1;
+        const ogkr_fr *up = k + 1 == n ? table : levels + (((size_t)2 << k) - 1);
+        ogkr_fr *ab = out_evals + 2 * (size_t)(k - 2), tau, d;
+        rc = ogkr_sumcheck_zerocheck(up, k, 2, &term, &one, 1, z, out_coeffs + 4 * row, out_len + row, out_r + row, ab, &eq, threads);
+        if (rc) break;
+        ogkr_multi_hash(ab, 2, &zero, &tau);
+        ogkr_fr_sub(&ab[1], &ab[0], &d);
+        ogkr_fr_mul(&tau, &d, &d);
+        ogkr_fr_add(&ab[0], &d, out_claim);
+        z[0] = tau;
+        memcpy(z + 1, out_r + row, (size_t)k * sizeof(ogkr_fr));
+    }
+    if (!rc) memcpy(out_point, z, (size_t)n * sizeof(ogkr_fr));
+    if (!out_levels) free(levels);
+    return rc;
+}
+
 /* ------------------------------------------------------------------ R1CS tables
  * The tables of the R1CS zero-check and inner sumcheck (tests/r1cs_rows_model.py, tests/r1cs_cols_model.py and
  * verifier.r1cs_matrix_evals restate the rules) on the flat records as they stand: counts[3 i + m] records for the combination

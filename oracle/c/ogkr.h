@@ -83,6 +83,18 @@ int ogkr_sumcheck_zerocheck(const ogkr_fr *tables, int n, int n_tables, const og
                             int n_terms, const ogkr_fr *z, ogkr_fr *out_coeffs, uint32_t *out_len, ogkr_fr *out_r,
                             ogkr_fr *out_evals, ogkr_fr *out_eq, int threads);
 
+/* The grand product P = prod_i table[i] of 2^n canonical values as GKR on the binary tree of products (include/gkr_amd.h,
+ * gkr_grand_product*): the C twin of tests/grand_product_model.py.  The tree L_k[i] = L_{k+1}[i] L_{k+1}[i + 2^k] is a loop of
+ * ogkr_fr_mul; the head is L_2, z^(2) = (multi_hash(L_2), multi_hash([zeta_1])); layer k = 2 .. n - 1 is ogkr_sumcheck_zerocheck
+ * with the one term T_0 T_1 (coefficient 1) on the two halves of level k + 1 at z^(k), then tau_k = multi_hash([a_k, b_k]),
+ * c_{k+1} = a_k + tau_k (b_k - a_k), z^(k+1) = (tau_k, r^(k)).  With R = n (n - 1) / 2 - 1 and layer k's rows from
+ * k (k - 1) / 2 - 1 on: out_head 4, out_coeffs R rows of 4 slots (right-aligned, highest degree first, unused slots zero),
+ * out_len R, out_r R, out_evals (n - 2) x 2 the (a_k, b_k), out_point n the point z^(n), out_claim c_n.  out_levels, if not
+ * NULL, takes the levels 0 .. n - 1, level k at 2^k - 1 (2^n - 1 elements: the library's layout for one table).
+ * -1: n < 3, n > 30 or a NULL pointer (out_levels apart); -2: no memory. */
+int ogkr_grand_product(const ogkr_fr *table, int n, ogkr_fr *out_product, ogkr_fr *out_head, ogkr_fr *out_coeffs, uint32_t *out_len,
+                       ogkr_fr *out_r, ogkr_fr *out_evals, ogkr_fr *out_point, ogkr_fr *out_claim, ogkr_fr *out_levels, int threads);
+
 /* The tables of the R1CS zero-check and inner sumcheck on the flat form of an R1CS: counts[3 * n_constraints] (the records of A,
  * B, C per constraint), wires[] and canonical coeffs[], one record after the other -- the C twins of tests/r1cs_rows_model.rows,
  * tests/r1cs_cols_model.cols_table and verifier.r1cs_matrix_evals, as loops over the records as they stand.  A zero coefficient

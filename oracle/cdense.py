@@ -209,6 +209,24 @@ def sumcheck_zerocheck_raw(tables_limbs, n, n_tables, terms, z_limbs, threads=0)
     return C, L, R, E, Q
 
 
+def grand_product_raw(table_limbs, n, threads=0, levels=False):
+    """ogkr_grand_product on one table of 2^n entries ((2^n, 4) limbs) -> (P (4,), H (4, 4), C (R, 4, 4) right-aligned, L (R,) uint32,
+    R (R, 4), E (n - 2, 2, 4), Z (n, 4), K (4,)) with R = n (n - 1) / 2 - 1: one proof's slice of the eight arrays
+    gkr_grand_product_batch_device returns.  levels=True: a ninth array (2^n - 1, 4), level k of the tree at 2^k - 1."""
+    table_limbs = np.ascontiguousarray(table_limbs, dtype=np.uint64)
+    rounds = n * (n - 1) // 2 - 1 if n >= 3 else 0
+    good = 3 <= n <= 30 and table_limbs.size == 4 << n
+    out = [np.zeros(s, dtype=np.uint64) for s in ((4,), (4, 4), (rounds, 4, 4))] + [np.zeros(rounds, dtype=np.uint32)]
+    out += [np.zeros(s, dtype=np.uint64) for s in ((rounds, 4), (max(n - 2, 0), 2, 4), (max(n, 0), 4), (4,))]
+    lv = np.zeros(((1 << n) - 1, 4), dtype=np.uint64) if levels and good else None
+    fn = lib().ogkr_grand_product
+    fn.restype = ctypes.c_int
+    rc = fn(_p(table_limbs) if good else None, ctypes.c_int(n), *[_p(a) for a in out], _p(lv) if lv is not None else None, _threads(threads))
+    if rc:
+        raise ValueError("ogkr_grand_product rc=%d" % rc)
+    return tuple(out) + ((lv,) if levels else ())
+
+
 def _r1cs_flat(counts, wires, coeffs):
     """The flat form of an R1CS (what gkr_r1cs_export writes): counts (3 * n_constraints,) uint32, wires (records,) uint32, coeffs
     (records, 4) uint64, checked against each other -> (n_constraints, counts, wires, coeffs)."""

@@ -27,7 +27,7 @@ from zerocheck_model import zerocheck_claim
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["gkr_grand_product_batch_device", "gkr_grand_product", "gkr_grand_product_verify_batch_device", "gkr_grand_product_verify",
-         "gkr_selftest_grand_product_geometry", "gkr_devtest_grand_product_tree"]
+         "gkr_selftest_grand_product_geometry", "gkr_devtest_grand_product_tree", "gkr_devtest_grand_product_chunk"]
 SIZES = (3, 4, 5, 6)
 
 
@@ -99,6 +99,11 @@ def test_bad_arguments_are_invalid_before_a_device_is_touched():
     for args in ([None, fake, 3, 1, fake], [fake, None, 3, 1, fake], [fake, fake, 3, 1, None], [fake, fake, 2, 1, fake], [fake, fake, 3, 0, fake],
                  [fake, fake, 31, 1, fake], [fake, fake, 3, 65536, fake]):
         assert lib.gkr_devtest_grand_product_tree(*args) == INVALID, args[2:4]
+    # ctx, n, batch, out: the verifier's shapes
+    for args in ([None, 3, 1, fake], [fake, 3, 1, None]) + tuple([fake, n, batch, fake] for n, batch in
+                                                              ((2, 1), (0, 1), (-1, 1), (31, 1), (3, 0), (3, -1), (3, 65536), (30, 2), (20, 2048))):
+        assert lib.gkr_devtest_grand_product_chunk(*args) == INVALID, args[1:3]
+    assert word[0] == 0                                            # nothing was written
 
 
 def tree_geometry(n):
