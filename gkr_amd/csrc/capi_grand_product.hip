@@ -4,17 +4,14 @@
 // of this path's own -- chained by Fiat-Shamir on the host (grand_product_rounds.h); and the verifier of such proofs, whose round
 // relations are verify_rounds.h's and whose one read of V is kernels_mle_eval.hip's.  C ABI: include/gkr_amd.h.
 //
-// The verifier, per chunk of proofs (as many as fit verify_workspace_mb), in the manner of capi_r1cs_verify.hip:
-//   1. the chunk's round vectors start hashing: on the device (the side stream) from verify_device_hash_min of them on, else on
-//      the host threads in step 4;
-//   2. the host threads run the shape and canonical checks of the whole proof, zeta, every tau_k, c_k and z^(k), and the layers'
-//      round sums and Horner steps;
-//   3. the points z^(n) of the proofs that passed SHAPE and NON_CANONICAL go up -- zeros for the others, whose verdict is
-//      decided -- and the one evaluation of every table is launched;
-//   4. the host hashes (if any) run while the device works; ONE synchronisation; then per proof the first failure in order.
-#include <atomic>
-
-#include "capi_internal.h"
+// The verifier builds a chunk of proofs from verify_chunk.h's pieces, which states the plan.  Particular to this file:
+//   - one set of round vectors, rows of four slots, all layers of a proof next to each other;
+//   - the host's relations (the shape and canonical checks of the whole proof, zeta, every tau_k, c_k and z^(k), the layers' round
+//     sums and Horner steps: grand_product_rounds.h) run BEFORE the device's share is queued, because the points z^(n) come out
+//     of them: those of the proofs that passed SHAPE and NON_CANONICAL go up, zeros for the others, whose verdict is decided.
+//     The host's hashes (if any) run after it is queued, while the device works;
+//   - the device's share is the one evaluation of every table; per proof the first failure in order.
+#include "verify_chunk.h"
 #include "grand_product_rounds.h"
 
 namespace {
@@ -23,7 +20,7 @@ using gkr::h64::F;
 namespace V = gkr::verify;
 namespace GP = gkr::gp;
 
-constexpr int kRelPiece = 4, kHashPiece = 16;   // proofs / round vectors per piece of host work
+constexpr size_t kRelPiece = 4;   // proofs per piece of host work
 
 // the shapes both the prover and the verifier admit (plain returns: decided before the context is looked at)
 bool gp_shape(int n, int batch) {
@@ -102,101 +99,35 @@ struct Proofs {
 
 // proofs of a chunk: what fits verify_workspace_mb (the evaluation's workspace, the point, the value; with hashes the rows and slots)
 size_t chunk_proofs(int n, int batch) {
-    long long mb = gkr::opt(gkr::OPT_verify_workspace_mb);
-    if (mb <= 0) mb = 2048;
     const size_t one = gkr::mle_eval_ws_bytes((uint32_t)n, 1, 1) + ((size_t)n + 1) * sizeof(Fr) +
                        GP::rounds(n) * (4 * sizeof(Fr) + sizeof(uint32_t) + sizeof(gkr::VerifyHashSlot));
-    const size_t chunk = ((size_t)mb << 20) / one;
-    return std::max<size_t>(1, std::min<size_t>({chunk, (size_t)32768, (size_t)batch}));   // (the table is a grid dimension of the launches)
+    return verify_chunk_size(one, 32768, batch);   // (the table is a grid dimension of the launches)
 }
 
 int verify_chunk(gkr_ctx* ctx, const Fr* d_tables, int n, uint32_t nb, const Proofs& t, int* accept, uint32_t* failed_layer, uint32_t* failed_round,
                  uint32_t* failed_check, gkr_fr* out_products) {
-    hipStream_t st = ctx->stream;
-    const size_t R = GP::rounds(n), n_rows = (size_t)nb * R;
-    const bool dev_hash = verify_device_hash_wanted(n_rows);
-    // the side stream's work is joined on every way out: nothing may still read or write a workspace the next call reuses
-    struct SideJoin {
-        hipStream_t forked = nullptr;
-        ~SideJoin() {
-            if (forked) (void)hipStreamSynchronize(forked);
-        }
-    } side;
+    const size_t R = GP::rounds(n);
     // ---- 1. the round vectors' hashes on the side stream: rows of four slots
-    std::vector<V::HashSlot> host_slots(dev_hash ? 0 : n_rows);
-    const V::HashSlot* slots = host_slots.data();
-    if (dev_hash) {
-        const size_t words = n_rows * 33;   // rows, then lengths
-        uint32_t *d_hin = nullptr, *h_hin = nullptr;
-        gkr::VerifyHashSlot *d_hout = nullptr, *h_hout = nullptr;
-        WS(ctx, "gp.ver.hash_in", uint32_t, words, d_hin);
-        WS(ctx, "gp.ver.hash_out", gkr::VerifyHashSlot, n_rows, d_hout);
-        HIP_TRY(ctx, ctx->pinned_host("gp.ver.hash_in", words * sizeof(uint32_t), reinterpret_cast<void**>(&h_hin)));
-        HIP_TRY(ctx, ctx->pinned_host("gp.ver.hash_out", n_rows * sizeof(gkr::VerifyHashSlot), reinterpret_cast<void**>(&h_hout)));
-        memcpy(h_hin, t.coeffs, n_rows * 32 * sizeof(uint32_t));
-        memcpy(h_hin + n_rows * 32, t.len, n_rows * sizeof(uint32_t));
-        HIP_TRY(ctx, ctx->aux_stream(2));
-        HIP_TRY(ctx, hipEventRecord(ctx->aux_events[0], st));             // fork: after whatever the main stream still holds
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux, ctx->aux_events[0], 0));
-        side.forked = ctx->aux;
-        HIP_TRY(ctx, hipMemcpyAsync(d_hin, h_hin, words * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->aux));
-        if (const int rc = verify_hash_rows_device(ctx, 4, d_hin, d_hin + n_rows * 32, n_rows, d_hout, ctx->aux)) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(h_hout, d_hout, n_rows * sizeof(gkr::VerifyHashSlot), hipMemcpyDeviceToHost, ctx->aux));
-        HIP_TRY(ctx, hipEventRecord(ctx->aux_events[1], ctx->aux));
-        slots = reinterpret_cast<const V::HashSlot*>(h_hout);
-    }
+    RoundHashes hashes(ctx, "gp.ver.", {RowSet{4u, (size_t)nb * R, {{t.coeffs, t.len}}}});
+    if (const int rc = hashes.start()) return rc;
     // ---- 2. what needs neither a round vector's hash nor V: the form, the chain of claims and points, the layers' sums
     std::vector<GP::Pre> pre(nb);
-    {
-        const size_t pieces = (nb + kRelPiece - 1) / kRelPiece;
-        std::atomic<size_t> next{0};
-        const std::function<bool()> work = [&] {
-            const size_t a = next.fetch_add(1, std::memory_order_relaxed);
-            if (a >= pieces) return false;
-            for (size_t b = a * kRelPiece; b < std::min<size_t>(nb, (a + 1) * kRelPiece); ++b) pre[b] = GP::pre_relations(n, t.at(n, b), host_hash);
-            return true;
-        };
-        gkr::SpinPool* pool = pieces >= 8 ? ctx->host_pool() : nullptr;
-        gkr::SpinPool::Session session(pool, &work);
-        while (work()) {
-        }
-    }
+    for_pieces(ctx, (nb + kRelPiece - 1) / kRelPiece, 8, [&](size_t a) {
+        for (size_t b = a * kRelPiece; b < std::min<size_t>(nb, (a + 1) * kRelPiece); ++b) pre[b] = GP::pre_relations(n, t.at(n, b), host_hash);
+    });
     // ---- 3. the device's share: V~(z^(n)) of the proofs still standing, at zero for the others
-    Fr *h_pts = nullptr, *h_out = nullptr, *d_pts = nullptr, *d_out = nullptr;
-    void* d_ws = nullptr;
-    HIP_TRY(ctx, ctx->pinned_host("gp.ver.points", (size_t)nb * n * sizeof(Fr), reinterpret_cast<void**>(&h_pts)));
+    Fr *h_pts = nullptr, *h_out = nullptr;
+    HIP_TRY(ctx, ctx->pinned_host("gp.ver.pts", (size_t)nb * n * sizeof(Fr), reinterpret_cast<void**>(&h_pts)));
     HIP_TRY(ctx, ctx->pinned_host("gp.ver.out", (size_t)nb * sizeof(Fr), reinterpret_cast<void**>(&h_out)));
-    WS(ctx, "gp.ver.points", Fr, (size_t)nb * n, d_pts);
-    WS(ctx, "gp.ver.out", Fr, nb, d_out);
-    HIP_TRY(ctx, ctx->workspace("gp.ver.eval_ws", gkr::mle_eval_ws_bytes((uint32_t)n, nb, 1), &d_ws));
     memset(h_pts, 0, (size_t)nb * n * sizeof(Fr));
     for (uint32_t b = 0; b < nb; ++b)
         if (pre[b].point) memcpy(h_pts + (size_t)b * n, pre[b].z.data() + GP::layer_row(n), (size_t)n * sizeof(Fr));
-    HIP_TRY(ctx, hipMemcpyAsync(d_pts, h_pts, (size_t)nb * n * sizeof(Fr), hipMemcpyHostToDevice, st));
-    {
-        Timed tm(ctx, "mle_eval", (double)nb * 32.0 * (double)((size_t)1 << n));
-        gkr::launch_mle_eval(d_tables, (uint32_t)n, nb, 1u, d_pts, d_ws, d_out, st);
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(h_out, d_out, (size_t)nb * sizeof(Fr), hipMemcpyDeviceToHost, st));
-    if (dev_hash) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->aux_events[1], 0));   // join: the main stream's end is the side stream's too
-    // ---- 4. the host's hashes while the device works, in pieces of kHashPiece round vectors
-    if (!dev_hash) {
-        const size_t pieces = (n_rows + kHashPiece - 1) / kHashPiece;
-        std::atomic<size_t> next{0};
-        const std::function<bool()> work = [&] {
-            const size_t a = next.fetch_add(1, std::memory_order_relaxed);
-            if (a >= pieces) return false;
-            for (size_t s = a * kHashPiece; s < std::min(n_rows, (a + 1) * kHashPiece); ++s) host_hash_slot(t.coeffs + 4 * s, 4u, t.len[s], &host_slots[s]);
-            return true;
-        };
-        gkr::SpinPool* pool = pieces >= 8 ? ctx->host_pool() : nullptr;
-        gkr::SpinPool::Session session(pool, &work);
-        while (work()) {
-        }
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    side.forked = nullptr;
+    if (const int rc = queue_eval(ctx, "gp.ver.", d_tables, n, nb, 1u, h_pts, h_out)) return rc;
+    if (const int rc = hashes.join()) return rc;
+    // ---- 4. the host's hashes (if any) while the device works
+    for_pieces(ctx, hashes.host_pieces(), 8, [&](size_t a) { hashes.hash_piece(a); });
+    if (const int rc = hashes.sync_main()) return rc;
+    const V::HashSlot* slots = hashes.slots();
     ctx->drain_events();
     for (uint32_t b = 0; b < nb; ++b) {
         GP::Verdict v;
@@ -243,16 +174,13 @@ int gkr_grand_product_verify_batch_device(gkr_ctx* ctx, const void* d_tables, in
     if (!ctx || !d_tables || !head || !coeffs || !len || !r || !evals || !accept) return GKR_ERR_INVALID;
     if (!gp_shape(n, batch)) return GKR_ERR_INVALID;
     GKR_ENTER(ctx);
-    const size_t chunk = chunk_proofs(n, batch), R = GP::rounds(n);
-    for (size_t b = 0; b < (size_t)batch; b += chunk) {
-        const uint32_t nb = (uint32_t)std::min(chunk, (size_t)batch - b);
+    const size_t R = GP::rounds(n);
+    return for_chunks(batch, chunk_proofs(n, batch), [&](size_t b, uint32_t nb) {
         const Proofs t{products ? products + b : nullptr, head + 4 * b, coeffs + 4 * b * R, r + b * R, evals + 2 * b * (n - 2), len + b * R};
-        const int rc = verify_chunk(ctx, static_cast<const Fr*>(d_tables) + (b << n), n, nb, t, accept + b, failed_layer ? failed_layer + b : nullptr,
-                                    failed_round ? failed_round + b : nullptr, failed_check ? failed_check + b : nullptr,
-                                    out_products ? out_products + b : nullptr);
-        if (rc) return rc;
-    }
-    return GKR_OK;
+        return verify_chunk(ctx, static_cast<const Fr*>(d_tables) + (b << n), n, nb, t, accept + b, failed_layer ? failed_layer + b : nullptr,
+                            failed_round ? failed_round + b : nullptr, failed_check ? failed_check + b : nullptr,
+                            out_products ? out_products + b : nullptr);
+    });
 }
 
 int gkr_grand_product_verify(gkr_ctx* ctx, const gkr_fr* table, int n, const gkr_fr* product, const gkr_fr* head, const gkr_fr* coeffs,

@@ -4,9 +4,10 @@
 // its dense form; capi_prove.hip: whole proofs; capi_product.hip: the sumcheck over a product of resident tables; capi_sop.hip: over a sum of
 // such products; capi_zerocheck.hip: the zero-check -- the entry points and shape checks of the three, whose one driver is
 // capi_resident.hip; capi_r1cs.hip: an R1CS's tables in front of it; capi_r1cs_verify.hip: the verifier of that pair of
-// sumchecks; capi_grand_product.hip: the grand product, a product tree and a zero-check per layer, and its verifier): the context,
-// its caches and workspaces, profiling brackets, the host transcript's helpers, the hand-off wait, the plain sumcheck's group
-// hand-off.  Not a public header.
+// sumchecks; capi_grand_product.hip: the grand product, a product tree and a zero-check per layer, and its verifier; capi_verify.hip
+// and capi_mle_verify.hip: the verifiers of whole proofs and of the sumchecks over resident tables; verify_chunk.h: the pieces the
+// four files with a batch verifier build a chunk from): the context, its caches and workspaces, profiling brackets, the host
+// transcript's helpers, the hand-off wait, the plain sumcheck's group hand-off.  Not a public header.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <sched.h>
@@ -633,6 +634,21 @@ constexpr int kMleShardTailLog2 = 6;   // entries (log2) every shard keeps for t
 #define WS(ctx, slot, type, count, ptr) \
     HIP_TRY(ctx, (ctx)->workspace(slot, (size_t)(count) * sizeof(type), reinterpret_cast<void**>(&(ptr))))
 
+// the status of a failed device allocation: GKR_ERR_NOMEM where the device is out of memory, as include/gkr_amd.h documents
+inline int alloc_status(gkr_ctx* ctx, hipError_t e, const char* what) {
+    if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError();
+        return ctx->fail(GKR_ERR_NOMEM, std::string(what) + ": out of device memory");
+    }
+    return ctx->hip_fail(e, what);
+}
+// WS with that status (the verifiers' workspaces, which grow with the caller's batch); slot: a C string
+#define WS_OR_NOMEM(ctx, slot, type, count, ptr)                                                                      \
+    do {                                                                                                              \
+        const hipError_t _e = (ctx)->workspace(slot, (size_t)(count) * sizeof(type), reinterpret_cast<void**>(&(ptr))); \
+        if (_e != hipSuccess) return alloc_status(ctx, _e, slot);                                                     \
+    } while (0)
+
 // Rounds the sub-block sums of a table of 2^m entries cover (= variables the next fold pass binds) in a sumcheck over
 // 2^n points with at most jmax rounds per pass.  A fold pass over more than kSmallPassEntries outputs splits each
 // sub-block over whole 64-entry chunks (so at most m - 6 rounds from its sums); and a fold should not leave 1024 or
@@ -787,12 +803,8 @@ int upload_gates(gkr_ctx* ctx, size_t gates, const uint8_t* gt, const uint32_t* 
 // run_layer_batch's other form, for the device transcript: over dense predicate tables, the proofs of a batch one after the other
 int run_layer_dense(gkr_ctx* ctx, int batch, int k_i, int k, const uint8_t* d_gt, const uint32_t* d_l, const uint32_t* d_r, const gkr_fr* z,
                     const Fr* d_W, gkr_fr* const* out_coeffs, uint32_t* const* out_len, gkr_fr* const* out_r);
-// ---- defined in capi_verify.hip
-// does a chunk of `rows` round vectors hash on the device (option verify_device_hash_min)?  and THE launcher of the hash kernel:
-// n rows of `slots` (3 or 4) right-aligned slots and their lengths, in device memory -> their slots in device memory, on stream s
-bool verify_device_hash_wanted(size_t rows);
-int verify_hash_rows_device(gkr_ctx* ctx, int slots, const uint32_t* d_rows, const uint32_t* d_len, size_t n, gkr::VerifyHashSlot* d_slots, hipStream_t s);
-// the same slot of one round vector on the calling thread: verify_rounds.h's rule with the host transcript's hash
+// the hash slot of one round vector on the calling thread: verify_rounds.h's rule with the host transcript's hash (the device's
+// side of the same slots: verify_chunk.h)
 inline void host_hash_slot(const gkr_fr* row, uint32_t width, uint32_t len, gkr::verify::HashSlot* slot) {
     gkr::verify::hash_slot(row, width, len, slot, [](const gkr::h64::F* v, int n) { return host_multi_hash(v, n, host_mimc_constants64()); });
 }

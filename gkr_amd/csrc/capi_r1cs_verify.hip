@@ -5,18 +5,17 @@
 //
 // A verifier holds no table: the last relation of either transcript is a value formed on the host (eq(z, r_x) (v_A v_B - v_C);
 // e_T e_w), and what ties the claims to the R1CS is e_T = sum_m rho_m M_m~(r_x, r_y), the device's share.  The round relations are
-// the sumcheck verifiers' own (verify_rounds.h).  Per chunk of proofs (as many as fit verify_workspace_mb):
-//   1. the chunk's round vectors -- rows of four slots of the zero-check, of three of the inner sumcheck -- start hashing: on the
-//      device (the side stream) from verify_device_hash_min of them on, else on the host threads in step 4;
-//   2. the host threads run shape, canonical checks, round sums and Horner steps of both transcripts (the inner one's claim is
-//      sum_m rho_m v_m, so it follows the zero-check's canonical checks);
-//   3. the points (r_x, r_y) of the proofs that passed SHAPE and NON_CANONICAL go up -- zeros for the others, whose verdict is
-//      decided -- and the eq tables, the matrix pass and, with a witness, its padded copy and its evaluation are launched;
-//   4. the host hashes (if any) run while the device works; ONE synchronisation; then per proof the first failure in the order of
-//      the stages.
-#include <atomic>
-
-#include "capi_internal.h"
+// the sumcheck verifiers' own (verify_rounds.h).  A chunk of proofs is built from verify_chunk.h's pieces, which states the plan.
+// Particular to this file:
+//   - two sets of round vectors, the zero-check's rows of four slots and the inner sumcheck's of three: two hash launches;
+//   - the host's relations (shape, canonical checks, round sums and Horner steps of both transcripts; the inner one's claim is
+//     sum_m rho_m v_m, so it follows the zero-check's canonical checks) run BEFORE the device's share is queued: only the points
+//     (r_x, r_y) of the proofs that passed SHAPE and NON_CANONICAL go up, zeros for the others, whose verdict is decided.  The
+//     host's hashes (if any) run after it is queued, while the device works;
+//   - the device's share: the eq tables, the matrix pass and, with a witness, its padded copy and its evaluation (whose points are
+//     on the device already);
+//   - per proof the first failure in the order of the stages.
+#include "verify_chunk.h"
 
 namespace {
 
@@ -26,7 +25,7 @@ using V::HashSlot;
 using V::Pre;
 
 constexpr uint32_t kEqMaxVars = 28;   // launch_eq_table's limit
-constexpr int kRelPiece = 8, kHashPiece = 16;   // proofs / round vectors per piece of host work
+constexpr size_t kRelPiece = 8;       // proofs per piece of host work
 
 // the CSC info's rule for the columns' variables, from the rows handle's n_wires
 uint32_t n_y_of(uint32_t n_wires) {
@@ -49,15 +48,12 @@ bool matrix_args(const gkr_ctx* ctx, const gkr_r1cs_rows* rows, int batch) {
 // proofs of a chunk: what fits verify_workspace_mb (the eq tables, the partials, the points; with a witness its padded copy and
 // the evaluation's workspace; with hashes both transcripts' rows and slots)
 size_t chunk_proofs(const gkr_r1cs_rows* rows, int batch, bool witness, bool hashes) {
-    long long mb = gkr::opt(gkr::OPT_verify_workspace_mb);
-    if (mb <= 0) mb = 2048;
     const uint32_t n = rows->info.n, n_y = n_y_of(rows->info.n_wires);
     size_t one = sizeof(Fr) * (((size_t)1 << n) + ((size_t)1 << n_y) + 3 * (size_t)gkr::r1cs_matrix_eval_slots(rows->csr()) + n + n_y + 3);
     if (witness) one += sizeof(Fr) * (((size_t)1 << n_y) + 1) + gkr::mle_eval_ws_bytes(n_y, 1, 1);
     if (hashes) one += (size_t)n * (4 * sizeof(Fr) + sizeof(uint32_t) + sizeof(gkr::VerifyHashSlot)) +
                        (size_t)n_y * (3 * sizeof(Fr) + sizeof(uint32_t) + sizeof(gkr::VerifyHashSlot));
-    const size_t chunk = ((size_t)mb << 20) / one;
-    return std::max<size_t>(1, std::min<size_t>({chunk, (size_t)32768, (size_t)batch}));   // (the proof is a grid dimension of the launches)
+    return verify_chunk_size(one, 32768, batch);   // (the proof is a grid dimension of the launches)
 }
 
 // The device side of `nb` proofs, queued on the main stream: h_pts (pinned: nb x n coordinates x_b, then nb x n_y coordinates
@@ -68,11 +64,11 @@ int queue_matrix_evals(gkr_ctx* ctx, const gkr_r1cs_rows* rows, uint32_t nb, con
     const gkr::R1csCsr csr = rows->csr();
     const size_t n_pts = (size_t)nb * (n + n_y), slots = gkr::r1cs_matrix_eval_slots(csr);
     Fr *d_pts = nullptr, *d_ex = nullptr, *d_ey = nullptr, *d_part = nullptr, *d_out = nullptr;
-    WS(ctx, "r1cs.mat.points", Fr, n_pts, d_pts);
-    WS(ctx, "r1cs.mat.ex", Fr, (size_t)nb << n, d_ex);
-    WS(ctx, "r1cs.mat.ey", Fr, (size_t)nb << n_y, d_ey);
-    WS(ctx, "r1cs.mat.partials", Fr, (size_t)nb * 3 * slots, d_part);
-    WS(ctx, "r1cs.mat.out", Fr, (size_t)nb * 3, d_out);
+    WS_OR_NOMEM(ctx, "r1cs.mat.points", Fr, n_pts, d_pts);
+    WS_OR_NOMEM(ctx, "r1cs.mat.ex", Fr, (size_t)nb << n, d_ex);
+    WS_OR_NOMEM(ctx, "r1cs.mat.ey", Fr, (size_t)nb << n_y, d_ey);
+    WS_OR_NOMEM(ctx, "r1cs.mat.partials", Fr, (size_t)nb * 3 * slots, d_part);
+    WS_OR_NOMEM(ctx, "r1cs.mat.out", Fr, (size_t)nb * 3, d_out);
     HIP_TRY(ctx, hipMemcpyAsync(d_pts, h_pts, n_pts * sizeof(Fr), hipMemcpyHostToDevice, s));
     {
         Timed t(ctx, "r1cs_mat_eq", (double)nb * 32.0 * (double)(((size_t)1 << n) + ((size_t)1 << n_y)));
@@ -206,57 +202,14 @@ int verify_chunk(gkr_ctx* ctx, const gkr_r1cs_rows* rows, uint32_t nb, const Tra
     hipStream_t st = ctx->stream;
     const int n = (int)rows->info.n, n_y = (int)n_y_of(rows->info.n_wires);
     const size_t rows_x = (size_t)nb * n, rows_y = (size_t)nb * n_y, n_rows = rows_x + rows_y;
-    const bool dev_hash = verify_device_hash_wanted(n_rows);
-    // the side stream's work is joined on every way out: nothing may still read or write a workspace the next call reuses
-    struct SideJoin {
-        hipStream_t forked = nullptr;
-        ~SideJoin() {
-            if (forked) (void)hipStreamSynchronize(forked);
-        }
-    } side;
     // ---- 1. the hashes on the side stream: the zero-check's rows of four slots, then the inner sumcheck's of three
-    std::vector<HashSlot> host_slots(dev_hash ? 0 : n_rows);
-    const HashSlot* slots = host_slots.data();
-    if (dev_hash) {
-        const size_t words_x = rows_x * 32, words_y = rows_y * 24, words = words_x + words_y + n_rows;   // rows, rows, all lengths
-        uint32_t *d_hin = nullptr, *h_hin = nullptr;
-        gkr::VerifyHashSlot *d_hout = nullptr, *h_hout = nullptr;
-        WS(ctx, "r1cs.ver.hash_in", uint32_t, words, d_hin);
-        WS(ctx, "r1cs.ver.hash_out", gkr::VerifyHashSlot, n_rows, d_hout);
-        HIP_TRY(ctx, ctx->pinned_host("r1cs.ver.hash_in", words * sizeof(uint32_t), reinterpret_cast<void**>(&h_hin)));
-        HIP_TRY(ctx, ctx->pinned_host("r1cs.ver.hash_out", n_rows * sizeof(gkr::VerifyHashSlot), reinterpret_cast<void**>(&h_hout)));
-        memcpy(h_hin, t.coeffs_x, words_x * sizeof(uint32_t));
-        memcpy(h_hin + words_x, t.coeffs_y, words_y * sizeof(uint32_t));
-        memcpy(h_hin + words_x + words_y, t.len_x, rows_x * sizeof(uint32_t));
-        memcpy(h_hin + words_x + words_y + rows_x, t.len_y, rows_y * sizeof(uint32_t));
-        HIP_TRY(ctx, ctx->aux_stream(2));
-        HIP_TRY(ctx, hipEventRecord(ctx->aux_events[0], st));             // fork: after whatever the main stream still holds
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux, ctx->aux_events[0], 0));
-        side.forked = ctx->aux;
-        HIP_TRY(ctx, hipMemcpyAsync(d_hin, h_hin, words * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->aux));
-        const uint32_t* d_len = d_hin + words_x + words_y;
-        if (const int rc = verify_hash_rows_device(ctx, 4, d_hin, d_len, rows_x, d_hout, ctx->aux)) return rc;
-        if (const int rc = verify_hash_rows_device(ctx, 3, d_hin + words_x, d_len + rows_x, rows_y, d_hout + rows_x, ctx->aux)) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(h_hout, d_hout, n_rows * sizeof(gkr::VerifyHashSlot), hipMemcpyDeviceToHost, ctx->aux));
-        HIP_TRY(ctx, hipEventRecord(ctx->aux_events[1], ctx->aux));
-        slots = reinterpret_cast<const HashSlot*>(h_hout);
-    }
+    RoundHashes hashes(ctx, "r1cs.ver.", {RowSet{4u, rows_x, {{t.coeffs_x, t.len_x}}}, RowSet{3u, rows_y, {{t.coeffs_y, t.len_y}}}});
+    if (const int rc = hashes.start()) return rc;
     // ---- 2. the relations that need neither a hash nor a device value, in pieces of kRelPiece proofs
     std::vector<ProofPre> pre(nb);
-    {
-        const size_t pieces = (nb + kRelPiece - 1) / kRelPiece;
-        std::atomic<size_t> next{0};
-        const std::function<bool()> work = [&] {
-            const size_t a = next.fetch_add(1, std::memory_order_relaxed);
-            if (a >= pieces) return false;
-            for (size_t b = a * kRelPiece; b < std::min<size_t>(nb, (a + 1) * kRelPiece); ++b) pre[b] = proof_pre(n, n_y, t, b);
-            return true;
-        };
-        gkr::SpinPool* pool = pieces >= 8 ? ctx->host_pool() : nullptr;
-        gkr::SpinPool::Session session(pool, &work);
-        while (work()) {
-        }
-    }
+    for_pieces(ctx, (nb + kRelPiece - 1) / kRelPiece, 8, [&](size_t a) {
+        for (size_t b = a * kRelPiece; b < std::min<size_t>(nb, (a + 1) * kRelPiece); ++b) pre[b] = proof_pre(n, n_y, t, b);
+    });
     // ---- 3. the device's share: the points of the proofs still standing, zeros for the others
     Fr *h_pts = nullptr, *h_out = nullptr;
     HIP_TRY(ctx, ctx->pinned_host("r1cs.mat.points", n_rows * sizeof(Fr), reinterpret_cast<void**>(&h_pts)));
@@ -273,10 +226,10 @@ int verify_chunk(gkr_ctx* ctx, const gkr_r1cs_rows* rows, uint32_t nb, const Tra
     if (d_witness) {   // stage 4's value: the witness zero-padded to 2^n_y, evaluated at r_y
         const size_t len = (size_t)1 << n_y;
         Fr *d_pad = nullptr, *d_w = nullptr;
-        void* d_ws = nullptr;
-        WS(ctx, "r1cs.ver.witness", Fr, (size_t)nb * len, d_pad);
-        WS(ctx, "r1cs.ver.w_out", Fr, nb, d_w);
-        HIP_TRY(ctx, ctx->workspace("r1cs.ver.eval_ws", gkr::mle_eval_ws_bytes((uint32_t)n_y, nb, 1), &d_ws));
+        unsigned char* d_ws = nullptr;
+        WS_OR_NOMEM(ctx, "r1cs.ver.witness", Fr, (size_t)nb * len, d_pad);
+        WS_OR_NOMEM(ctx, "r1cs.ver.w_out", Fr, nb, d_w);
+        WS_OR_NOMEM(ctx, "r1cs.ver.eval_ws", unsigned char, gkr::mle_eval_ws_bytes((uint32_t)n_y, nb, 1), d_ws);
         gkr::launch_r1cs_pad_witness(d_witness, stride, rows->info.n_wires, (uint32_t)n_y, nb, d_pad, len, st);
         {
             Timed tm(ctx, "mle_eval", (double)nb * 32.0 * (double)len);
@@ -286,29 +239,11 @@ int verify_chunk(gkr_ctx* ctx, const gkr_r1cs_rows* rows, uint32_t nb, const Tra
         h_w = h_out + (size_t)nb * 3;
         HIP_TRY(ctx, hipMemcpyAsync(h_w, d_w, (size_t)nb * sizeof(Fr), hipMemcpyDeviceToHost, st));
     }
-    if (dev_hash) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->aux_events[1], 0));   // join: the main stream's end is the side stream's too
-    // ---- 4. the host's hashes while the device works, in pieces of kHashPiece round vectors
-    if (!dev_hash) {
-        const size_t pieces = (n_rows + kHashPiece - 1) / kHashPiece;
-        std::atomic<size_t> next{0};
-        const std::function<bool()> work = [&] {
-            const size_t a = next.fetch_add(1, std::memory_order_relaxed);
-            if (a >= pieces) return false;
-            for (size_t s = a * kHashPiece; s < std::min(n_rows, (a + 1) * kHashPiece); ++s) {
-                if (s < rows_x)
-                    host_hash_slot(t.coeffs_x + 4 * s, 4u, t.len_x[s], &host_slots[s]);
-                else
-                    host_hash_slot(t.coeffs_y + 3 * (s - rows_x), 3u, t.len_y[s - rows_x], &host_slots[s]);
-            }
-            return true;
-        };
-        gkr::SpinPool* pool = pieces >= 8 ? ctx->host_pool() : nullptr;
-        gkr::SpinPool::Session session(pool, &work);
-        while (work()) {
-        }
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    side.forked = nullptr;
+    if (const int rc = hashes.join()) return rc;
+    // ---- 4. the host's hashes (if any) while the device works
+    for_pieces(ctx, hashes.host_pieces(), 8, [&](size_t a) { hashes.hash_piece(a); });
+    if (const int rc = hashes.sync_main()) return rc;
+    const HashSlot* slots = hashes.slots();
     ctx->drain_events();
     for (uint32_t b = 0; b < nb; ++b) {
         Verdict v;
@@ -333,9 +268,7 @@ int gkr_r1cs_matrix_evals_device(gkr_ctx* ctx, const gkr_r1cs_rows* rows, const 
     if (!all_canonical(x, (size_t)batch * n)) return ctx->fail(GKR_ERR_NON_CANONICAL, "x entry >= r");
     if (!all_canonical(y, (size_t)batch * n_y)) return ctx->fail(GKR_ERR_NON_CANONICAL, "y entry >= r");
     GKR_ENTER(ctx);
-    const size_t chunk = chunk_proofs(rows, batch, false, false);
-    for (size_t b = 0; b < (size_t)batch; b += chunk) {
-        const uint32_t nb = (uint32_t)std::min(chunk, (size_t)batch - b);
+    return for_chunks(batch, chunk_proofs(rows, batch, false, false), [&](size_t b, uint32_t nb) -> int {
         Fr *h_pts = nullptr, *h_out = nullptr;
         HIP_TRY(ctx, ctx->pinned_host("r1cs.mat.points", (size_t)nb * (n + n_y) * sizeof(Fr), reinterpret_cast<void**>(&h_pts)));
         HIP_TRY(ctx, ctx->pinned_host("r1cs.mat.out", (size_t)nb * 3 * sizeof(Fr), reinterpret_cast<void**>(&h_out)));
@@ -345,8 +278,8 @@ int gkr_r1cs_matrix_evals_device(gkr_ctx* ctx, const gkr_r1cs_rows* rows, const 
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         ctx->drain_events();
         memcpy(out + b * 3, h_out, (size_t)nb * 3 * sizeof(Fr));
-    }
-    return GKR_OK;
+        return GKR_OK;
+    });
 }
 
 int gkr_r1cs_verify_batch_device(gkr_ctx* ctx, const gkr_r1cs_rows* rows, int batch, const gkr_fr* z, const gkr_fr* coeffs_x, const uint32_t* len_x,
@@ -361,9 +294,7 @@ int gkr_r1cs_verify_batch_device(gkr_ctx* ctx, const gkr_r1cs_rows* rows, int ba
     if (!all_canonical(z, (size_t)batch * n)) return ctx->fail(GKR_ERR_NON_CANONICAL, "z entry >= r");
     if (!all_canonical(rho, (size_t)batch * 3)) return ctx->fail(GKR_ERR_NON_CANONICAL, "rho entry >= r");
     GKR_ENTER(ctx);
-    const size_t chunk = chunk_proofs(rows, batch, d_witness != nullptr, true);
-    for (size_t b = 0; b < (size_t)batch; b += chunk) {
-        const uint32_t nb = (uint32_t)std::min(chunk, (size_t)batch - b);
+    return for_chunks(batch, chunk_proofs(rows, batch, d_witness != nullptr, true), [&](size_t b, uint32_t nb) {
         Transcripts t;
         t.z = z + b * n;
         t.coeffs_x = coeffs_x + 4 * b * n;
@@ -375,12 +306,10 @@ int gkr_r1cs_verify_batch_device(gkr_ctx* ctx, const gkr_r1cs_rows* rows, int ba
         t.len_y = len_y + b * n_y;
         t.r_y = r_y + b * n_y;
         t.evals_tw = evals_tw + 2 * b;
-        const int rc = verify_chunk(ctx, rows, nb, t, d_witness ? static_cast<const Fr*>(d_witness) + b * stride_elements : nullptr, stride_elements,
-                                    accept + b, failed_stage ? failed_stage + b : nullptr, failed_round ? failed_round + b : nullptr,
-                                    failed_check ? failed_check + b : nullptr);
-        if (rc) return rc;
-    }
-    return GKR_OK;
+        return verify_chunk(ctx, rows, nb, t, d_witness ? static_cast<const Fr*>(d_witness) + b * stride_elements : nullptr, stride_elements,
+                            accept + b, failed_stage ? failed_stage + b : nullptr, failed_round ? failed_round + b : nullptr,
+                            failed_check ? failed_check + b : nullptr);
+    });
 }
 
 int gkr_r1cs_verify(gkr_ctx* ctx, const gkr_r1cs* r1cs, const gkr_fr* z, const gkr_fr* coeffs_x, const uint32_t* len_x, const gkr_fr* r_x,

@@ -19,15 +19,15 @@
 //      the canonical scans, and the two coefficient-table evaluations; one copy brings every result back;
 //   3. it joins the hashing (the side stream's event, or the host pool), synchronises ONCE, and runs the shared relations per
 //      proof with the device's values.  Verdicts do not depend on where the hashes ran: both sides fill the same HashSlot array
-//      by the same rule (hash_piece below is that rule; the kernel restates it).
+//      by the same rule.
+// The hashing, the chunk size and the host's pieces are verify_chunk.h's, shared with the other batch verifiers; particular to
+// this one: the host's session opens BEFORE the uploads of 2 are queued and is drained after.
 //
 // gkr_mimc7_multi_hash_device is the same kernel through the same launcher for a caller's own rows.
 //
 // Requirement (verify_core.h states it where the order lives): the device computes from proof elements nobody has checked yet,
 // so some of its values may be garbage; the relations consult a value only after the elements behind it passed their own checks.
-#include <atomic>
-
-#include "capi_internal.h"
+#include "verify_chunk.h"
 #include "verify_core.h"
 
 struct gkr_verify_circuit {
@@ -40,19 +40,6 @@ namespace {
 
 using gkr::h64::F;
 namespace V = gkr::verify;
-
-int alloc_status(gkr_ctx* ctx, hipError_t e, const char* what) {
-    if (e == hipErrorOutOfMemory) {
-        (void)hipGetLastError();
-        return ctx->fail(GKR_ERR_NOMEM, std::string(what) + ": out of device memory");
-    }
-    return ctx->hip_fail(e, what);
-}
-#define VERIFY_WS(ctx, slot, type, count, ptr)                                                                        \
-    do {                                                                                                              \
-        const hipError_t _e = (ctx)->workspace(slot, (size_t)(count) * sizeof(type), reinterpret_cast<void**>(&(ptr))); \
-        if (_e != hipSuccess) return alloc_status(ctx, _e, slot);                                                     \
-    } while (0)
 
 void release(gkr_verify_circuit* vc) {
     for (uint2* p : vc->gates)
@@ -67,74 +54,8 @@ int check_circuit_args(const gkr_circuit_desc* circuit) {
     return V::check_k_list(circuit);
 }
 
-// the challenge hashes of a chunk, computed while the device works: slot (proof, row) holds multi_hash of that round vector
-// when the row is well-formed (1 .. 3 canonical coefficients); the relations reject a malformed row before they ask for its hash
-struct HashSlot {
-    gkr_fr h;
-    uint32_t valid;
-};
-static_assert(sizeof(HashSlot) == sizeof(gkr::VerifyHashSlot) && offsetof(HashSlot, valid) == offsetof(gkr::VerifyHashSlot, valid),
-              "the kernel writes the slots the relations read");
-// one piece of 16 slots; false when none is left (safe to call from many threads: the shape of a SpinPool job)
-bool hash_piece(const gkr_proof_buf* proofs, size_t rounds, size_t n, std::atomic<size_t>& next, HashSlot* slots) {
-    const F* cts = host_mimc_constants64();
-    {
-        const size_t a = next.fetch_add(16, std::memory_order_relaxed);
-        if (a >= n) return false;
-        for (size_t s = a; s < std::min(n, a + 16); ++s) {
-            const gkr_proof_buf& p = proofs[s / rounds];
-            const size_t row = s % rounds;
-            const uint32_t len = p.sumcheck_len[row];
-            slots[s].valid = 0;
-            if (len < 1 || len > 3) continue;
-            const gkr_fr* g = p.sumcheck_coeffs + row * 3 + (3 - len);
-            F v[3];
-            bool ok = true;
-            for (uint32_t t = 0; t < len; ++t) {
-                ok = ok && V::canonical(g[t]);
-                v[t] = V::load(g[t]);
-            }
-            if (!ok) continue;
-            const F h = host_multi_hash(v, (int)len, cts);
-            memcpy(slots[s].h.l, h.l, 32);
-            slots[s].valid = 1;
-        }
-    }
-    return true;
-}
-
-// Smallest number of round vectors in a chunk that are hashed on the device when verify_device_hash_min is 0; 0: never.
-// Measured (profiles/r08, tools/bench_verify.py --hash both --sweep: the demo circuit k = [5,6,7,7,7,7], 68 vectors per proof,
-// MI355X, 16 host CPUs, median (interquartile range) of 20 alternating calls, ms):
-//     vectors      68     136     272     544    1088    4352   17408   69632  278528
-//     host      0.305   0.318   0.499   0.761   1.616   4.826  18.411  70.622 285.474
-//     device    0.483   0.489   0.518   0.563   0.630   1.058   2.960  10.478  59.930
-// From 544 vectors on, at every larger point, the device median is below the host median by more than the sum of the two
-// interquartile ranges (at 272: 0.019 ms in favour of the host); rounded up to a power of two.
-constexpr long long kVerifyDeviceHashMinRows = 1024;
-constexpr size_t kHashRowWords = 24, kHashLaunchRows = (size_t)1 << 24;   // (rows per launch: the grid stays far below 2^31 blocks)
-constexpr double kHashRowBytes = 96.0 + 4.0 + 36.0;                       // a row in, its length, hash and valid word out
-
-bool device_hash_wanted(size_t rows) {
-    long long min_rows = gkr::opt(gkr::OPT_verify_device_hash_min);
-    if (min_rows == 0) min_rows = kVerifyDeviceHashMinRows;
-    return min_rows > 0 && rows >= (size_t)min_rows;
-}
-
-// n rows and their lengths, in device memory -> their slots in device memory, on stream s: THE launcher of both entry points
-// (slots: 3, this file's rows, or 4, the degree-3 product sumcheck's)
-int hash_rows_device(gkr_ctx* ctx, int slots, const uint32_t* d_rows, const uint32_t* d_len, size_t n, gkr::VerifyHashSlot* d_slots, hipStream_t s) {
-    const size_t row_words = (size_t)slots * 8;
-    for (size_t a = 0; a < n; a += kHashLaunchRows) {
-        const size_t m = std::min(kHashLaunchRows, n - a);
-        {
-            Timed t(ctx, "verify_hash", (double)m * (kHashRowBytes + 32.0 * (slots - 3)), s);
-            gkr::launch_verify_hash(slots, d_rows + a * row_words, d_len + a, (uint32_t)m, ctx->d_cts, d_slots + a, s);
-        }
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    return GKR_OK;
-}
+using V::HashSlot;                     // (verify_rounds.h)
+constexpr size_t kHashRowWords = 24;   // a round vector of the layer sumcheck: three slots
 
 // gkr_verify_prepared's provider of the shared relations: what the kernels left, read back (pinned host memory)
 struct DeviceProvider {
@@ -212,36 +133,26 @@ int verify_chunk(gkr_ctx* ctx, const gkr_verify_circuit* vc, const Shape& sh, co
     const std::vector<uint32_t>& k = vc->k;
     const uint32_t L = sh.L;
     hipStream_t st = ctx->stream;
-    // ---- 1. the hashes start: on the context's host pool (its workers take pieces for as long as the session is open; the
-    //         guard closes it on every way out, before `host_slots` goes), or -- a chunk of enough round vectors -- on the device,
-    //         further down, once the workspaces are there (no piece is left for the pool then)
-    const size_t n_rows = (size_t)nb * sh.rounds;
-    const bool dev_hash = device_hash_wanted(n_rows);
-    std::vector<HashSlot> host_slots(dev_hash ? 0 : n_rows);
-    const HashSlot* slots = host_slots.data();
-    std::atomic<size_t> next{dev_hash ? n_rows : 0};
-    const std::function<bool()> hash_work = [&] { return hash_piece(proofs, sh.rounds, n_rows, next, host_slots.data()); };
-    gkr::SpinPool* pool = !dev_hash && n_rows >= 64 ? ctx->host_pool() : nullptr;   // waking the pool is worth some tens of hashes
-    gkr::SpinPool::Session hashing(pool, &hash_work);
-    // the side stream's work is joined on every way out: nothing may still read or write a workspace the next call reuses
-    struct SideJoin {
-        hipStream_t forked = nullptr;
-        ~SideJoin() {
-            if (forked) (void)hipStreamSynchronize(forked);
-        }
-    } side;
+    // ---- 1. the hashes start: on the context's host pool, whose workers take pieces from here on (the job's guard closes the
+    //         session on every way out, before the slots go), or -- a chunk of enough round vectors -- on the device, further down,
+    //         once the workspaces are there (no piece is left for the pool then)
+    RowSet rows{3u, sh.rounds, {}};
+    for (uint32_t p = 0; p < nb; ++p) rows.spans.push_back({proofs[p].sumcheck_coeffs, proofs[p].sumcheck_len});
+    RoundHashes hashes(ctx, "verify_", {std::move(rows)});
+    gkr::PieceJob hashing(hashes.host_pieces() && hashes.rows() >= 64 ? ctx->host_pool() : nullptr,   // waking the pool is worth some tens of hashes
+                          hashes.host_pieces(), [&](size_t a) { hashes.hash_piece(a); });
     // ---- 2. upload, every launch, one copy back
     const uint32_t pstride = (uint32_t)(sh.zlen + sh.rounds);
     Fr *d_pts, *d_dco, *d_ico, *d_tables, *d_mono, *d_partials, *d_out;
     gkr::VerifyLayer* d_layers;
-    VERIFY_WS(ctx, "verify_pts", Fr, (size_t)nb * pstride + 1, d_pts);
-    VERIFY_WS(ctx, "verify_dco", Fr, (size_t)nb * sh.n_d, d_dco);
-    VERIFY_WS(ctx, "verify_ico", Fr, (size_t)nb * sh.n_in, d_ico);
-    VERIFY_WS(ctx, "verify_tables", Fr, (size_t)nb * sh.table_elems, d_tables);
-    VERIFY_WS(ctx, "verify_mono", Fr, (size_t)nb * sh.mono_elems, d_mono);
-    VERIFY_WS(ctx, "verify_partials", Fr, (size_t)nb * sh.partial_elems, d_partials);
-    VERIFY_WS(ctx, "verify_out", Fr, (size_t)nb * sh.out_elems + (2 * (size_t)nb * sizeof(uint32_t) + sizeof(Fr) - 1) / sizeof(Fr), d_out);
-    VERIFY_WS(ctx, "verify_layers", gkr::VerifyLayer, L, d_layers);
+    WS_OR_NOMEM(ctx, "verify_pts", Fr, (size_t)nb * pstride + 1, d_pts);
+    WS_OR_NOMEM(ctx, "verify_dco", Fr, (size_t)nb * sh.n_d, d_dco);
+    WS_OR_NOMEM(ctx, "verify_ico", Fr, (size_t)nb * sh.n_in, d_ico);
+    WS_OR_NOMEM(ctx, "verify_tables", Fr, (size_t)nb * sh.table_elems, d_tables);
+    WS_OR_NOMEM(ctx, "verify_mono", Fr, (size_t)nb * sh.mono_elems, d_mono);
+    WS_OR_NOMEM(ctx, "verify_partials", Fr, (size_t)nb * sh.partial_elems, d_partials);
+    WS_OR_NOMEM(ctx, "verify_out", Fr, (size_t)nb * sh.out_elems + (2 * (size_t)nb * sizeof(uint32_t) + sizeof(Fr) - 1) / sizeof(Fr), d_out);
+    WS_OR_NOMEM(ctx, "verify_layers", gkr::VerifyLayer, L, d_layers);
     uint32_t* d_flags = reinterpret_cast<uint32_t*>(d_out + (size_t)nb * sh.out_elems);
     const size_t out_bytes = (size_t)nb * sh.out_elems * sizeof(Fr) + 2 * (size_t)nb * sizeof(uint32_t);
     const size_t coeff_bytes = (size_t)nb * (sh.n_d + sh.n_in) * sizeof(Fr);
@@ -252,30 +163,7 @@ int verify_chunk(gkr_ctx* ctx, const gkr_verify_circuit* vc, const Shape& sh, co
     HIP_TRY(ctx, ctx->pinned_host("verify_out", out_bytes, reinterpret_cast<void**>(&h_out)));
     HIP_TRY(ctx, ctx->pinned_host("verify_layers", (size_t)L * sizeof(gkr::VerifyLayer), reinterpret_cast<void**>(&h_layers)));
     if (stage) HIP_TRY(ctx, ctx->pinned_host("verify_coeffs", coeff_bytes, reinterpret_cast<void**>(&h_co)));
-    if (dev_hash) {
-        // round vectors, then lengths, in ONE staging buffer and one copy up; the slots come back into pinned memory on the side
-        // stream, whose last event the main stream waits for in front of its own result copy
-        uint32_t *d_hin, *h_hin;
-        gkr::VerifyHashSlot *d_hout, *h_hout;
-        VERIFY_WS(ctx, "verify_hash_in", uint32_t, n_rows * (kHashRowWords + 1), d_hin);
-        VERIFY_WS(ctx, "verify_hash_out", gkr::VerifyHashSlot, n_rows, d_hout);
-        HIP_TRY(ctx, ctx->pinned_host("verify_hash_in", n_rows * (kHashRowWords + 1) * sizeof(uint32_t), reinterpret_cast<void**>(&h_hin)));
-        HIP_TRY(ctx, ctx->pinned_host("verify_hash_out", n_rows * sizeof(gkr::VerifyHashSlot), reinterpret_cast<void**>(&h_hout)));
-        uint32_t* h_hlen = h_hin + n_rows * kHashRowWords;
-        for (uint32_t p = 0; p < nb; ++p) {
-            memcpy(h_hin + (size_t)p * sh.rounds * kHashRowWords, proofs[p].sumcheck_coeffs, sh.rounds * kHashRowWords * sizeof(uint32_t));
-            memcpy(h_hlen + (size_t)p * sh.rounds, proofs[p].sumcheck_len, sh.rounds * sizeof(uint32_t));
-        }
-        HIP_TRY(ctx, ctx->aux_stream(2));
-        HIP_TRY(ctx, hipEventRecord(ctx->aux_events[0], st));             // fork: after whatever the main stream still holds
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux, ctx->aux_events[0], 0));
-        side.forked = ctx->aux;
-        HIP_TRY(ctx, hipMemcpyAsync(d_hin, h_hin, n_rows * (kHashRowWords + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->aux));
-        if (const int rc = hash_rows_device(ctx, 3, d_hin, d_hin + n_rows * kHashRowWords, n_rows, d_hout, ctx->aux)) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(h_hout, d_hout, n_rows * sizeof(gkr::VerifyHashSlot), hipMemcpyDeviceToHost, ctx->aux));
-        HIP_TRY(ctx, hipEventRecord(ctx->aux_events[1], ctx->aux));
-        slots = reinterpret_cast<const HashSlot*>(h_hout);
-    }
+    if (const int rc = hashes.start()) return rc;   // (the device's share of 1)
     for (uint32_t p = 0; p < nb; ++p) {
         if (sh.zlen) memcpy(h_pts + (size_t)p * pstride, proofs[p].z, sh.zlen * sizeof(Fr));
         memcpy(h_pts + (size_t)p * pstride + sh.zlen, proofs[p].sumcheck_r, sh.rounds * sizeof(Fr));
@@ -330,19 +218,16 @@ int verify_chunk(gkr_ctx* ctx, const gkr_verify_circuit* vc, const Shape& sh, co
         gkr::launch_verify_mono_eval(d_pts, pstride, (uint32_t)sh.z_off[L], kL, d_ico, mono, mono + ((size_t)nb << (kL - kL / 2)), part, d_ev + nb, nb, st);
     }
     HIP_TRY(ctx, hipGetLastError());
-    if (dev_hash) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->aux_events[1], 0));   // join: the slots are back before the results are
+    if (const int rc = hashes.join()) return rc;   // the slots are back before the results are
     HIP_TRY(ctx, hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
     // ---- 3. this thread hashes too (the host's pieces, if there are any), then the one synchronisation and the relations
-    while (hash_work()) {
-    }
-    hashing.close();
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    side.forked = nullptr;   // (joined: the main stream waited for the side stream's last event)
+    hashing.drain();
+    if (const int rc = hashes.sync_main()) return rc;
     const Fr* h_evals = h_out + (size_t)nb * 2 * L;
     const uint32_t* h_flags = reinterpret_cast<const uint32_t*>(h_out + (size_t)nb * sh.out_elems);
     for (uint32_t p = 0; p < nb; ++p) {
         const Fr evals[2] = {h_evals[p], h_evals[nb + p]};
-        DeviceProvider prov{L, sh.rounds, sh.last_row.data(), slots + (size_t)p * sh.rounds, h_out + (size_t)p * 2 * L, evals, h_flags + 2 * (size_t)p};
+        DeviceProvider prov{L, sh.rounds, sh.last_row.data(), hashes.slots() + (size_t)p * sh.rounds, h_out + (size_t)p * 2 * L, evals, h_flags + 2 * (size_t)p};
         uint32_t fl = 0, fc = 0;
         const int rc = V::relations(L, k.data(), &proofs[p], prov, &accept[p], &fl, &fc);
         if (rc) return ctx->fail(rc, "gkr_verify_prepared: the relations of a proof could not be evaluated");
@@ -353,15 +238,6 @@ int verify_chunk(gkr_ctx* ctx, const gkr_verify_circuit* vc, const Shape& sh, co
 }
 
 }  // namespace
-
-// the plain and the product sumcheck's verifier (capi_mle_verify.hip) hash their round vectors through the same threshold and the same launcher
-namespace gkr_host {
-bool verify_device_hash_wanted(size_t rows) { return device_hash_wanted(rows); }
-int verify_hash_rows_device(gkr_ctx* ctx, int slots, const uint32_t* d_rows, const uint32_t* d_len, size_t n, gkr::VerifyHashSlot* d_slots,
-                            hipStream_t s) {
-    return hash_rows_device(ctx, slots, d_rows, d_len, n, d_slots, s);
-}
-}  // namespace gkr_host
 
 extern "C" {
 
@@ -421,17 +297,10 @@ int gkr_verify_prepared(gkr_ctx* ctx, const gkr_verify_circuit* vc, const gkr_pr
     if (vc->device != ctx->device) return ctx->fail(GKR_ERR_INVALID, "the handle was prepared on another device");
     GKR_ENTER(ctx);
     const Shape sh = shape_of(vc->k);
-    long long mb = gkr::opt(gkr::OPT_verify_workspace_mb);
-    if (mb <= 0) mb = 2048;
-    size_t chunk = ((size_t)mb << 20) / sh.bytes_per_proof();
-    chunk = std::max<size_t>(1, std::min<size_t>(chunk, 32768));   // (the proof is a grid dimension of the launches)
-    for (int b = 0; b < batch; b += (int)chunk) {
-        const uint32_t nb = (uint32_t)std::min<size_t>(chunk, (size_t)(batch - b));
-        const int rc = verify_chunk(ctx, vc, sh, proofs + b, nb, accept + b, failed_layer ? failed_layer + b : nullptr,
-                                    failed_check ? failed_check + b : nullptr);
-        if (rc) return rc;
-    }
-    return GKR_OK;
+    return for_chunks(batch, verify_chunk_size(sh.bytes_per_proof(), 32768, batch), [&](size_t b, uint32_t nb) {
+        return verify_chunk(ctx, vc, sh, proofs + b, nb, accept + b, failed_layer ? failed_layer + b : nullptr,
+                            failed_check ? failed_check + b : nullptr);
+    });
 }
 
 int gkr_mimc7_multi_hash_device(gkr_ctx* ctx, const gkr_fr* rows, const uint32_t* len, size_t n, gkr_fr* out, uint32_t* valid) {
@@ -441,8 +310,8 @@ int gkr_mimc7_multi_hash_device(gkr_ctx* ctx, const gkr_fr* rows, const uint32_t
     const size_t cap = std::min(n, kPieceRows);
     uint32_t *d_in, *h_in;
     gkr::VerifyHashSlot *d_out, *h_out;
-    VERIFY_WS(ctx, "verify_hash_in", uint32_t, cap * (kHashRowWords + 1), d_in);
-    VERIFY_WS(ctx, "verify_hash_out", gkr::VerifyHashSlot, cap, d_out);
+    WS_OR_NOMEM(ctx, "verify_hash_in", uint32_t, cap * (kHashRowWords + 1), d_in);
+    WS_OR_NOMEM(ctx, "verify_hash_out", gkr::VerifyHashSlot, cap, d_out);
     HIP_TRY(ctx, ctx->pinned_host("verify_hash_in", cap * (kHashRowWords + 1) * sizeof(uint32_t), reinterpret_cast<void**>(&h_in)));
     HIP_TRY(ctx, ctx->pinned_host("verify_hash_out", cap * sizeof(gkr::VerifyHashSlot), reinterpret_cast<void**>(&h_out)));
     for (size_t a = 0; a < n; a += cap) {
@@ -450,7 +319,7 @@ int gkr_mimc7_multi_hash_device(gkr_ctx* ctx, const gkr_fr* rows, const uint32_t
         memcpy(h_in, rows + a * 3, m * kHashRowWords * sizeof(uint32_t));
         memcpy(h_in + m * kHashRowWords, len + a, m * sizeof(uint32_t));
         HIP_TRY(ctx, hipMemcpyAsync(d_in, h_in, m * (kHashRowWords + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-        if (const int rc = hash_rows_device(ctx, 3, d_in, d_in + m * kHashRowWords, m, d_out, ctx->stream)) return rc;
+        if (const int rc = verify_hash_rows_device(ctx, 3, d_in, d_in + m * kHashRowWords, m, d_out, ctx->stream)) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(h_out, d_out, m * sizeof(gkr::VerifyHashSlot), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         for (size_t i = 0; i < m; ++i) {

@@ -229,4 +229,36 @@ class SpinPool {
     std::atomic<int> job_busy_{0};
 };
 
+// Host work cut into the numbered pieces 0 .. pieces - 1 (the batch verifiers' hashes and relations): piece(a) runs exactly once
+// for every a.  Two steps: from the constructor on the pool's workers take pieces (a session is open; null pool: nobody does);
+// drain() makes the calling thread take pieces too and returns once every piece has been run to its end.  Whatever path leaves
+// the scope closes the session, so the job and what `piece` refers to may live in the caller's stack frame.
+class PieceJob {
+   public:
+    PieceJob(SpinPool* pool, size_t pieces, std::function<void(size_t)> piece)
+        : pieces_(pieces), piece_(std::move(piece)), work_([this] { return take(); }), session_(pool, &work_) {}
+    void drain() {
+        while (take()) {
+        }
+        session_.close();
+    }
+
+   private:
+    bool take() {
+        const size_t a = cursor_.next.fetch_add(1, std::memory_order_relaxed);
+        if (a >= pieces_) return false;
+        piece_(a);
+        return true;
+    }
+    // The cursor has a cache line to itself: idle workers keep claiming from it for as long as the session is open, and the job
+    // lives in the stack frame of a thread that queues device work meanwhile -- its locals must not share the line.
+    struct alignas(64) Cursor {
+        std::atomic<size_t> next{0};
+    } cursor_;
+    const size_t pieces_;
+    const std::function<void(size_t)> piece_;
+    const std::function<bool()> work_;
+    SpinPool::Session session_;   // the last member: closed before the others go
+};
+
 }  // namespace gkr

@@ -97,6 +97,45 @@ int main(int argc, char** argv) {
             });
         for (auto& t : ts) t.join();
     }
+    // PieceJob (the batch verifiers' for_pieces): every piece runs exactly once, with no pool, with pools of 0, 1 and several
+    // workers, for no piece at all, for counts below, at and above the verifiers' pool threshold of 8, in both forms -- drained at
+    // once, and opened, left to the workers for a while, then drained; the counters live in the caller's frame
+    {
+        gkr::SpinPool none(0), one(1), several(workers + 2);
+        gkr::SpinPool* const pools[] = {nullptr, &none, &one, &several};
+        const size_t counts[] = {0, 1, 7, 8, 9, 64, 1000};
+        for (long rep = 0; rep < rounds / 2000 + 5; ++rep)
+            for (gkr::SpinPool* p : pools)
+                for (const size_t n : counts)
+                    for (int two_step = 0; two_step < 2; ++two_step) {
+                        std::vector<std::atomic<int>> ran(n);
+                        std::vector<int> plain(n, 0);   // written by whoever runs the piece, read after drain(): a race if drain returns early
+                        for (auto& r : ran) r.store(0);
+                        {
+                            gkr::PieceJob job(p, n, [&](size_t a) {
+                                if (a >= n) bad.fetch_add(1);
+                                else {
+                                    ran[a].fetch_add(1, std::memory_order_relaxed);
+                                    plain[a] += 1;
+                                }
+                            });
+                            if (two_step) std::this_thread::yield();   // (the caller queues its device work here)
+                            job.drain();
+                            for (size_t a = 0; a < n; ++a)
+                                if (ran[a].load() != 1 || plain[a] != 1) bad.fetch_add(1);
+                        }
+                    }
+        // a job left without drain() (an error return): the guard closes the session, nobody runs a piece afterwards
+        for (int rep = 0; rep < 200; ++rep) {
+            std::atomic<int> ran{0};
+            {
+                gkr::PieceJob job(&several, 100, [&](size_t) { ran.fetch_add(1, std::memory_order_relaxed); });
+            }
+            const int seen = ran.load();
+            std::this_thread::yield();
+            if (seen > 100 || ran.load() != seen) bad.fetch_add(1);
+        }
+    }
     printf("workers=%d rounds=%ld bad=%ld\n", workers, rounds, bad.load());
     return bad.load() ? 1 : 0;
 }
