@@ -28,6 +28,8 @@ GKR_VERIFY_ROUND_SUM, GKR_VERIFY_CHALLENGE, GKR_VERIFY_EVALUATION = 4, 5, 10
 GKR_VERIFY_MATRIX, GKR_VERIFY_WITNESS = 11, 12
 # the grand product verifier's own (gkr_grand_product_verify*): a layer's last relation, a claimed product against the head's
 GKR_VERIFY_FINAL_CLAIM, GKR_VERIFY_PRODUCT = 6, 13
+# the fractional sum verifier's own (gkr_fraction_sum_verify*): the head's Q is zero, a claimed (P, Q) against the head's root
+GKR_VERIFY_ZERO_DENOMINATOR, GKR_VERIFY_FRACTION_SUM = 14, 15
 
 # rows of an R1CS matrix with more terms than this get a wave each on the device (GKR_R1CS_LONG_ROW)
 GKR_R1CS_LONG_ROW = 32
@@ -55,6 +57,8 @@ SYMBOLS = [
     "gkr_sumcheck_zerocheck_batch_device", "gkr_sumcheck_zerocheck", "gkr_eq_table_device",
     "gkr_grand_product_batch_device", "gkr_grand_product", "gkr_grand_product_verify_batch_device", "gkr_grand_product_verify",
     "gkr_selftest_grand_product_geometry", "gkr_devtest_grand_product_tree", "gkr_devtest_grand_product_chunk",
+    "gkr_fraction_sum_batch_device", "gkr_fraction_sum", "gkr_fraction_sum_verify_batch_device", "gkr_fraction_sum_verify",
+    "gkr_selftest_fraction_sum_geometry", "gkr_devtest_fraction_sum_tree", "gkr_devtest_fraction_sum_chunk",
     "gkr_mle_eval_batch_device", "gkr_sumcheck_mle_verify_batch_device", "gkr_sumcheck_mle_verify",
     "gkr_sumcheck_layer", "gkr_sumcheck_layer_sharded", "gkr_sumcheck_layer_device", "gkr_resident_layer_create", "gkr_resident_layer_sumcheck", "gkr_resident_layer_sumcheck_wdev", "gkr_resident_layer_free", "gkr_exchange_limbs", "gkr_resident_layer_sumcheck_dev", "gkr_exchange_limbs_mle", "gkr_sumcheck_mle_sharded_dev", "gkr_exchange_rccl_unique_id", "gkr_exchange_rccl_create", "gkr_exchange_rccl_dev",
     "gkr_exchange_rccl_calls", "gkr_exchange_rccl_destroy", "gkr_exchange_rccl_error", "gkr_fr_widen", "gkr_fr_narrow", "gkr_predicate_tables", "gkr_layer_eval", "gkr_proof_sizes", "gkr_prove", "gkr_prove_batch",
@@ -217,6 +221,20 @@ def lib():
         L.gkr_devtest_grand_product_tree.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p]
         L.gkr_devtest_grand_product_chunk.restype = ctypes.c_int
         L.gkr_devtest_grand_product_chunk.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 2 + [ctypes.c_void_p]
+        L.gkr_fraction_sum_batch_device.restype = ctypes.c_int
+        L.gkr_fraction_sum_batch_device.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 8
+        L.gkr_fraction_sum.restype = ctypes.c_int
+        L.gkr_fraction_sum.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] + [ctypes.c_void_p] * 8
+        L.gkr_fraction_sum_verify_batch_device.restype = ctypes.c_int
+        L.gkr_fraction_sum_verify_batch_device.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 11
+        L.gkr_fraction_sum_verify.restype = ctypes.c_int
+        L.gkr_fraction_sum_verify.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] + [ctypes.c_void_p] * 10
+        L.gkr_selftest_fraction_sum_geometry.restype = ctypes.c_int
+        L.gkr_selftest_fraction_sum_geometry.argtypes = [ctypes.c_int, ctypes.c_void_p]
+        L.gkr_devtest_fraction_sum_tree.restype = ctypes.c_int
+        L.gkr_devtest_fraction_sum_tree.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p]
+        L.gkr_devtest_fraction_sum_chunk.restype = ctypes.c_int
+        L.gkr_devtest_fraction_sum_chunk.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 2 + [ctypes.c_void_p]
         # the R1CS zero-check: the CSR form (host only), the resident handle, the rows, the zero-check on them
         L.gkr_r1cs_csr_info.restype = ctypes.c_int
         L.gkr_r1cs_csr_info.argtypes = [ctypes.c_void_p] * 2

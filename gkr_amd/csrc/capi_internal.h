@@ -4,9 +4,10 @@
 // its dense form; capi_prove.hip: whole proofs; capi_product.hip: the sumcheck over a product of resident tables; capi_sop.hip: over a sum of
 // such products; capi_zerocheck.hip: the zero-check -- the entry points and shape checks of the three, whose one driver is
 // capi_resident.hip; capi_r1cs.hip: an R1CS's tables in front of it; capi_r1cs_verify.hip: the verifier of that pair of
-// sumchecks; capi_grand_product.hip: the grand product, a product tree and a zero-check per layer, and its verifier; capi_verify.hip
+// sumchecks; capi_grand_product.hip: the grand product, a product tree and a zero-check per layer, and its verifier;
+// capi_fraction_sum.hip: the fractional sum, a tree of fractions and a zero-check per layer, and its verifier; capi_verify.hip
 // and capi_mle_verify.hip: the verifiers of whole proofs and of the sumchecks over resident tables; verify_chunk.h: the pieces the
-// four files with a batch verifier build a chunk from): the context, its caches and workspaces, profiling brackets, the host
+// five files with a batch verifier build a chunk from): the context, its caches and workspaces, profiling brackets, the host
 // transcript's helpers, the hand-off wait, the plain sumcheck's group hand-off.  Not a public header.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -831,6 +832,11 @@ int run_sop_batch(gkr_ctx* ctx, const Fr* d_tables, int n, const gkr::SopTerms& 
 // argument checks: everything already queued on the context's stream is waited for, the outputs are in the caller's arrays
 int run_zerocheck_batch(gkr_ctx* ctx, const Fr* d_tables, int n, const gkr::SopTerms& ts, const gkr::SopCoeffs& cf, int batch,
                         const gkr_fr* z, gkr_fr* out_coeffs, uint32_t* out_len, gkr_fr* out_r, gkr_fr* out_evals, gkr_fr* out_eq);
+// `batch` layers of the fractional sum: the zero-check of T0 T3 + T1 T2 + lambda_b T2 T3 at z_b over four resident tables of 2^k
+// entries per sumcheck (table m of sumcheck b at d_tables + (4 b + m) * 2^k); z: batch x k, lambda: batch, canonical.  Byte for
+// byte run_zerocheck_batch with batch 1 on each sumcheck with its own coefficients (1, 1, lambda_b)
+int run_fraction_layer_batch(gkr_ctx* ctx, const Fr* d_tables, int k, int batch, const gkr_fr* z, const gkr_fr* lambda, gkr_fr* out_coeffs,
+                             uint32_t* out_len, gkr_fr* out_r, gkr_fr* out_evals, gkr_fr* out_eq);
 // ---- defined in capi_prove.hip
 void mobius_msb(std::vector<gkr::h64::F>& c, int k);
 void line_restriction(const std::vector<gkr::h64::F>& vals, const std::vector<gkr::h64::F>& coeffs, int k, const gkr_fr* b, const gkr_fr* c,

@@ -1,7 +1,8 @@
 // THE driver of the sumchecks over resident multilinear tables -- a product (capi_product.hip), a sum of products (capi_sop.hip),
-// the zero-check (capi_zerocheck.hip): the workspace, per round one pass launch (round 1: values only; later: fold and values) and
-// one round launch, the read-backs.  A family describes itself in a small struct: its slot names and timing labels, its sizes,
-// three launch hooks and what it reads back besides; run_product_batch, run_sop_batch and run_zerocheck_batch fill one in.
+// the zero-check (capi_zerocheck.hip), a layer of the fractional sum (capi_fraction_sum.hip): the workspace, per round one pass
+// launch (round 1: values only; later: fold and values) and one round launch, the read-backs.  A family describes itself in a small struct: its slot names and timing labels, its sizes,
+// three launch hooks and what it reads back besides; run_product_batch, run_sop_batch, run_zerocheck_batch and run_fraction_layer_batch
+// fill one in.
 #include "capi_internal.h"
 
 namespace gkr_host {
@@ -109,17 +110,11 @@ struct SopFamily {
     hipError_t read_back(const ResidentCall&) const { return hipSuccess; }
 };
 
-// the SOP family's passes with the weights of the variables still free, its round with the points and the bound variables' scalar
-// (kernels_zerocheck.hip); rows have one slot more: the eq factor's degree
-struct ZerocheckFamily {
-    static constexpr ResidentNames names = {"zc.work", "zc.partials", "zc.coeffs", "zc.r", "zc.rtab", "zc.len", "zc.evals",
-                                            "zc_first", "zc_fold_sum", "zc_round"};
+// the SOP family's passes with the weights of the variables still free (kernels_zerocheck.hip): shared by the zero-check and the
+// fractional sum's layers
+struct ZcPasses {
     const gkr::SopTerms& ts;
-    const gkr::SopCoeffs& cf;
-    uint32_t n_tables, slots, partials_per_block;
     gkr::ZcWeights w;
-    Fr *d_z, *d_s, *d_eq;
-    gkr_fr* out_eq;
     // round `round` has n - 1 - round free variables: the last kl <= 8 of them weigh per thread, the kh in front per iteration
     static uint32_t lo_vars(const ResidentCall& c, uint32_t round) { return std::min(c.n - 1u - round, 8u); }
     void first(const ResidentCall& c, const Fr* tables, uint32_t items, uint32_t nblk) const {
@@ -131,8 +126,35 @@ struct ZerocheckFamily {
         gkr::launch_zc_fold_sum(ts, src, src_stride, c.work, c.len / 2, items, c.batch, nblk, c.d_rtab + (round - 1), c.n, w, c.n - 1u - round - kl,
                                 kl, c.partials, c.s);
     }
+};
+
+// those passes, the round with the points and the bound variables' scalar; rows have one slot more: the eq factor's degree
+struct ZerocheckFamily : ZcPasses {
+    static constexpr ResidentNames names = {"zc.work", "zc.partials", "zc.coeffs", "zc.r", "zc.rtab", "zc.len", "zc.evals",
+                                            "zc_first", "zc_fold_sum", "zc_round"};
+    const gkr::SopCoeffs& cf;
+    uint32_t n_tables, slots, partials_per_block;
+    Fr *d_z, *d_s, *d_eq;
+    gkr_fr* out_eq;
     void round(const ResidentCall& c, uint32_t round, uint32_t nblk) const {
         gkr::launch_zc_round(ts, cf, c.partials, nblk, round, c.n, c.batch, c.ctx->d_cts, d_z, d_s, c.work, c.len / 2, c.d_coeffs, c.d_len, c.d_r,
+                             c.d_rtab, c.d_evals, d_eq, c.s);
+    }
+    hipError_t read_back(const ResidentCall& c) const {
+        return out_eq ? hipMemcpyAsync(out_eq, d_eq, (size_t)c.batch * sizeof(Fr), hipMemcpyDeviceToHost, c.s) : hipSuccess;
+    }
+};
+
+// a layer of the fractional sum (kernels_fraction_sum.hip): the zero-check's passes over the layer's three terms, its round with
+// the third term's coefficient per sumcheck; slots of its own, so that neither resizes the other's buffers
+struct FractionFamily : ZcPasses {
+    static constexpr ResidentNames names = {"fs.work", "fs.partials", "fs.coeffs", "fs.r", "fs.rtab", "fs.len", "fs.evals",
+                                            "fs_first", "fs_fold_sum", "fs_round"};
+    uint32_t n_tables, slots, partials_per_block;
+    Fr *d_z, *d_lambda, *d_s, *d_eq;
+    gkr_fr* out_eq;
+    void round(const ResidentCall& c, uint32_t round, uint32_t nblk) const {
+        gkr::launch_fs_round(c.partials, nblk, round, c.n, c.batch, d_lambda, c.ctx->d_cts, d_z, d_s, c.work, c.len / 2, c.d_coeffs, c.d_len, c.d_r,
                              c.d_rtab, c.d_evals, d_eq, c.s);
     }
     hipError_t read_back(const ResidentCall& c) const {
@@ -157,7 +179,7 @@ int run_sop_batch(gkr_ctx* ctx, const Fr* d_tables, int n, const gkr::SopTerms& 
 
 int run_zerocheck_batch(gkr_ctx* ctx, const Fr* d_tables, int n, const gkr::SopTerms& ts, const gkr::SopCoeffs& cf, int batch,
                         const gkr_fr* z, gkr_fr* out_coeffs, uint32_t* out_len, gkr_fr* out_r, gkr_fr* out_evals, gkr_fr* out_eq) {
-    ZerocheckFamily fam{ts, cf, ts.n_tables, ts.max_degree + 2u, ts.n_terms, {}, nullptr, nullptr, nullptr, out_eq};
+    ZerocheckFamily fam{{ts, {}}, cf, ts.n_tables, ts.max_degree + 2u, ts.n_terms, nullptr, nullptr, nullptr, out_eq};
     Fr* d_w = nullptr;
     WS(ctx, "zc.points", Fr, (size_t)batch * n, fam.d_z);
     WS(ctx, "zc.s", Fr, batch, fam.d_s);
@@ -170,6 +192,27 @@ int run_zerocheck_batch(gkr_ctx* ctx, const Fr* d_tables, int n, const gkr::SopT
         gkr::launch_zc_weights(fam.d_z, (uint32_t)n, (uint32_t)batch, fam.w, ctx->stream);
     }
     return run_resident_batch(ctx, fam, d_tables, n, batch, out_coeffs, out_len, out_r, out_evals);
+}
+
+int run_fraction_layer_batch(gkr_ctx* ctx, const Fr* d_tables, int k, int batch, const gkr_fr* z, const gkr_fr* lambda, gkr_fr* out_coeffs,
+                             uint32_t* out_len, gkr_fr* out_r, gkr_fr* out_evals, gkr_fr* out_eq) {
+    // T0 T3 + T1 T2 + lambda T2 T3: the structure the passes read; the coefficients are the round kernel's own
+    static const gkr::SopTerms ts = {4u, 3u, 2u, {2u | 0u << 8 | 3u << 16, 2u | 1u << 8 | 2u << 16, 2u | 2u << 8 | 3u << 16}};
+    FractionFamily fam{{ts, {}}, ts.n_tables, ts.max_degree + 2u, ts.n_terms, nullptr, nullptr, nullptr, nullptr, out_eq};
+    Fr* d_w = nullptr;
+    WS(ctx, "fs.points", Fr, (size_t)batch * (k + 1), fam.d_z);   // the points, then the lambdas
+    WS(ctx, "fs.s", Fr, batch, fam.d_s);
+    WS(ctx, "fs.eq", Fr, batch, fam.d_eq);
+    WS(ctx, "fs.weights", Fr, gkr::zc_weight_elements((uint32_t)k, (uint32_t)batch), d_w);
+    fam.d_lambda = fam.d_z + (size_t)batch * k;
+    fam.w = gkr::zc_weights_layout(d_w, (uint32_t)k, (uint32_t)batch);
+    HIP_TRY(ctx, hipMemcpyAsync(fam.d_z, z, (size_t)batch * k * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(fam.d_lambda, lambda, (size_t)batch * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+    {
+        Timed t(ctx, "fs_weights", 0.0, nullptr, true);
+        gkr::launch_zc_weights(fam.d_z, (uint32_t)k, (uint32_t)batch, fam.w, ctx->stream);
+    }
+    return run_resident_batch(ctx, fam, d_tables, k, batch, out_coeffs, out_len, out_r, out_evals);
 }
 
 }  // namespace gkr_host

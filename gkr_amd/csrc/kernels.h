@@ -349,6 +349,20 @@ __host__ __device__ inline size_t gp_layer_offset(uint32_t level, uint32_t batch
 // tables: batch x 2^n canonical values, table b at + b * 2^n, not modified; layers: batch * (2^n - 1) elements, levels 0 .. n-1
 void launch_gp_tree(const Fr* tables, uint32_t n, uint32_t batch, Fr* layers, hipStream_t s);
 
+// ---- the fractional sum's tree and round (kernels_fraction_sum.hip): (p, q)_k[i] = (p lo q hi + p hi q lo, q lo q hi) of level k + 1 ----
+// One launch per level k = n-1 .. 0, fs_level_blocks(k) = ceil(2^k / 256) blocks of 256 threads per pair, a thread per node.
+uint32_t fs_level_blocks(uint32_t k);
+// level k (p_k then q_k, 2^k entries each, per pair) of a batch's trees starts at this element of `layers`, pair b at + b * 2^(k+1)
+__host__ __device__ inline size_t fs_layer_offset(uint32_t level, uint32_t batch) { return 2 * (size_t)batch * (((size_t)1 << level) - 1); }
+// tables: batch pairs (N then D, 2^n canonical values each), pair b at + b * 2^(n+1), not modified; layers: 2 batch (2^n - 1)
+// elements, levels 0 .. n-1
+void launch_fs_tree(const Fr* tables, uint32_t n, uint32_t batch, Fr* layers, hipStream_t s);
+// launch_zc_round for the layer's three terms T0 T3 + T1 T2 + lambda[b] T2 T3 over four tables: lambda: batch canonical elements;
+// partials: batch x nblk x 3; out_coeffs: batch x n rows of 4 slots; evals: batch x 4
+void launch_fs_round(const ProductPartial* partials, uint32_t nblk, uint32_t round, uint32_t n, uint32_t batch, const Fr* lambda, const Fr* cts,
+                     const Fr* z, Fr* s_slot, const Fr* work, size_t work_stride, Fr* out_coeffs, uint32_t* out_len, Fr* out_r, FixedMul* rtab,
+                     Fr* evals, Fr* eq_out, hipStream_t s);
+
 void launch_layer_eval(uint32_t gates, const uint8_t* gate_type, const uint32_t* left, const uint32_t* right,
                        const Fr* prev, Fr* out, uint32_t batch, uint32_t prev_stride, hipStream_t s, const GateSet* sets = nullptr);
 // words 32-bit words src -> dst (16-byte aligned when words >= 4); either side may be pinned host memory

@@ -134,7 +134,8 @@ __global__ void __launch_bounds__(256) k_zc_fold_sum(const Fr* src, size_t src_s
 
 // One wave per sumcheck and round: term after term the blocks' partials are totalled, a degree-2 term's 2^-256 undone, the term's
 // coefficients formed (product_values_to_coeffs<d_k>), multiplied by c_k and added right-aligned into h_j's three slots.  Then
-// g_j = (a + b X) h_j with a = s_j (1 - z_j), b = s_j (2 z_j - 1), written out slot by slot, and the sum-of-products path's steps
+// (from here on zc_round_tail, product_common.h, shared with k_fs_round) g_j = (a + b X) h_j with a = s_j (1 - z_j),
+// b = s_j (2 z_j - 1), written out slot by slot, and the sum-of-products path's steps
 // of EVERY round (product_common.h): leading zero coefficients dropped, one kept at least, MiMC7 of the used slots, r published
 // canonical and as the next fold's multiplier table.  s_{j+1} = a + b r_j goes to the sumcheck's slot s_slot[b] (Montgomery).  Rows of out_coeffs have
 // D + 1 slots, D = ts.max_degree + 1.  After round n: evals[b M + m] = T_m~(r_1 .. r_n) and eq_out[b] = s_{n+1} = eq(z, r).
@@ -144,35 +145,13 @@ __global__ void __launch_bounds__(64) k_zc_round(const ProductPartial* __restric
                                                  Fr* __restrict__ s_slot, const Fr* __restrict__ work, size_t work_stride,
                                                  Fr* __restrict__ out_coeffs, uint32_t* __restrict__ out_len, Fr* __restrict__ out_r,
                                                  FixedMul* __restrict__ rtab, Fr* __restrict__ evals, Fr* __restrict__ eq_out) {
-    constexpr int V = kZcValues, S = kZcValues + 1;
+    constexpr int V = kZcValues;
     const uint32_t b = blockIdx.x, K = ts.n_terms;
     const ProductPartial* p = partials + (size_t)b * nblk * K;
     Fr h[V];   // h_j, highest degree first, right-aligned (thread 0's)
     terms_total<V - 1>(p, nblk, ts, cf, h);
     if (threadIdx.x != 0) return;
-    // the linear factor of the round's own variable times the bound variables' scalar, in Montgomery form
-    const Fr zj = load_fr(z + (size_t)b * n + round);
-    Fr one = fr_zero();
-    one.l[0] = 1u;
-    const Fr s_j = round == 0 ? fr_mont_one() : load_fr(s_slot + b);
-    const Fr fa = mont_mul(to_mont(fr_sub(one, zj)), s_j);                    // s_j (1 - z_j)
-    const Fr fb = mont_mul(to_mont(fr_sub(fr_add(zj, zj), one)), s_j);        // s_j (2 z_j - 1)
-    Fr sum[S];   // g_j = (fa + fb X) h_j, highest degree first
-    sum[0] = mont_mul(h[0], fb);
-    sum[1] = fr_add(mont_mul(h[0], fa), mont_mul(h[1], fb));
-    sum[2] = fr_add(mont_mul(h[1], fa), mont_mul(h[2], fb));
-    sum[3] = mont_mul(h[2], fa);
-    const size_t row = (size_t)b * n + round;
-    const Fr r = round_publish<S>(sum, round_length<S>(sum), ts.max_degree + 1u, row, cts, out_coeffs, out_len, out_r);
-    const Fr r_mont = to_mont(r);
-    const Fr s_next = fr_add(fa, mont_mul(fb, r_mont));   // s_j eq(z_j, r_j)
-    if (round + 1 < n) {
-        store_fixed_mul(rtab + row, r);
-        store_fr(s_slot + b, s_next);
-    } else {
-        fold_last_entries(work, work_stride, b, ts.n_tables, r_mont, evals);
-        store_fr(eq_out + b, from_mont(s_next));
-    }
+    zc_round_tail(h, b, round, n, ts.n_tables, ts.max_degree, cts, z, s_slot, work, work_stride, out_coeffs, out_len, out_r, rtab, evals, eq_out);
 }
 
 // ---------------------------------------------------------------------------

@@ -2,7 +2,8 @@
 // (kernels_sop.hip), the zero-check (kernels_zerocheck.hip): a block's chunk, the fold of every table of a chunk, what a thread
 // accumulates a round polynomial's values in, one index's terms of the D + 1 values, the block's partial, the term structure's
 // decoders, and the round kernels' steps: a term's partials -> its scaled coefficients, the length rule, the row with its hash
-// and challenge, the tables' values after the last round.  Internal to the library.
+// and challenge, the tables' values after the last round, and the zero-check's round behind h_j (k_zc_round and
+// kernels_fraction_sum.hip's k_fs_round).  Internal to the library.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -250,6 +251,41 @@ __device__ __forceinline__ void fold_last_entries(const Fr* __restrict__ work, s
     for (uint32_t m = 0; m < n_tables; ++m) {
         const Fr* t = work + ((size_t)b * n_tables + m) * work_stride;
         evals[(size_t)b * n_tables + m] = fr_fold(t[0], t[1], r_mont);
+    }
+}
+
+// The zero-check's round behind h_j (thread 0 alone; h: three coefficients, highest degree first, Montgomery), shared by
+// k_zc_round and k_fs_round: g_j = (a + b X) h_j with a = s_j (1 - z_j), b = s_j (2 z_j - 1), the length rule, the row with its hash
+// and challenge, s_{j+1} = a + b r_j to s_slot[b] (Montgomery) and r as the next fold's multiplier table; behind round n the
+// tables' last values and eq_out[b] = eq(z, r) instead.  Rows have max_degree + 2 slots.
+__device__ __forceinline__ void zc_round_tail(const Fr (&h)[3], uint32_t b, uint32_t round, uint32_t n, uint32_t n_tables, uint32_t max_degree,
+                                              const Fr* __restrict__ cts, const Fr* __restrict__ z, Fr* __restrict__ s_slot,
+                                              const Fr* __restrict__ work, size_t work_stride, Fr* __restrict__ out_coeffs,
+                                              uint32_t* __restrict__ out_len, Fr* __restrict__ out_r, FixedMul* __restrict__ rtab,
+                                              Fr* __restrict__ evals, Fr* __restrict__ eq_out) {
+    constexpr int S = 4;
+    // the linear factor of the round's own variable times the bound variables' scalar, in Montgomery form
+    const Fr zj = load_fr(z + (size_t)b * n + round);
+    Fr one = fr_zero();
+    one.l[0] = 1u;
+    const Fr s_j = round == 0 ? fr_mont_one() : load_fr(s_slot + b);
+    const Fr fa = mont_mul(to_mont(fr_sub(one, zj)), s_j);                    // s_j (1 - z_j)
+    const Fr fb = mont_mul(to_mont(fr_sub(fr_add(zj, zj), one)), s_j);        // s_j (2 z_j - 1)
+    Fr sum[S];   // g_j = (fa + fb X) h_j, highest degree first
+    sum[0] = mont_mul(h[0], fb);
+    sum[1] = fr_add(mont_mul(h[0], fa), mont_mul(h[1], fb));
+    sum[2] = fr_add(mont_mul(h[1], fa), mont_mul(h[2], fb));
+    sum[3] = mont_mul(h[2], fa);
+    const size_t row = (size_t)b * n + round;
+    const Fr r = round_publish<S>(sum, round_length<S>(sum), max_degree + 1u, row, cts, out_coeffs, out_len, out_r);
+    const Fr r_mont = to_mont(r);
+    const Fr s_next = fr_add(fa, mont_mul(fb, r_mont));   // s_j eq(z_j, r_j)
+    if (round + 1 < n) {
+        store_fixed_mul(rtab + row, r);
+        store_fr(s_slot + b, s_next);
+    } else {
+        fold_last_entries(work, work_stride, b, n_tables, r_mont, evals);
+        store_fr(eq_out + b, from_mont(s_next));
     }
 }
 

@@ -677,6 +677,104 @@ class Context:
                                                      ctypes.byref(check)))
         return int(check.value), int(layer.value), int(rnd.value)
 
+    # -- the fractional sum (LogUp) sum_i N[i] / D[i] = P / Q: the tree of fractions on the device, a zero-check per layer
+    @staticmethod
+    def fraction_sum_rounds(n):
+        """R = n (n - 1) / 2 - 1: the rounds of the layers k = 2 .. n - 1 of a fractional sum over 2^n fractions; layer k's rows
+        start at k (k - 1) / 2 - 1 (the grand product's bookkeeping)."""
+        return n * (n - 1) // 2 - 1
+
+    def fraction_sum_batch_device(self, d_tables, n, batch, out=None):
+        """gkr_fraction_sum_batch_device: `batch` fractional sums over resident pairs of tables of 2^n canonical values (pair b:
+        N at d_tables + 2 b 2^n elements, D at + (2 b + 1) 2^n; not modified), n >= 3.  -> (S, H, C, L, R, E, Z, K): S (batch, 2, 4)
+        the sums (P, Q); H (batch, 8, 4) the heads p_2, q_2; C (batch, R, 4, 4) the layers' right-aligned round vectors, layers
+        k = 2 .. n - 1 in order, R = fraction_sum_rounds(n); L (batch, R); R (batch, R, 4) the challenges; E (batch, n - 2, 4, 4) the
+        layers' values (a0, a1, b0, b1); Z (batch, n, 4) the final point z^(n); K (batch, 2, 4) the final claims cp_n = N~(z^(n)),
+        cq_n = D~(z^(n)).  out: the eight arrays of an earlier call."""
+        rounds = self.fraction_sum_rounds(n)
+        shapes = [((batch, 2, 4), np.uint64), ((batch, 8, 4), np.uint64), ((batch, rounds, 4, 4), np.uint64), ((batch, rounds), np.uint32),
+                  ((batch, rounds, 4), np.uint64), ((batch, n - 2, 4, 4), np.uint64), ((batch, n, 4), np.uint64), ((batch, 2, 4), np.uint64)]
+        if n < 3 or batch < 1:
+            raise GkrError(N.GKR_ERR_INVALID, "n >= 3 and batch >= 1 expected")
+        if out is not None:
+            if len(out) != 8 or any(a.shape != s or a.dtype != d for a, (s, d) in zip(out, shapes)):
+                raise GkrError(N.GKR_ERR_INVALID, "output arrays do not match (batch, n)")
+        else:
+            out = tuple(np.zeros(s, dtype=d) for s, d in shapes)
+        self._check(N.lib().gkr_fraction_sum_batch_device(self._h, d_tables, n, batch, *(_ptr(a) for a in out)))
+        return out
+
+    def prove_fraction_sum(self, numerators, denominators, v):
+        """The fractional sum of 2^v fractions N[i] / D[i] (v >= 3) with its GKR proof.  -> ((P, Q), head, layers, point, claims):
+        head = p_2 then q_2 (eight values, (P, Q) their root); layers[k - 2] = (proof, r, (a0, a1, b0, b1)) of the zero-check of
+        layer k = 2 .. v - 1 (proof[j] the round vector's used slots, highest degree first); point = z^(v) and claims = (cp_v, cq_v),
+        the evaluations of N and D the proof leaves.  verifier.verify_fraction_sum checks it on plain integers."""
+        num, den = as_limbs(numerators), as_limbs(denominators)
+        if v < 3 or num.shape[0] != 1 << v or den.shape[0] != 1 << v:
+            raise GkrError(N.GKR_ERR_INVALID, "two tables of 2^v values, v >= 3, expected")
+        rounds = self.fraction_sum_rounds(v)
+        S, H = np.zeros((2, 4), dtype=np.uint64), np.zeros((8, 4), dtype=np.uint64)
+        C, L, R = np.zeros((rounds, 4, 4), dtype=np.uint64), np.zeros(rounds, dtype=np.uint32), np.zeros((rounds, 4), dtype=np.uint64)
+        E, Z, K = np.zeros((v - 2, 4, 4), dtype=np.uint64), np.zeros((v, 4), dtype=np.uint64), np.zeros((2, 4), dtype=np.uint64)
+        self._check(N.lib().gkr_fraction_sum(self._h, _ptr(num), _ptr(den), v, _ptr(S), _ptr(H), _ptr(C), _ptr(L), _ptr(R), _ptr(E), _ptr(Z), _ptr(K)))
+        rs, layers = from_limbs(R), []
+        for k in range(2, v):
+            row = k * (k - 1) // 2 - 1
+            layers.append(([from_limbs(C[row + j])[4 - int(L[row + j]):] for j in range(k)], rs[row:row + k], tuple(from_limbs(E[k - 2]))))
+        return tuple(from_limbs(S)), from_limbs(H), layers, from_limbs(Z), tuple(from_limbs(K))
+
+    def verify_fraction_sum_batch_device(self, d_tables, n, batch, H, C, L, R, E, sums=None):
+        """gkr_fraction_sum_verify_batch_device on the resident pairs and the arrays fraction_sum_batch_device returned (its H, C,
+        L, R, E); sums: (batch, 2, 4) limbs of claimed (P, Q) or None.  -> (accept (batch,) bool, failed_layer, failed_round,
+        failed_check (batch,) uint32, sums (batch, 2, 4): the heads' own roots).  verifier.verify_fraction_sum is the same verdict
+        on plain integers."""
+        rounds = self.fraction_sum_rounds(n)
+        H, C, R, E = (np.ascontiguousarray(a, dtype=np.uint64) for a in (H, C, R, E))
+        L = np.ascontiguousarray(L, dtype=np.uint32)
+        if (H.shape != (batch, 8, 4) or C.shape != (batch, rounds, 4, 4) or L.shape != (batch, rounds) or R.shape != (batch, rounds, 4)
+                or E.shape != (batch, n - 2, 4, 4)):
+            raise GkrError(N.GKR_ERR_INVALID, "proof arrays do not match (batch, n)")
+        if sums is not None:
+            sums = np.ascontiguousarray(sums, dtype=np.uint64)
+            if sums.shape != (batch, 2, 4):
+                raise GkrError(N.GKR_ERR_INVALID, "sums of shape (batch, 2, 4) expected")
+        accept = np.zeros(batch, dtype=np.int32)
+        layer, rnd, check = (np.zeros(batch, dtype=np.uint32) for _ in range(3))
+        out = np.zeros((batch, 2, 4), dtype=np.uint64)
+        self._check(N.lib().gkr_fraction_sum_verify_batch_device(self._h, d_tables, n, batch, _ptr(sums) if sums is not None else None,
+                                                                 _ptr(H), _ptr(C), _ptr(L), _ptr(R), _ptr(E), _ptr(accept), _ptr(layer), _ptr(rnd),
+                                                                 _ptr(check), _ptr(out)))
+        return accept.astype(bool), layer, rnd, check, out
+
+    def verify_fraction_sum(self, numerators, denominators, head, layers, sums=None):
+        """gkr_fraction_sum_verify on host tables and what prove_fraction_sum returned (its head and layers; sums: the claimed (P, Q)
+        or None).  -> (check, layer, round), (0, 0, 0) for an accepted proof: verifier.verify_fraction_sum's verdict."""
+        num, den = as_limbs(numerators), as_limbs(denominators)
+        n = len(layers) + 2
+        if num.shape[0] != 1 << n or den.shape[0] != 1 << n or len(head) != 8:
+            raise GkrError(N.GKR_ERR_INVALID, "two tables of 2^n values, eight head values and n - 2 layers expected")
+        rounds = self.fraction_sum_rounds(n)
+        C, L, R = np.zeros((rounds, 4, 4), dtype=np.uint64), np.zeros(rounds, dtype=np.uint32), np.zeros((rounds, 4), dtype=np.uint64)
+        E = np.zeros((n - 2, 4, 4), dtype=np.uint64)
+        for k, (proof, r, vals) in enumerate(layers, start=2):
+            row = k * (k - 1) // 2 - 1
+            if len(proof) != k or len(r) != k or len(vals) != 4:
+                raise GkrError(N.GKR_ERR_INVALID, "layer k has k round vectors, k challenges and four values")
+            for j, g in enumerate(proof):
+                L[row + j] = len(g)
+                if 1 <= len(g) <= 4:                                       # (another length: SHAPE, the slots are not read)
+                    C[row + j, 4 - len(g):] = to_limbs([int(c) for c in g])
+            R[row:row + k] = to_limbs([int(x) for x in r])
+            E[k - 2] = to_limbs([int(x) for x in vals])
+        H = to_limbs([int(x) for x in head])
+        sl = to_limbs([int(x) for x in sums]) if sums is not None else None
+        accept = ctypes.c_int(0)
+        layer, rnd, check = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+        self._check(N.lib().gkr_fraction_sum_verify(self._h, _ptr(num), _ptr(den), n, _ptr(sl) if sl is not None else None, _ptr(H), _ptr(C),
+                                                    _ptr(L), _ptr(R), _ptr(E), ctypes.byref(accept), ctypes.byref(layer), ctypes.byref(rnd),
+                                                    ctypes.byref(check)))
+        return int(check.value), int(layer.value), int(rnd.value)
+
     # -- the R1CS zero-check: Az, Bz, Cz of resident witnesses built on the device, then eq(z, .) (A B - C)
     def r1cs_rows(self, r1cs) -> R1csRows:
         """gkr_r1cs_rows_prepare: the CSR form of `r1cs` (convert.R1cs) resident on this context's device."""
@@ -1272,6 +1370,10 @@ def prove_zerocheck(tables, terms, z, v):
 
 def prove_grand_product(table, v):
     return default_context().prove_grand_product(table, v)
+
+
+def prove_fraction_sum(numerators, denominators, v):
+    return default_context().prove_fraction_sum(numerators, denominators, v)
 
 
 def prove_r1cs_zerocheck(r1cs, witness, z):

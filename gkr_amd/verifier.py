@@ -370,6 +370,75 @@ def verify_grand_product(head: List[int], layers, table=None, product=None):
     return 0, 0, 0
 
 
+def fraction_root(head: List[int]):
+    """(P, Q) of a fractional sum's head p_2[0..3], q_2[0..3] by the tree rule: level 2 -> level 1 -> level 0."""
+    p, q = head[:4], head[4:]
+    p1 = [(p[i] * q[i + 2] + p[i + 2] * q[i]) % P for i in range(2)]
+    q1 = [q[i] * q[i + 2] % P for i in range(2)]
+    return (p1[0] * q1[1] + p1[1] * q1[0]) % P, q1[0] * q1[1] % P
+
+
+def verify_fraction_sum(head: List[int], layers, numerators=None, denominators=None, sums=None):
+    """The verifier of a fractional sum (LogUp) proof (Context.prove_fraction_sum) on plain integers: what
+    Context.verify_fraction_sum_batch_device decides on the device.  head: p_2 then q_2, eight values; layers[k - 2] = (rounds,
+    challenges, (a0, a1, b0, b1)) of the zero-check of layer k = 2 .. n - 1; numerators, denominators: the 2^n values N and D, or
+    both None (the last claims cp_n = N~(z^(n)), cq_n = D~(z^(n)) are then the caller's to settle); sums: the claimed (P, Q), or
+    None.  Proof elements are taken as they are: one outside 0 .. r - 1 is NON_CANONICAL.  -> (check, layer, round) of the first
+    failure, (0, 0, 0) for an accepted proof:
+      SHAPE             a round vector of layer k, round j, with a length outside 1 .. 4: at (k, j);
+      NON_CANONICAL     a head entry or a claimed sum at (0, 0); else the first layer k with a round's coefficients or challenge
+                        at (k, j), or one of its four values at (k, k);
+      ZERO_DENOMINATOR  the head's Q (fraction_root) is 0: at (0, 0);
+      FRACTION_SUM      sums != the head's (P, Q), as a pair: at (0, 0);
+      per layer k, with zeta_1 = multi_hash(head, 0), zeta_2 = multi_hash([zeta_1], 0), z^(2) = (zeta_1, zeta_2),
+                        lambda_2 = multi_hash([zeta_2], 0), cp_2 = p_2~(z^(2)), cq_2 = q_2~(z^(2)): ROUND_SUM then CHALLENGE round
+                        by round against cp_k + lambda_k cq_k at (k, j); FINAL_CLAIM at (k, k) for
+                        g_k(r_k) != eq(z^(k), r^(k)) (a0 b1 + a1 b0 + lambda_k b0 b1); then tau_k = multi_hash([a0, a1, b0, b1], 0),
+                        cp_{k+1} = a0 + tau_k (a1 - a0), cq_{k+1} = b0 + tau_k (b1 - b0), z^(k+1) = (tau_k, r^(k)_1 .. r^(k)_k),
+                        lambda_{k+1} = multi_hash([tau_k], 0);
+      EVALUATION        with tables: cp_n != N~(z^(n)) or cq_n != D~(z^(n)): at (n, n)."""
+    n = len(layers) + 2
+    if len(head) != 8 or any(len(lay) != 3 or len(lay[0]) != k or len(lay[1]) != k or len(lay[2]) != 4 for k, lay in enumerate(layers, start=2)):
+        raise ValueError("eight head values and, for layer k = 2 .., k round vectors, k challenges and four values expected")
+    if (numerators is None) != (denominators is None) or (sums is not None and len(sums) != 2):
+        raise ValueError("both tables or neither, and two claimed sums or None expected")
+    for k, (rounds, _, _) in enumerate(layers, start=2):
+        for j, g in enumerate(rounds):
+            if not 1 <= len(g) <= 4:
+                return N.GKR_VERIFY_SHAPE, k, j
+    if any(not 0 <= h < P for h in head) or (sums is not None and any(not 0 <= s < P for s in sums)):
+        return N.GKR_VERIFY_NON_CANONICAL, 0, 0
+    for k, (rounds, challenges, vals) in enumerate(layers, start=2):
+        bad = _transcript_form(rounds, challenges, 4, vals)
+        if bad is not None:
+            return bad[1], k, bad[0]
+    root = fraction_root(head)
+    if root[1] == 0:
+        return N.GKR_VERIFY_ZERO_DENOMINATOR, 0, 0
+    if sums is not None and tuple(sums) != root:
+        return N.GKR_VERIFY_FRACTION_SUM, 0, 0
+    z = [multi_hash(head, 0)]
+    z.append(multi_hash([z[0]], 0))
+    lam = multi_hash([z[1]], 0)
+    cp, cq = mle_eval(head[:4], z), mle_eval(head[4:], z)
+    for k, (rounds, challenges, (a0, a1, b0, b1)) in enumerate(layers, start=2):
+        bad, last = _transcript_rounds(rounds, challenges, cp + lam * cq)
+        if bad is not None:
+            return bad[1], k, bad[0]
+        eq_r = 1
+        for zj, rj in zip(z, challenges):
+            eq_r = eq_r * (zj * rj + (1 - zj) * (1 - rj)) % P
+        if last != eq_r * (a0 * b1 + a1 * b0 + lam * b0 % P * b1) % P:
+            return N.GKR_VERIFY_FINAL_CLAIM, k, k
+        tau = multi_hash([a0, a1, b0, b1], 0)
+        cp, cq = (a0 + tau * (a1 - a0)) % P, (b0 + tau * (b1 - b0)) % P
+        z = [tau] + list(challenges)
+        lam = multi_hash([tau], 0)
+    if numerators is not None and (cp != mle_eval(numerators, z) or cq != mle_eval(denominators, z)):
+        return N.GKR_VERIFY_EVALUATION, n, n
+    return 0, 0, 0
+
+
 def verify(proof: Proof, circuit: GKRCircuit) -> bool:
     """python/gkr.py:202-231 on the Rust-shaped proof."""
     L = circuit.depth()

@@ -537,7 +537,8 @@ int gkr_sumcheck_mle_verify(gkr_ctx *ctx, const gkr_fr *table, int n, const gkr_
                             const uint32_t *len, const gkr_fr *r, int *accept, uint32_t *failed_round, uint32_t *failed_check);
 
 /* ---- GRAND PRODUCT: P = prod_i V[i] over a resident table, proven as GKR on the binary tree of multiplication gates ----
- * Permutation, multiset-equality, memory-checking and lookup arguments rest on it.  `batch` independent tables of 2^n canonical
+ * Permutation and multiset-equality arguments rest on it (lookups with multiplicities and batched memory checks rest on the
+ * FRACTIONAL SUM below).  `batch` independent tables of 2^n canonical
  * values, table b at d_tables + b * 2^n elements, variable 1 = the most significant index bit; 3 <= n <= GKR_MAX_MLE_N,
  * batch in 1 .. 65535, batch * 2^n <= 2^30.  The reference has no such argument; the protocol is the library's own:
  *   tree     L_n = V;  L_k[i] = L_{k+1}[i] * L_{k+1}[i + 2^k] mod r  for k = n-1 .. 0, i < 2^k;  P = L_0[0].  One launch per level
@@ -615,6 +616,93 @@ int  gkr_devtest_grand_product_tree(gkr_ctx *ctx, const void *d_tables, int n, i
  * (verify_workspace_mb, and mle_eval_mfma_min_n through the evaluation's workspace): *out = min(what fits, 32768, batch), at
  * least 1; the last chunk takes what is left.  No device work.  The argument checks of gkr_grand_product_verify_batch_device. */
 int  gkr_devtest_grand_product_chunk(gkr_ctx *ctx, int n, int batch, uint32_t *out);
+
+/* ---- FRACTIONAL SUM (LogUp): sum_i N[i] / D[i] = P / Q over a resident pair of tables, proven as GKR on the tree of fraction additions ----
+ * Lookups with multiplicities and batched memory checks rest on it.  `batch` independent pairs of tables N (numerators) and D
+ * (denominators) of 2^n canonical values each, pair b at d_tables + (2 b) * 2^n (N) and + (2 b + 1) * 2^n (D) elements, variable 1 =
+ * the most significant index bit; 3 <= n <= GKR_MAX_MLE_N, batch in 1 .. 65535, batch * 2^(n+1) <= 2^30 (the zero-check's own limit
+ * on the top layer's four tables).  The reference has no such argument; the protocol is the library's own:
+ *   tree     (p_n, q_n) = (N, D);  for k = n-1 .. 0, i < 2^k, with lo = i, hi = i + 2^k in level k+1:
+ *                p_k[i] = p_{k+1}[lo] q_{k+1}[hi] + p_{k+1}[hi] q_{k+1}[lo],   q_k[i] = q_{k+1}[lo] q_{k+1}[hi];
+ *            (P, Q) = (p_0[0], q_0[0]) and sum_i N[i] / D[i] = P / Q.  Nothing is inverted.  One launch per level
+ *            (csrc/kernels_fraction_sum.hip) stores every level, canonical, in context workspace in the input's own layout: level k
+ *            of pair b is p_k (2^k) then q_k (2^k).  The four tables of layer k's sumcheck, T0 = p lo half, T1 = p hi half,
+ *            T2 = q lo half, T3 = q hi half of level k+1, lie at (4 b + m) 2^k in place: nothing is gathered or copied.
+ *   head     the proof opens with level 2: p_2[0..3], q_2[0..3] (8 values); (P, Q) follow from them by the tree rule.
+ *            zeta_1 = multi_hash(those 8 values, key 0), zeta_2 = multi_hash([zeta_1], key 0), z^(2) = (zeta_1, zeta_2),
+ *            lambda_2 = multi_hash([zeta_2], key 0), cp_2 = p_2~(z^(2)), cq_2 = q_2~(z^(2)).
+ *   layer k  = 2 .. n-1:  the zero-check at z^(k) of g = T0 T3 + T1 T2 + lambda_k T2 T3 (terms {2,{0,3}}, {2,{1,2}}, {2,{2,3}},
+ *            coefficients 1, 1, lambda_k), claimed sum cp_k + lambda_k cq_k.  It yields k round vectors in rows of 4 slots, their
+ *            lengths, the challenges r^(k), the four values (a0, a1, b0, b1) = T0..T3~(r^(k)) and eq(z^(k), r^(k)) -- byte for byte
+ *            what gkr_sumcheck_zerocheck_batch_device returns with batch 1 on that pair's four tables with those coefficients and
+ *            that point.  Then tau_k = multi_hash([a0, a1, b0, b1], key 0), cp_{k+1} = a0 + tau_k (a1 - a0),
+ *            cq_{k+1} = b0 + tau_k (b1 - b0), z^(k+1) = (tau_k, r^(k)_1 .. r^(k)_k), lambda_{k+1} = multi_hash([tau_k], key 0).
+ *   end      cp_n = N~(z^(n)) and cq_n = D~(z^(n)), which the verifier evaluates itself (no commitment, as elsewhere).
+ * R = n (n - 1) / 2 - 1 rounds in all, layer k's rows from row k (k - 1) / 2 - 1 on: the grand product's bookkeeping.
+ *   out_sums      batch x 2 values (P, Q)                         out_head    batch x 8 values p_2, q_2
+ *   out_coeffs    batch x R rows of 4 slots, layers k = 2 .. n-1   out_len     batch x R values in 1 .. 4
+ *   out_r         batch x R challenges                            out_evals   batch x (n - 2) x 4 values (a0, a1, b0, b1), or NULL
+ *   out_point     batch x n coordinates z^(n), or NULL            out_claims  batch x 2 values (cp_n, cq_n), or NULL
+ * zeta, tau, lambda and the claims are formed on the host between the layers; the rows are hashed on the device by the round
+ * kernel, which reads the layer's lambda per proof (the zero-check's coefficients are one kernel argument for a whole batch).  A
+ * D with a zero entry makes Q = 0: the prover still runs and stays exact, the verifier rejects (GKR_VERIFY_ZERO_DENOMINATOR).  A
+ * layer whose g vanishes identically returns every vector as [0] with length 1 (the zero-check's own rule).  Inputs are not
+ * modified.  The tree (2 batch (2^n - 1) elements) and the layers' buffers live in context workspace under slot names of this
+ * path's own (fs.*): a zero-check, SOP, product or grand-product call on the same context is unaffected.
+ * GKR_ERR_INVALID before a device or the context is touched (plain returns): NULL ctx or pointer (the three optional outputs
+ * excepted), batch outside 1 .. 65535, n outside 3 .. GKR_MAX_MLE_N, batch * 2^(n+1) above 2^30 values. */
+int  gkr_fraction_sum_batch_device(gkr_ctx *ctx, const void *d_tables, int n, int batch, gkr_fr *out_sums, gkr_fr *out_head,
+                                   gkr_fr *out_coeffs, uint32_t *out_len, gkr_fr *out_r, gkr_fr *out_evals /* or NULL */,
+                                   gkr_fr *out_point /* or NULL */, gkr_fr *out_claims /* or NULL */);
+
+/* one pair of tables of 2^n values each in host memory: upload + the call above with batch 1.  GKR_ERR_NON_CANONICAL (through
+ * the context) for an entry >= r. */
+int  gkr_fraction_sum(gkr_ctx *ctx, const gkr_fr *numerators, const gkr_fr *denominators, int n, gkr_fr *out_sum, gkr_fr *out_head,
+                      gkr_fr *out_coeffs, uint32_t *out_len, gkr_fr *out_r, gkr_fr *out_evals, gkr_fr *out_point, gkr_fr *out_claims);
+
+/* Verifier of gkr_fraction_sum_batch_device's proofs against the resident pairs.  head / coeffs / len / r / evals: exactly the
+ * arrays and layout of the prover (evals is required here); sums: batch x 2 claimed values (P, Q), or NULL (the head's own root is
+ * then what the proof proves; out_sums returns it).  Built from the pieces of the grand product's verifier: the round relations
+ * of every layer run on host threads (csrc/verify_rounds.h, csrc/fraction_sum_rounds.h), the round vectors' hashes on the device
+ * from verify_device_hash_min round vectors on, else on the host threads (zeta, tau and lambda always on the host), and N and D
+ * are read ONCE on the device, both at the one point z^(n) (gkr_mle_eval_batch_device's kernels, groups of two tables).
+ * accept[batch] required; failed_layer / failed_round / failed_check (batch each) and out_sums (batch x 2) may be NULL.
+ * Per proof, in this order, the first failure reported (failed_check, at failed_layer, failed_round):
+ *   1. GKR_VERIFY_SHAPE             some len outside 1 .. 4; at (k, j) of the first such row
+ *   2. GKR_VERIFY_NON_CANONICAL     an element >= r (unused slots are never read): a head entry or a claimed sum at (0, 0); else the
+ *                                   first layer k with such an element: a used slot or a challenge of row j at (k, j), else one
+ *                                   of its four values at (k, k)
+ *   3. GKR_VERIFY_ZERO_DENOMINATOR  the head's Q is 0; at (0, 0).  Always checked
+ *   4. GKR_VERIFY_FRACTION_SUM      with sums: (P, Q) claimed != the head's root, as a pair; at (0, 0)
+ *   5. for k = 2 .. n-1, with the running claim cp_k + lambda_k cq_k:  for j = 0 .. k-1  GKR_VERIFY_ROUND_SUM, GKR_VERIFY_CHALLENGE
+ *      at (k, j), in the order of the sumcheck verifiers;  then  GKR_VERIFY_FINAL_CLAIM
+ *      g_k(r_k) != eq(z^(k), r^(k)) (a0 b1 + a1 b0 + lambda_k b0 b1)  at (k, k)
+ *   6. GKR_VERIFY_EVALUATION        cp_n != N~(z^(n)) or cq_n != D~(z^(n)); at (n, n)
+ * An accepted proof reports (0, 0, 0).  out_sums[b]: the head's root for every proof that passes checks 1 and 2, zeros for the
+ * others.  Table entries are read as integers modulo r.  The return value is the status of the CALL, not the verdict;
+ * GKR_ERR_INVALID before a device or the context is touched (plain returns): NULL ctx or required pointer and every shape the
+ * prover refuses.  Chunks hold min(what fits verify_workspace_mb, 32768, batch) proofs; verdicts depend neither on
+ * verify_workspace_mb nor on verify_device_hash_min. */
+int  gkr_fraction_sum_verify_batch_device(gkr_ctx *ctx, const void *d_tables, int n, int batch, const gkr_fr *sums /* or NULL */,
+                                          const gkr_fr *head, const gkr_fr *coeffs, const uint32_t *len, const gkr_fr *r,
+                                          const gkr_fr *evals, int *accept, uint32_t *failed_layer, uint32_t *failed_round,
+                                          uint32_t *failed_check, gkr_fr *out_sums /* or NULL */);
+
+/* one pair in host memory: upload + the call above with batch 1.  GKR_ERR_NON_CANONICAL for an entry >= r. */
+int  gkr_fraction_sum_verify(gkr_ctx *ctx, const gkr_fr *numerators, const gkr_fr *denominators, int n, const gkr_fr *sum /* 2, or NULL */,
+                             const gkr_fr *head, const gkr_fr *coeffs, const uint32_t *len, const gkr_fr *r, const gkr_fr *evals,
+                             int *accept, uint32_t *failed_layer, uint32_t *failed_round, uint32_t *failed_check);
+
+/* the launch geometry of the tree (host logic, from the function the launches call): one launch per level k = n-1 .. 0,
+ * blocks[k] = its blocks of 256 threads per pair, ceil(2^k / 256), a thread per node (k = 0 .. n-1: n words).
+ * GKR_ERR_INVALID: NULL pointer, n outside 3 .. GKR_MAX_MLE_N. */
+int  gkr_selftest_fraction_sum_geometry(int n, uint32_t *blocks);
+/* The tree alone, into the CALLER's device buffer instead of the context's workspace: d_layers takes 2 batch (2^n - 1) elements,
+ * level k of pair b (p_k then q_k) at 2 batch (2^k - 1) + b 2^(k+1).  The argument checks of gkr_fraction_sum_batch_device. */
+int  gkr_devtest_fraction_sum_tree(gkr_ctx *ctx, const void *d_tables, int n, int batch, void *d_layers);
+/* The proofs per chunk gkr_fraction_sum_verify_batch_device works through for (n, batch) under the context's options: *out =
+ * min(what fits, 32768, batch), at least 1.  No device work.  The argument checks of gkr_fraction_sum_verify_batch_device. */
+int  gkr_devtest_fraction_sum_chunk(gkr_ctx *ctx, int n, int batch, uint32_t *out);
 
 /* ---- GKR layer sumcheck: prove_sumcheck_opt, sumcheck.rs:36-44 ----------- */
 /* Layer i has 2^k_i gates; gate g is add (0) or mult (1) of entries left[g],
@@ -918,7 +1006,9 @@ enum {
                                       gkr_r1cs_verify*: g_n(r_n) != the transcript's own evaluations combined */
     GKR_VERIFY_MATRIX = 11,        /* gkr_r1cs_verify*: e_T != sum_m rho_m M_m~(r_x, r_y) from the public matrices */
     GKR_VERIFY_WITNESS = 12,       /* gkr_r1cs_verify* with a witness: e_w != w~(r_y) */
-    GKR_VERIFY_PRODUCT = 13        /* gkr_grand_product_verify* with claimed products: a claim != the product of the proof's head */
+    GKR_VERIFY_PRODUCT = 13,       /* gkr_grand_product_verify* with claimed products: a claim != the product of the proof's head */
+    GKR_VERIFY_ZERO_DENOMINATOR = 14,  /* gkr_fraction_sum_verify*: the head's Q is 0 -- the sum P / Q is undefined */
+    GKR_VERIFY_FRACTION_SUM = 15   /* gkr_fraction_sum_verify* with claimed sums: a claimed (P, Q) != the root of the proof's head */
 };
 int  gkr_verify(const gkr_circuit_desc *circuit, const gkr_proof_buf *proof, int threads, int *accept, uint32_t *failed_layer,
                 uint32_t *failed_check);
