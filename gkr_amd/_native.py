@@ -203,38 +203,22 @@ def lib():
         # the eq-table builder: (ctx, z, n, batch, d_out, stride_elements)
         L.gkr_eq_table_device.restype = ctypes.c_int
         L.gkr_eq_table_device.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p, ctypes.c_size_t]
-        # the grand product: (ctx, tables, n[, batch], out_products, out_head, out_coeffs, out_len, out_r, out_evals, out_point, out_claim)
-        L.gkr_grand_product_batch_device.restype = ctypes.c_int
-        L.gkr_grand_product_batch_device.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 8
-        L.gkr_grand_product.restype = ctypes.c_int
-        L.gkr_grand_product.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 8
-        # its verifier: (ctx, tables, n[, batch], products, head, coeffs, len, r, evals, accept, failed_layer, failed_round, failed_check
-        # [, out_products])
-        L.gkr_grand_product_verify_batch_device.restype = ctypes.c_int
-        L.gkr_grand_product_verify_batch_device.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 11
-        L.gkr_grand_product_verify.restype = ctypes.c_int
-        L.gkr_grand_product_verify.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 10
-        # (n, blocks[n]); (ctx, tables, n, batch, d_layers); (ctx, n, batch, out)
-        L.gkr_selftest_grand_product_geometry.restype = ctypes.c_int
-        L.gkr_selftest_grand_product_geometry.argtypes = [ctypes.c_int, ctypes.c_void_p]
-        L.gkr_devtest_grand_product_tree.restype = ctypes.c_int
-        L.gkr_devtest_grand_product_tree.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p]
-        L.gkr_devtest_grand_product_chunk.restype = ctypes.c_int
-        L.gkr_devtest_grand_product_chunk.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 2 + [ctypes.c_void_p]
-        L.gkr_fraction_sum_batch_device.restype = ctypes.c_int
-        L.gkr_fraction_sum_batch_device.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 8
-        L.gkr_fraction_sum.restype = ctypes.c_int
-        L.gkr_fraction_sum.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] + [ctypes.c_void_p] * 8
-        L.gkr_fraction_sum_verify_batch_device.restype = ctypes.c_int
-        L.gkr_fraction_sum_verify_batch_device.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 11
-        L.gkr_fraction_sum_verify.restype = ctypes.c_int
-        L.gkr_fraction_sum_verify.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] + [ctypes.c_void_p] * 10
-        L.gkr_selftest_fraction_sum_geometry.restype = ctypes.c_int
-        L.gkr_selftest_fraction_sum_geometry.argtypes = [ctypes.c_int, ctypes.c_void_p]
-        L.gkr_devtest_fraction_sum_tree.restype = ctypes.c_int
-        L.gkr_devtest_fraction_sum_tree.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p]
-        L.gkr_devtest_fraction_sum_chunk.restype = ctypes.c_int
-        L.gkr_devtest_fraction_sum_chunk.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 2 + [ctypes.c_void_p]
+        # the tree arguments, the grand product (one host table) and the fractional sum (two: numerators, denominators):
+        #   (ctx, tables, n[, batch], out_root, out_head, out_coeffs, out_len, out_r, out_evals, out_point, out_claims)
+        #   their verifiers: (ctx, tables, n[, batch], claimed, head, coeffs, len, r, evals, accept, failed_layer, failed_round,
+        #   failed_check[, out_root]);  (n, blocks[n]); (ctx, tables, n, batch, d_layers); (ctx, n, batch, out)
+        # the host-table forms differ in the number of leading pointers
+        for name, host_tables in (("grand_product", 1), ("fraction_sum", 2)):
+            for fn, argtypes in (
+                    ("gkr_%s_batch_device", [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 8),
+                    ("gkr_%s", [ctypes.c_void_p] * (1 + host_tables) + [ctypes.c_int] + [ctypes.c_void_p] * 8),
+                    ("gkr_%s_verify_batch_device", [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 11),
+                    ("gkr_%s_verify", [ctypes.c_void_p] * (1 + host_tables) + [ctypes.c_int] + [ctypes.c_void_p] * 10),
+                    ("gkr_selftest_%s_geometry", [ctypes.c_int, ctypes.c_void_p]),
+                    ("gkr_devtest_%s_tree", [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p]),
+                    ("gkr_devtest_%s_chunk", [ctypes.c_void_p] + [ctypes.c_int] * 2 + [ctypes.c_void_p])):
+                getattr(L, fn % name).restype = ctypes.c_int
+                getattr(L, fn % name).argtypes = argtypes
         # the R1CS zero-check: the CSR form (host only), the resident handle, the rows, the zero-check on them
         L.gkr_r1cs_csr_info.restype = ctypes.c_int
         L.gkr_r1cs_csr_info.argtypes = [ctypes.c_void_p] * 2

@@ -1,6 +1,6 @@
 // The pieces every batch verifier builds a chunk of proofs from: capi_verify.hip (whole GKR proofs), capi_mle_verify.hip (the plain,
-// product and sum-of-products sumchecks), capi_r1cs_verify.hip, capi_grand_product.hip and capi_fraction_sum.hip.  All of them
-// follow one plan per chunk --
+// product and sum-of-products sumchecks), capi_r1cs_verify.hip and tree_argument.h's one chunk verifier of the grand product and
+// the fractional sum (capi_grand_product.hip, capi_fraction_sum.hip).  All of them follow one plan per chunk --
 // hash the round vectors, on the side stream or on the host threads; run the relations that need neither a hash nor a device
 // value; read the tables once on the device; synchronise ONCE; decide a verdict per proof -- and each calls these pieces in an
 // order of its own, which is what its overlap of host and device rests on:

@@ -161,6 +161,16 @@ def _terms_from_coeffs(coeffs, k):
     return [[c] + [(m >> (k - 1 - j)) & 1 for j in range(k)] for m, c in enumerate(vals) if c]
 
 
+def _tree_rounds(n):
+    """R = n (n - 1) / 2 - 1: the rows of the layers k = 2 .. n - 1 of a tree argument (grand product, fractional sum) over 2^n leaves."""
+    return n * (n - 1) // 2 - 1
+
+
+def _tree_row(k):
+    """the first row of layer k"""
+    return k * (k - 1) // 2 - 1
+
+
 class VerifyHandle:
     """A circuit prepared for the device verifier (gkr_verify_prepare): its gate arrays live on the context's device until
     close().  Context.prepare_verify makes one; Context.verify_batch takes it any number of times."""
@@ -579,12 +589,85 @@ class Context:
         pts = self._points(z, batch, n)
         self._check(N.lib().gkr_eq_table_device(self._h, _ptr(pts), n, batch, d_out, (1 << n) if stride is None else int(stride)))
 
+    # -- the two GKR tree arguments, the grand product (W = 1 table per proof) and the fractional sum (W = 2): one plumbing for both.
+    # Every width follows from W: the head 4 W values, a layer's end values 2 W, the root and the end claims W (an axis of their
+    # own only for W > 1); R = _tree_rounds(n) rows, layer k from row _tree_row(k).
+    @staticmethod
+    def _tree_shapes(W, n, lead):
+        """The shapes of (root, H, C, L, R, E, Z, K) behind the leading axes `lead` -- (batch,), or () for one proof."""
+        rounds, vals = _tree_rounds(n), lead + ((4,) if W == 1 else (W, 4))
+        return [vals, lead + (4 * W, 4), lead + (rounds, 4, 4), lead + (rounds,), lead + (rounds, 4), lead + (n - 2, 2 * W, 4), lead + (n, 4), vals]
+
+    def _tree_batch_device(self, fn, W, d_tables, n, batch, out):
+        shapes = [(s, np.uint32 if i == 3 else np.uint64) for i, s in enumerate(self._tree_shapes(W, n, (batch,)))]
+        if n < 3 or batch < 1:
+            raise GkrError(N.GKR_ERR_INVALID, "n >= 3 and batch >= 1 expected")
+        if out is not None:
+            if len(out) != 8 or any(a.shape != s or a.dtype != d for a, (s, d) in zip(out, shapes)):
+                raise GkrError(N.GKR_ERR_INVALID, "output arrays do not match (batch, n)")
+        else:
+            out = tuple(np.zeros(s, dtype=d) for s, d in shapes)
+        self._check(fn(self._h, d_tables, n, batch, *(_ptr(a) for a in out)))
+        return out
+
+    def _tree_prove(self, fn, W, tables, v):
+        """fn(ctx, *tables, v, the eight outputs) -> (root, head, layers, point, claims) as lists of integers."""
+        shapes = self._tree_shapes(W, v, ())
+        shapes[0] = shapes[7] = (W, 4)                                     # (W values also where W = 1)
+        S, H, C, L, R, E, Z, K = (np.zeros(s, dtype=np.uint32 if i == 3 else np.uint64) for i, s in enumerate(shapes))
+        self._check(fn(self._h, *(_ptr(t) for t in tables), v, *(_ptr(a) for a in (S, H, C, L, R, E, Z, K))))
+        rs, layers = from_limbs(R), []
+        for k in range(2, v):
+            row = _tree_row(k)
+            layers.append(([from_limbs(C[row + j])[4 - int(L[row + j]):] for j in range(k)], rs[row:row + k], tuple(from_limbs(E[k - 2]))))
+        return from_limbs(S), from_limbs(H), layers, from_limbs(Z), from_limbs(K)
+
+    def _tree_verify_batch_device(self, fn, W, name, d_tables, n, batch, H, C, L, R, E, claimed):
+        shapes = self._tree_shapes(W, n, (batch,))
+        H, C, R, E = (np.ascontiguousarray(a, dtype=np.uint64) for a in (H, C, R, E))
+        L = np.ascontiguousarray(L, dtype=np.uint32)
+        if [a.shape for a in (H, C, L, R, E)] != shapes[1:6]:
+            raise GkrError(N.GKR_ERR_INVALID, "proof arrays do not match (batch, n)")
+        if claimed is not None:
+            claimed = np.ascontiguousarray(claimed, dtype=np.uint64)
+            if claimed.shape != shapes[0]:
+                raise GkrError(N.GKR_ERR_INVALID, "%s of shape (%s) expected" % (name, ", ".join(["batch"] + [str(x) for x in shapes[0][1:]])))
+        accept = np.zeros(batch, dtype=np.int32)
+        layer, rnd, check = (np.zeros(batch, dtype=np.uint32) for _ in range(3))
+        out = np.zeros(shapes[0], dtype=np.uint64)
+        self._check(fn(self._h, d_tables, n, batch, _ptr(claimed) if claimed is not None else None, _ptr(H), _ptr(C), _ptr(L), _ptr(R), _ptr(E),
+                       _ptr(accept), _ptr(layer), _ptr(rnd), _ptr(check), _ptr(out)))
+        return accept.astype(bool), layer, rnd, check, out
+
+    def _tree_verify(self, fn, W, tables, head, layers, claimed):
+        """fn(ctx, *tables, n, claimed or None, the proof, the verdict's four outputs) -> (check, layer, round)"""
+        n = len(layers) + 2
+        _, _, cs, ls, rs, es, _, _ = self._tree_shapes(W, n, ())
+        C, L, R, E = np.zeros(cs, dtype=np.uint64), np.zeros(ls, dtype=np.uint32), np.zeros(rs, dtype=np.uint64), np.zeros(es, dtype=np.uint64)
+        for k, (proof, r, vals) in enumerate(layers, start=2):
+            row = _tree_row(k)
+            if len(proof) != k or len(r) != k or len(vals) != 2 * W:
+                raise GkrError(N.GKR_ERR_INVALID, "layer k has k round vectors, k challenges and %s values" % ("two", "four")[W - 1])
+            for j, g in enumerate(proof):
+                L[row + j] = len(g)
+                if 1 <= len(g) <= 4:                                       # (another length: SHAPE, the slots are not read)
+                    C[row + j, 4 - len(g):] = to_limbs([int(c) for c in g])
+            R[row:row + k] = to_limbs([int(x) for x in r])
+            E[k - 2] = to_limbs([int(x) for x in vals])
+        H = to_limbs([int(x) for x in head])
+        cl = to_limbs([int(x) for x in claimed]) if claimed is not None else None
+        accept = ctypes.c_int(0)
+        layer, rnd, check = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+        self._check(fn(self._h, *(_ptr(t) for t in tables), n, _ptr(cl) if cl is not None else None, _ptr(H), _ptr(C), _ptr(L), _ptr(R), _ptr(E),
+                       ctypes.byref(accept), ctypes.byref(layer), ctypes.byref(rnd), ctypes.byref(check)))
+        return int(check.value), int(layer.value), int(rnd.value)
+
     # -- the grand product P = prod_i V[i]: the product tree on the device, a zero-check per layer, chained by Fiat-Shamir
     @staticmethod
     def grand_product_rounds(n):
         """R = n (n - 1) / 2 - 1: the rounds of the layers k = 2 .. n - 1 of a grand product over 2^n values; layer k's rows start
         at k (k - 1) / 2 - 1."""
-        return n * (n - 1) // 2 - 1
+        return _tree_rounds(n)
 
     def grand_product_batch_device(self, d_tables, n, batch, out=None):
         """gkr_grand_product_batch_device: `batch` grand products over resident tables of 2^n canonical values (table b at
@@ -593,18 +676,7 @@ class Context:
         R = grand_product_rounds(n); L (batch, R); R (batch, R, 4) the challenges; E (batch, n - 2, 2, 4) the layers' values
         (a_k, b_k); Z (batch, n, 4) the final point z^(n); K (batch, 4) the final claim c_n = V~(z^(n)).  Each layer is byte for
         byte sumcheck_zerocheck_batch_device on the two halves of the level below.  out: the eight arrays of an earlier call."""
-        rounds = self.grand_product_rounds(n)
-        shapes = [((batch, 4), np.uint64), ((batch, 4, 4), np.uint64), ((batch, rounds, 4, 4), np.uint64), ((batch, rounds), np.uint32),
-                  ((batch, rounds, 4), np.uint64), ((batch, n - 2, 2, 4), np.uint64), ((batch, n, 4), np.uint64), ((batch, 4), np.uint64)]
-        if n < 3 or batch < 1:
-            raise GkrError(N.GKR_ERR_INVALID, "n >= 3 and batch >= 1 expected")
-        if out is not None:
-            if len(out) != 8 or any(a.shape != s or a.dtype != d for a, (s, d) in zip(out, shapes)):
-                raise GkrError(N.GKR_ERR_INVALID, "output arrays do not match (batch, n)")
-        else:
-            out = tuple(np.zeros(s, dtype=d) for s, d in shapes)
-        self._check(N.lib().gkr_grand_product_batch_device(self._h, d_tables, n, batch, *(_ptr(a) for a in out)))
-        return out
+        return self._tree_batch_device(N.lib().gkr_grand_product_batch_device, 1, d_tables, n, batch, out)
 
     def prove_grand_product(self, table, v):
         """The grand product of a table of 2^v values (v >= 3) with its GKR proof.  -> (product, head, layers, point, claim):
@@ -614,75 +686,30 @@ class Context:
         limbs = as_limbs(table)
         if v < 3 or limbs.shape[0] != 1 << v:
             raise GkrError(N.GKR_ERR_INVALID, "a table of 2^v values, v >= 3, expected")
-        rounds = self.grand_product_rounds(v)
-        P, H = np.zeros((1, 4), dtype=np.uint64), np.zeros((4, 4), dtype=np.uint64)
-        C, L, R = np.zeros((rounds, 4, 4), dtype=np.uint64), np.zeros(rounds, dtype=np.uint32), np.zeros((rounds, 4), dtype=np.uint64)
-        E, Z, K = np.zeros((v - 2, 2, 4), dtype=np.uint64), np.zeros((v, 4), dtype=np.uint64), np.zeros((1, 4), dtype=np.uint64)
-        self._check(N.lib().gkr_grand_product(self._h, _ptr(limbs), v, _ptr(P), _ptr(H), _ptr(C), _ptr(L), _ptr(R), _ptr(E), _ptr(Z), _ptr(K)))
-        rs, layers = from_limbs(R), []
-        for k in range(2, v):
-            row = k * (k - 1) // 2 - 1
-            layers.append(([from_limbs(C[row + j])[4 - int(L[row + j]):] for j in range(k)], rs[row:row + k], tuple(from_limbs(E[k - 2]))))
-        return from_limbs(P)[0], from_limbs(H), layers, from_limbs(Z), from_limbs(K)[0]
+        P, head, layers, point, K = self._tree_prove(N.lib().gkr_grand_product, 1, (limbs,), v)
+        return P[0], head, layers, point, K[0]
 
     def verify_grand_product_batch_device(self, d_tables, n, batch, H, C, L, R, E, products=None):
         """gkr_grand_product_verify_batch_device on the resident tables and the arrays grand_product_batch_device returned (its H,
         C, L, R, E); products: (batch, 4) limbs of claimed products or None.  -> (accept (batch,) bool, failed_layer, failed_round,
         failed_check (batch,) uint32, products (batch, 4): the heads' own products).  verifier.verify_grand_product is the same
         verdict on plain integers."""
-        rounds = self.grand_product_rounds(n)
-        H, C, R, E = (np.ascontiguousarray(a, dtype=np.uint64) for a in (H, C, R, E))
-        L = np.ascontiguousarray(L, dtype=np.uint32)
-        if (H.shape != (batch, 4, 4) or C.shape != (batch, rounds, 4, 4) or L.shape != (batch, rounds) or R.shape != (batch, rounds, 4)
-                or E.shape != (batch, n - 2, 2, 4)):
-            raise GkrError(N.GKR_ERR_INVALID, "proof arrays do not match (batch, n)")
-        if products is not None:
-            products = np.ascontiguousarray(products, dtype=np.uint64)
-            if products.shape != (batch, 4):
-                raise GkrError(N.GKR_ERR_INVALID, "products of shape (batch, 4) expected")
-        accept = np.zeros(batch, dtype=np.int32)
-        layer, rnd, check = (np.zeros(batch, dtype=np.uint32) for _ in range(3))
-        out = np.zeros((batch, 4), dtype=np.uint64)
-        self._check(N.lib().gkr_grand_product_verify_batch_device(self._h, d_tables, n, batch, _ptr(products) if products is not None else None,
-                                                                  _ptr(H), _ptr(C), _ptr(L), _ptr(R), _ptr(E), _ptr(accept), _ptr(layer), _ptr(rnd),
-                                                                  _ptr(check), _ptr(out)))
-        return accept.astype(bool), layer, rnd, check, out
+        return self._tree_verify_batch_device(N.lib().gkr_grand_product_verify_batch_device, 1, "products", d_tables, n, batch, H, C, L, R, E, products)
 
     def verify_grand_product(self, table, head, layers, product=None):
         """gkr_grand_product_verify on a host table and what prove_grand_product returned (its head and layers; product: the claimed
         product or None).  -> (check, layer, round), (0, 0, 0) for an accepted proof: verifier.verify_grand_product's verdict."""
         limbs = as_limbs(table)
-        n = len(layers) + 2
-        if limbs.shape[0] != 1 << n or len(head) != 4:
+        if limbs.shape[0] != 1 << (len(layers) + 2) or len(head) != 4:
             raise GkrError(N.GKR_ERR_INVALID, "a table of 2^n values, four head values and n - 2 layers expected")
-        rounds = self.grand_product_rounds(n)
-        C, L, R = np.zeros((rounds, 4, 4), dtype=np.uint64), np.zeros(rounds, dtype=np.uint32), np.zeros((rounds, 4), dtype=np.uint64)
-        E = np.zeros((n - 2, 2, 4), dtype=np.uint64)
-        for k, (proof, r, ab) in enumerate(layers, start=2):
-            row = k * (k - 1) // 2 - 1
-            if len(proof) != k or len(r) != k or len(ab) != 2:
-                raise GkrError(N.GKR_ERR_INVALID, "layer k has k round vectors, k challenges and two values")
-            for j, g in enumerate(proof):
-                L[row + j] = len(g)
-                if 1 <= len(g) <= 4:                                       # (another length: SHAPE, the slots are not read)
-                    C[row + j, 4 - len(g):] = to_limbs([int(c) for c in g])
-            R[row:row + k] = to_limbs([int(x) for x in r])
-            E[k - 2] = to_limbs([int(x) for x in ab])
-        H = to_limbs([int(x) for x in head])
-        pl = to_limbs([int(product)]) if product is not None else None
-        accept = ctypes.c_int(0)
-        layer, rnd, check = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
-        self._check(N.lib().gkr_grand_product_verify(self._h, _ptr(limbs), n, _ptr(pl) if pl is not None else None, _ptr(H), _ptr(C), _ptr(L),
-                                                     _ptr(R), _ptr(E), ctypes.byref(accept), ctypes.byref(layer), ctypes.byref(rnd),
-                                                     ctypes.byref(check)))
-        return int(check.value), int(layer.value), int(rnd.value)
+        return self._tree_verify(N.lib().gkr_grand_product_verify, 1, (limbs,), head, layers, None if product is None else [product])
 
     # -- the fractional sum (LogUp) sum_i N[i] / D[i] = P / Q: the tree of fractions on the device, a zero-check per layer
     @staticmethod
     def fraction_sum_rounds(n):
         """R = n (n - 1) / 2 - 1: the rounds of the layers k = 2 .. n - 1 of a fractional sum over 2^n fractions; layer k's rows
         start at k (k - 1) / 2 - 1 (the grand product's bookkeeping)."""
-        return n * (n - 1) // 2 - 1
+        return _tree_rounds(n)
 
     def fraction_sum_batch_device(self, d_tables, n, batch, out=None):
         """gkr_fraction_sum_batch_device: `batch` fractional sums over resident pairs of tables of 2^n canonical values (pair b:
@@ -691,18 +718,7 @@ class Context:
         k = 2 .. n - 1 in order, R = fraction_sum_rounds(n); L (batch, R); R (batch, R, 4) the challenges; E (batch, n - 2, 4, 4) the
         layers' values (a0, a1, b0, b1); Z (batch, n, 4) the final point z^(n); K (batch, 2, 4) the final claims cp_n = N~(z^(n)),
         cq_n = D~(z^(n)).  out: the eight arrays of an earlier call."""
-        rounds = self.fraction_sum_rounds(n)
-        shapes = [((batch, 2, 4), np.uint64), ((batch, 8, 4), np.uint64), ((batch, rounds, 4, 4), np.uint64), ((batch, rounds), np.uint32),
-                  ((batch, rounds, 4), np.uint64), ((batch, n - 2, 4, 4), np.uint64), ((batch, n, 4), np.uint64), ((batch, 2, 4), np.uint64)]
-        if n < 3 or batch < 1:
-            raise GkrError(N.GKR_ERR_INVALID, "n >= 3 and batch >= 1 expected")
-        if out is not None:
-            if len(out) != 8 or any(a.shape != s or a.dtype != d for a, (s, d) in zip(out, shapes)):
-                raise GkrError(N.GKR_ERR_INVALID, "output arrays do not match (batch, n)")
-        else:
-            out = tuple(np.zeros(s, dtype=d) for s, d in shapes)
-        self._check(N.lib().gkr_fraction_sum_batch_device(self._h, d_tables, n, batch, *(_ptr(a) for a in out)))
-        return out
+        return self._tree_batch_device(N.lib().gkr_fraction_sum_batch_device, 2, d_tables, n, batch, out)
 
     def prove_fraction_sum(self, numerators, denominators, v):
         """The fractional sum of 2^v fractions N[i] / D[i] (v >= 3) with its GKR proof.  -> ((P, Q), head, layers, point, claims):
@@ -712,39 +728,15 @@ class Context:
         num, den = as_limbs(numerators), as_limbs(denominators)
         if v < 3 or num.shape[0] != 1 << v or den.shape[0] != 1 << v:
             raise GkrError(N.GKR_ERR_INVALID, "two tables of 2^v values, v >= 3, expected")
-        rounds = self.fraction_sum_rounds(v)
-        S, H = np.zeros((2, 4), dtype=np.uint64), np.zeros((8, 4), dtype=np.uint64)
-        C, L, R = np.zeros((rounds, 4, 4), dtype=np.uint64), np.zeros(rounds, dtype=np.uint32), np.zeros((rounds, 4), dtype=np.uint64)
-        E, Z, K = np.zeros((v - 2, 4, 4), dtype=np.uint64), np.zeros((v, 4), dtype=np.uint64), np.zeros((2, 4), dtype=np.uint64)
-        self._check(N.lib().gkr_fraction_sum(self._h, _ptr(num), _ptr(den), v, _ptr(S), _ptr(H), _ptr(C), _ptr(L), _ptr(R), _ptr(E), _ptr(Z), _ptr(K)))
-        rs, layers = from_limbs(R), []
-        for k in range(2, v):
-            row = k * (k - 1) // 2 - 1
-            layers.append(([from_limbs(C[row + j])[4 - int(L[row + j]):] for j in range(k)], rs[row:row + k], tuple(from_limbs(E[k - 2]))))
-        return tuple(from_limbs(S)), from_limbs(H), layers, from_limbs(Z), tuple(from_limbs(K))
+        S, head, layers, point, K = self._tree_prove(N.lib().gkr_fraction_sum, 2, (num, den), v)
+        return tuple(S), head, layers, point, tuple(K)
 
     def verify_fraction_sum_batch_device(self, d_tables, n, batch, H, C, L, R, E, sums=None):
         """gkr_fraction_sum_verify_batch_device on the resident pairs and the arrays fraction_sum_batch_device returned (its H, C,
         L, R, E); sums: (batch, 2, 4) limbs of claimed (P, Q) or None.  -> (accept (batch,) bool, failed_layer, failed_round,
         failed_check (batch,) uint32, sums (batch, 2, 4): the heads' own roots).  verifier.verify_fraction_sum is the same verdict
         on plain integers."""
-        rounds = self.fraction_sum_rounds(n)
-        H, C, R, E = (np.ascontiguousarray(a, dtype=np.uint64) for a in (H, C, R, E))
-        L = np.ascontiguousarray(L, dtype=np.uint32)
-        if (H.shape != (batch, 8, 4) or C.shape != (batch, rounds, 4, 4) or L.shape != (batch, rounds) or R.shape != (batch, rounds, 4)
-                or E.shape != (batch, n - 2, 4, 4)):
-            raise GkrError(N.GKR_ERR_INVALID, "proof arrays do not match (batch, n)")
-        if sums is not None:
-            sums = np.ascontiguousarray(sums, dtype=np.uint64)
-            if sums.shape != (batch, 2, 4):
-                raise GkrError(N.GKR_ERR_INVALID, "sums of shape (batch, 2, 4) expected")
-        accept = np.zeros(batch, dtype=np.int32)
-        layer, rnd, check = (np.zeros(batch, dtype=np.uint32) for _ in range(3))
-        out = np.zeros((batch, 2, 4), dtype=np.uint64)
-        self._check(N.lib().gkr_fraction_sum_verify_batch_device(self._h, d_tables, n, batch, _ptr(sums) if sums is not None else None,
-                                                                 _ptr(H), _ptr(C), _ptr(L), _ptr(R), _ptr(E), _ptr(accept), _ptr(layer), _ptr(rnd),
-                                                                 _ptr(check), _ptr(out)))
-        return accept.astype(bool), layer, rnd, check, out
+        return self._tree_verify_batch_device(N.lib().gkr_fraction_sum_verify_batch_device, 2, "sums", d_tables, n, batch, H, C, L, R, E, sums)
 
     def verify_fraction_sum(self, numerators, denominators, head, layers, sums=None):
         """gkr_fraction_sum_verify on host tables and what prove_fraction_sum returned (its head and layers; sums: the claimed (P, Q)
@@ -753,27 +745,7 @@ class Context:
         n = len(layers) + 2
         if num.shape[0] != 1 << n or den.shape[0] != 1 << n or len(head) != 8:
             raise GkrError(N.GKR_ERR_INVALID, "two tables of 2^n values, eight head values and n - 2 layers expected")
-        rounds = self.fraction_sum_rounds(n)
-        C, L, R = np.zeros((rounds, 4, 4), dtype=np.uint64), np.zeros(rounds, dtype=np.uint32), np.zeros((rounds, 4), dtype=np.uint64)
-        E = np.zeros((n - 2, 4, 4), dtype=np.uint64)
-        for k, (proof, r, vals) in enumerate(layers, start=2):
-            row = k * (k - 1) // 2 - 1
-            if len(proof) != k or len(r) != k or len(vals) != 4:
-                raise GkrError(N.GKR_ERR_INVALID, "layer k has k round vectors, k challenges and four values")
-            for j, g in enumerate(proof):
-                L[row + j] = len(g)
-                if 1 <= len(g) <= 4:                                       # (another length: SHAPE, the slots are not read)
-                    C[row + j, 4 - len(g):] = to_limbs([int(c) for c in g])
-            R[row:row + k] = to_limbs([int(x) for x in r])
-            E[k - 2] = to_limbs([int(x) for x in vals])
-        H = to_limbs([int(x) for x in head])
-        sl = to_limbs([int(x) for x in sums]) if sums is not None else None
-        accept = ctypes.c_int(0)
-        layer, rnd, check = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
-        self._check(N.lib().gkr_fraction_sum_verify(self._h, _ptr(num), _ptr(den), n, _ptr(sl) if sl is not None else None, _ptr(H), _ptr(C),
-                                                    _ptr(L), _ptr(R), _ptr(E), ctypes.byref(accept), ctypes.byref(layer), ctypes.byref(rnd),
-                                                    ctypes.byref(check)))
-        return int(check.value), int(layer.value), int(rnd.value)
+        return self._tree_verify(N.lib().gkr_fraction_sum_verify, 2, (num, den), head, layers, sums)
 
     # -- the R1CS zero-check: Az, Bz, Cz of resident witnesses built on the device, then eq(z, .) (A B - C)
     def r1cs_rows(self, r1cs) -> R1csRows:

@@ -320,6 +320,64 @@ def verify_r1cs(constraints, z: List[int], rho: List[int], zc_rounds: List[List[
     return 0, 0, 0
 
 
+class _TreeGate:
+    """What differs between the tree arguments (the C++ statement: csrc/tree_rounds.h and its gates): W tables per proof -- head
+    4 W values, table w at [4 w, 4 w + 4); a layer's 2 W values, the halves of table w at 2 w, 2 w + 1 --, whether a lambda is
+    drawn per layer, the zero-check's claim and the gate on a layer's values, form(head, claimed) -> the first failed check of
+    the head or 0, and the text for a proof of another shape."""
+
+    def __init__(self, W, draws_lambda, claim, gate, form, expected):
+        self.W, self.draws_lambda, self.claim, self.gate, self.form, self.expected = W, draws_lambda, claim, gate, form, expected
+
+
+def _verify_tree(head: List[int], layers, gate: _TreeGate, tables, claimed):
+    """The one chain of both tree arguments: tables: the W input tables or None; claimed: the W claimed root values or None.
+    -> (check, layer, round) as verify_grand_product and verify_fraction_sum document it."""
+    n, W = len(layers) + 2, gate.W
+    if len(head) != 4 * W or any(len(lay) != 3 or len(lay[0]) != k or len(lay[1]) != k or len(lay[2]) != 2 * W
+                                 for k, lay in enumerate(layers, start=2)):
+        raise ValueError(gate.expected)
+    for k, (rounds, _, _) in enumerate(layers, start=2):
+        for j, g in enumerate(rounds):
+            if not 1 <= len(g) <= 4:
+                return N.GKR_VERIFY_SHAPE, k, j
+    if any(not 0 <= h < P for h in head) or (claimed is not None and any(not 0 <= s < P for s in claimed)):
+        return N.GKR_VERIFY_NON_CANONICAL, 0, 0
+    for k, (rounds, challenges, vals) in enumerate(layers, start=2):
+        bad = _transcript_form(rounds, challenges, 4, vals)
+        if bad is not None:
+            return bad[1], k, bad[0]
+    check = gate.form(head, claimed)
+    if check:
+        return check, 0, 0
+    z = [multi_hash(head, 0)]
+    z.append(multi_hash([z[0]], 0))
+    lam = multi_hash([z[1]], 0) if gate.draws_lambda else 0
+    claims = [mle_eval(head[4 * w:4 * w + 4], z) for w in range(W)]
+    for k, (rounds, challenges, vals) in enumerate(layers, start=2):
+        bad, last = _transcript_rounds(rounds, challenges, gate.claim(claims, lam))
+        if bad is not None:
+            return bad[1], k, bad[0]
+        eq_r = 1
+        for zj, rj in zip(z, challenges):
+            eq_r = eq_r * (zj * rj + (1 - zj) * (1 - rj)) % P
+        if last != eq_r * gate.gate(vals, lam) % P:
+            return N.GKR_VERIFY_FINAL_CLAIM, k, k
+        tau = multi_hash(list(vals), 0)
+        claims = [(vals[2 * w] + tau * (vals[2 * w + 1] - vals[2 * w])) % P for w in range(W)]
+        z = [tau] + list(challenges)
+        lam = multi_hash([tau], 0) if gate.draws_lambda else 0
+    if tables is not None and any(c != mle_eval(t, z) for c, t in zip(claims, tables)):
+        return N.GKR_VERIFY_EVALUATION, n, n
+    return 0, 0, 0
+
+
+_GRAND_PRODUCT = _TreeGate(
+    1, False, lambda c, lam: c[0], lambda v, lam: v[0] * v[1] % P,
+    lambda head, claimed: N.GKR_VERIFY_PRODUCT if claimed is not None and claimed[0] != head[0] * head[1] % P * head[2] % P * head[3] % P else 0,
+    "four head values and, for layer k = 2 .., k round vectors, k challenges and two values expected")
+
+
 def verify_grand_product(head: List[int], layers, table=None, product=None):
     """The verifier of a grand product proof (Context.prove_grand_product) on plain integers: what
     Context.verify_grand_product_batch_device decides on the device.  head: L_2, four values; layers[k - 2] = (rounds, challenges,
@@ -335,39 +393,7 @@ def verify_grand_product(head: List[int], layers, table=None, product=None):
                      g_k(r_k) != eq(z^(k), r^(k)) a_k b_k; then tau_k = multi_hash([a_k, b_k], 0), c_{k+1} = a_k + tau_k (b_k - a_k),
                      z^(k+1) = (tau_k, r^(k)_1 .. r^(k)_k);
       EVALUATION     with a table: c_n != V~(z^(n)): at (n, n)."""
-    n = len(layers) + 2
-    if len(head) != 4 or any(len(lay) != 3 or len(lay[0]) != k or len(lay[1]) != k or len(lay[2]) != 2 for k, lay in enumerate(layers, start=2)):
-        raise ValueError("four head values and, for layer k = 2 .., k round vectors, k challenges and two values expected")
-    for k, (rounds, _, _) in enumerate(layers, start=2):
-        for j, g in enumerate(rounds):
-            if not 1 <= len(g) <= 4:
-                return N.GKR_VERIFY_SHAPE, k, j
-    if any(not 0 <= h < P for h in head) or (product is not None and not 0 <= product < P):
-        return N.GKR_VERIFY_NON_CANONICAL, 0, 0
-    for k, (rounds, challenges, ab) in enumerate(layers, start=2):
-        bad = _transcript_form(rounds, challenges, 4, ab)
-        if bad is not None:
-            return bad[1], k, bad[0]
-    if product is not None and product != head[0] * head[1] % P * head[2] % P * head[3] % P:
-        return N.GKR_VERIFY_PRODUCT, 0, 0
-    z = [multi_hash(head, 0)]
-    z.append(multi_hash([z[0]], 0))
-    claim = mle_eval(head, z)
-    for k, (rounds, challenges, (a, b)) in enumerate(layers, start=2):
-        bad, last = _transcript_rounds(rounds, challenges, claim)
-        if bad is not None:
-            return bad[1], k, bad[0]
-        eq_r = 1
-        for zj, rj in zip(z, challenges):
-            eq_r = eq_r * (zj * rj + (1 - zj) * (1 - rj)) % P
-        if last != eq_r * a % P * b % P:
-            return N.GKR_VERIFY_FINAL_CLAIM, k, k
-        tau = multi_hash([a, b], 0)
-        claim = (a + tau * (b - a)) % P
-        z = [tau] + list(challenges)
-    if table is not None and claim != mle_eval(table, z):
-        return N.GKR_VERIFY_EVALUATION, n, n
-    return 0, 0, 0
+    return _verify_tree(head, layers, _GRAND_PRODUCT, None if table is None else [table], None if product is None else [product])
 
 
 def fraction_root(head: List[int]):
@@ -376,6 +402,18 @@ def fraction_root(head: List[int]):
     p1 = [(p[i] * q[i + 2] + p[i + 2] * q[i]) % P for i in range(2)]
     q1 = [q[i] * q[i + 2] % P for i in range(2)]
     return (p1[0] * q1[1] + p1[1] * q1[0]) % P, q1[0] * q1[1] % P
+
+
+def _fraction_form(head, claimed):
+    root = fraction_root(head)
+    if root[1] == 0:
+        return N.GKR_VERIFY_ZERO_DENOMINATOR
+    return N.GKR_VERIFY_FRACTION_SUM if claimed is not None and tuple(claimed) != root else 0
+
+
+_FRACTION_SUM = _TreeGate(
+    2, True, lambda c, lam: c[0] + lam * c[1], lambda v, lam: v[0] * v[3] + v[1] * v[2] + lam * v[2] % P * v[3], _fraction_form,
+    "eight head values and, for layer k = 2 .., k round vectors, k challenges and four values expected")
 
 
 def verify_fraction_sum(head: List[int], layers, numerators=None, denominators=None, sums=None):
@@ -397,46 +435,9 @@ def verify_fraction_sum(head: List[int], layers, numerators=None, denominators=N
                         cp_{k+1} = a0 + tau_k (a1 - a0), cq_{k+1} = b0 + tau_k (b1 - b0), z^(k+1) = (tau_k, r^(k)_1 .. r^(k)_k),
                         lambda_{k+1} = multi_hash([tau_k], 0);
       EVALUATION        with tables: cp_n != N~(z^(n)) or cq_n != D~(z^(n)): at (n, n)."""
-    n = len(layers) + 2
-    if len(head) != 8 or any(len(lay) != 3 or len(lay[0]) != k or len(lay[1]) != k or len(lay[2]) != 4 for k, lay in enumerate(layers, start=2)):
-        raise ValueError("eight head values and, for layer k = 2 .., k round vectors, k challenges and four values expected")
     if (numerators is None) != (denominators is None) or (sums is not None and len(sums) != 2):
         raise ValueError("both tables or neither, and two claimed sums or None expected")
-    for k, (rounds, _, _) in enumerate(layers, start=2):
-        for j, g in enumerate(rounds):
-            if not 1 <= len(g) <= 4:
-                return N.GKR_VERIFY_SHAPE, k, j
-    if any(not 0 <= h < P for h in head) or (sums is not None and any(not 0 <= s < P for s in sums)):
-        return N.GKR_VERIFY_NON_CANONICAL, 0, 0
-    for k, (rounds, challenges, vals) in enumerate(layers, start=2):
-        bad = _transcript_form(rounds, challenges, 4, vals)
-        if bad is not None:
-            return bad[1], k, bad[0]
-    root = fraction_root(head)
-    if root[1] == 0:
-        return N.GKR_VERIFY_ZERO_DENOMINATOR, 0, 0
-    if sums is not None and tuple(sums) != root:
-        return N.GKR_VERIFY_FRACTION_SUM, 0, 0
-    z = [multi_hash(head, 0)]
-    z.append(multi_hash([z[0]], 0))
-    lam = multi_hash([z[1]], 0)
-    cp, cq = mle_eval(head[:4], z), mle_eval(head[4:], z)
-    for k, (rounds, challenges, (a0, a1, b0, b1)) in enumerate(layers, start=2):
-        bad, last = _transcript_rounds(rounds, challenges, cp + lam * cq)
-        if bad is not None:
-            return bad[1], k, bad[0]
-        eq_r = 1
-        for zj, rj in zip(z, challenges):
-            eq_r = eq_r * (zj * rj + (1 - zj) * (1 - rj)) % P
-        if last != eq_r * (a0 * b1 + a1 * b0 + lam * b0 % P * b1) % P:
-            return N.GKR_VERIFY_FINAL_CLAIM, k, k
-        tau = multi_hash([a0, a1, b0, b1], 0)
-        cp, cq = (a0 + tau * (a1 - a0)) % P, (b0 + tau * (b1 - b0)) % P
-        z = [tau] + list(challenges)
-        lam = multi_hash([tau], 0)
-    if numerators is not None and (cp != mle_eval(numerators, z) or cq != mle_eval(denominators, z)):
-        return N.GKR_VERIFY_EVALUATION, n, n
-    return 0, 0, 0
+    return _verify_tree(head, layers, _FRACTION_SUM, None if numerators is None else [numerators, denominators], sums)
 
 
 def verify(proof: Proof, circuit: GKRCircuit) -> bool:

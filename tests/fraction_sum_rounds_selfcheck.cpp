@@ -1,5 +1,5 @@
-// Stand-alone check of the fractional sum's chain of claims (gkr_amd/csrc/fraction_sum_rounds.h: pre_relations, verdict and the
-// Fiat-Shamir steps the driver shares with them) without a device or a context, meant to be built under
+// Stand-alone check of the fractional sum's chain of claims (gkr_amd/csrc/tree_rounds.h with the gate of fraction_sum_rounds.h:
+// pre_relations, verdict and the Fiat-Shamir steps the driver shares with them) without a device or a context, meant to be built under
 // -fsanitize=address,undefined (tests/test_fraction_sum_host.py; make -C gkr_amd/csrc asan_fs):
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined tests/fraction_sum_rounds_selfcheck.cpp gkr_amd/csrc/keccak.cpp
 //   ./a.out CASES
@@ -27,12 +27,17 @@ namespace {
 
 using gkr::h64::F;
 namespace V = gkr::verify;
-namespace FS = gkr::fs;
+namespace T = gkr::tree;
+using Gate = gkr::fs::Gate;
 
 F g_cts[gkr::kMimcRounds];
+size_t g_hashes = 0;   // multi-hash calls so far
 const F kZero = {{0, 0, 0, 0}};
 
-F hash(const F* v, int n) { return gkr::h64::mimc7_multi_hash(v, n, g_cts, nullptr); }
+F hash(const F* v, int n) {
+    ++g_hashes;
+    return gkr::h64::mimc7_multi_hash(v, n, g_cts, nullptr);
+}
 
 bool read_fr(std::ifstream& in, gkr_fr* out) {
     std::string s;
@@ -65,7 +70,7 @@ F mle(const std::vector<gkr_fr>& table, const gkr_fr* point, int n) {   // entri
     for (const gkr_fr& x : table) t.push_back(reduced(x));
     for (int j = 0; j < n; ++j) {
         const size_t h = t.size() / 2;
-        for (size_t i = 0; i < h; ++i) t[i] = FS::lerp(t[i], t[i + h], V::load(point[j]));
+        for (size_t i = 0; i < h; ++i) t[i] = T::lerp(t[i], t[i + h], V::load(point[j]));
         t.resize(h);
     }
     return t[0];
@@ -93,7 +98,7 @@ int main(int argc, char** argv) {
             printf("fraction_sum_rounds_selfcheck: FAILED: case %d is malformed\n", cases);
             return 1;
         }
-        const size_t R = FS::rounds(n), size = (size_t)1 << n;
+        const size_t R = T::rounds(n), size = (size_t)1 << n;
         std::vector<gkr_fr> sums, head, coeffs, r, evals, num, den;
         std::vector<uint32_t> len(R);
         bool ok = read_frs(in, 2, &sums) && read_frs(in, 8, &head) && read_frs(in, R * 4, &coeffs);
@@ -105,14 +110,16 @@ int main(int argc, char** argv) {
             printf("fraction_sum_rounds_selfcheck: FAILED: case %d is cut short\n", cases);
             return 1;
         }
-        const FS::Proof p{with_sums ? sums.data() : nullptr, head.data(), coeffs.data(), r.data(), evals.data(), len.data()};
-        const FS::Pre pre = FS::pre_relations(n, p, hash);
+        const T::Proof p{with_sums ? sums.data() : nullptr, head.data(), coeffs.data(), r.data(), evals.data(), len.data()};
+        const size_t hashes_before = g_hashes;
+        const T::Pre<Gate> pre = T::pre_relations<Gate>(n, p, hash);
+        const size_t pre_hashes = g_hashes - hashes_before;
         std::vector<V::HashSlot> slots(R);
         for (size_t s = 0; s < R; ++s) V::hash_slot(coeffs.data() + 4 * s, 4u, len[s], &slots[s], hash);
-        const F vn = pre.point ? mle(num, pre.z.data() + FS::layer_row(n), n) : kZero;
-        const F vd = pre.point ? mle(den, pre.z.data() + FS::layer_row(n), n) : kZero;
-        FS::Verdict v;
-        if (!FS::verdict(n, p, pre, slots.data(), vn, vd, &v)) {
+        const F values[2] = {pre.point ? mle(num, pre.z.data() + T::layer_row(n), n) : kZero,
+                             pre.point ? mle(den, pre.z.data() + T::layer_row(n), n) : kZero};
+        T::Verdict v;
+        if (!T::verdict<Gate>(n, p, pre, slots.data(), values, &v)) {
             printf("fraction_sum_rounds_selfcheck: FAILED: case %d: a well-formed round vector without a hash\n", cases);
             return 1;
         }
@@ -122,20 +129,21 @@ int main(int argc, char** argv) {
             return 1;
         }
         if (honest) {
-            F P, Q;
-            FS::head_root(head.data(), &P, &Q);
-            bool good = pre.point && same(FS::abi(P), want[0]) && same(FS::abi(Q), want[1]);
-            for (int j = 0; good && j < n; ++j) good = same(pre.z[FS::layer_row(n) + (size_t)j], want[2 + (size_t)j]);
-            good = good && pre.cp.size() == (size_t)n - 1 && same(FS::abi(pre.cp.back()), want[(size_t)n + 2]) &&
-                   same(FS::abi(pre.cq.back()), want[(size_t)n + 3]);
+            F root[2];
+            Gate::root(head.data(), root);
+            bool good = pre.point && same(T::abi(root[0]), want[0]) && same(T::abi(root[1]), want[1]);
+            good = good && pre_hashes == 3 + 2 * (size_t)(n - 2);   // the head's three, then tau and lambda per layer
+            for (int j = 0; good && j < n; ++j) good = same(pre.z[T::layer_row(n) + (size_t)j], want[2 + (size_t)j]);
+            good = good && pre.link.size() == (size_t)n - 1 && same(T::abi(pre.link.back().c[0]), want[(size_t)n + 2]) &&
+                   same(T::abi(pre.link.back().c[1]), want[(size_t)n + 3]);
             if (check == 0) {   // a missing hash is an error of the call, not a verdict
                 std::vector<V::HashSlot> none(R);
                 for (V::HashSlot& s : none) s.valid = 0;
-                FS::Verdict u;
-                good = good && !FS::verdict(n, p, pre, none.data(), vn, vd, &u);
+                T::Verdict u;
+                good = good && !T::verdict<Gate>(n, p, pre, none.data(), values, &u);
             }
             if (!good) {
-                printf("fraction_sum_rounds_selfcheck: FAILED: case %d (n %d): the honest proof's root, point or end claims\n", cases, n);
+                printf("fraction_sum_rounds_selfcheck: FAILED: case %d (n %d): the honest proof's root, point, end claims or number of multi-hash calls\n", cases, n);
                 return 1;
             }
             ++honest_cases;

@@ -1,5 +1,5 @@
-// Stand-alone check of the grand product's chain of claims (gkr_amd/csrc/grand_product_rounds.h: pre_relations, verdict and the
-// Fiat-Shamir steps the driver shares with them) without a device or a context, meant to be built under
+// Stand-alone check of the grand product's chain of claims (gkr_amd/csrc/tree_rounds.h with the gate of grand_product_rounds.h:
+// pre_relations, verdict and the Fiat-Shamir steps the driver shares with them) without a device or a context, meant to be built under
 // -fsanitize=address,undefined (tests/test_grand_product_host.py; make -C gkr_amd/csrc asan_gp):
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined tests/grand_product_rounds_selfcheck.cpp gkr_amd/csrc/keccak.cpp
 // Proofs over tables of 2^3 .. 2^6 values are made here by a plain prover -- the tree, then per layer the zero-check's round
@@ -20,21 +20,26 @@ namespace {
 
 using gkr::h64::F;
 namespace V = gkr::verify;
-namespace GP = gkr::gp;
+namespace T = gkr::tree;
+using Gate = gkr::gp::Gate;
 using gkr::h64::add;
 using gkr::h64::sub;
-using GP::mul;
+using T::mul;
 
 F g_cts[gkr::kMimcRounds];
+size_t g_hashes = 0;   // multi-hash calls so far
 const F kZero = {{0, 0, 0, 0}}, kOne = {{1, 0, 0, 0}};
 
-F hash(const F* v, int n) { return gkr::h64::mimc7_multi_hash(v, n, g_cts, nullptr); }
+F hash(const F* v, int n) {
+    ++g_hashes;
+    return gkr::h64::mimc7_multi_hash(v, n, g_cts, nullptr);
+}
 gkr_fr modulus() {
     gkr_fr x;
     memcpy(x.l, gkr::h64::kMod, 32);
     return x;
 }
-gkr_fr plus_one(const gkr_fr& x) { return GP::abi(add(V::load(x), kOne)); }
+gkr_fr plus_one(const gkr_fr& x) { return T::abi(add(V::load(x), kOne)); }
 
 struct Made {
     int n = 0;
@@ -42,7 +47,7 @@ struct Made {
     gkr_fr product{};
     std::vector<gkr_fr> head, coeffs, r, evals;
     std::vector<uint32_t> len;
-    GP::Proof view(bool with_product) const { return GP::Proof{with_product ? &product : nullptr, head.data(), coeffs.data(), r.data(), evals.data(), len.data()}; }
+    T::Proof view(bool with_product) const { return T::Proof{with_product ? &product : nullptr, head.data(), coeffs.data(), r.data(), evals.data(), len.data()}; }
 };
 
 std::vector<F> eq_table(const std::vector<F>& z, size_t from) {
@@ -61,7 +66,7 @@ std::vector<F> eq_table(const std::vector<F>& z, size_t from) {
 F mle(std::vector<F> t, const gkr_fr* point, int n) {
     for (int j = 0; j < n; ++j) {
         const size_t h = t.size() / 2;
-        for (size_t i = 0; i < h; ++i) t[i] = GP::lerp(t[i], t[i + h], V::load(point[j]));
+        for (size_t i = 0; i < h; ++i) t[i] = T::lerp(t[i], t[i + h], V::load(point[j]));
         t.resize(h);
     }
     return t[0];
@@ -79,18 +84,18 @@ Made make(int n, int kind, uint64_t seed) {
     level[n] = m.table;
     for (int k = n - 1; k >= 0; --k)
         for (size_t i = 0; i < ((size_t)1 << k); ++i) level[k].push_back(mul(level[k + 1][i], level[k + 1][i + ((size_t)1 << k)]));
-    m.product = GP::abi(level[0][0]);
-    for (const F& v : level[2]) m.head.push_back(GP::abi(v));
-    const size_t R = GP::rounds(n);
+    m.product = T::abi(level[0][0]);
+    for (const F& v : level[2]) m.head.push_back(T::abi(v));
+    const size_t R = T::rounds(n);
     m.coeffs.assign(R * 4, modulus());
     m.r.resize(R);
     m.len.resize(R);
     m.evals.resize(2 * (size_t)(n - 2));
-    F zeta1, zeta2;
-    GP::head_point(m.head.data(), hash, &zeta1, &zeta2);
-    std::vector<F> z{zeta1, zeta2};
+    gkr_fr z2[2];
+    T::head_link<Gate>(m.head.data(), hash, z2);
+    std::vector<F> z{V::load(z2[0]), V::load(z2[1])};
     for (int k = 2; k < n; ++k) {
-        const size_t half = (size_t)1 << k, row = GP::layer_row(k);
+        const size_t half = (size_t)1 << k, row = T::layer_row(k);
         std::vector<F> A(level[k + 1].begin(), level[k + 1].begin() + half), B(level[k + 1].begin() + half, level[k + 1].end());
         F s = kOne;
         for (int j = 0; j < k; ++j) {
@@ -108,21 +113,21 @@ Made make(int n, int kind, uint64_t seed) {
             uint32_t lead = 0;
             while (lead < 3 && gkr::h64::is_zero(g[lead])) ++lead;
             m.len[row + j] = 4 - lead;
-            for (uint32_t t = lead; t < 4; ++t) m.coeffs[4 * (row + j) + t] = GP::abi(g[t]);
+            for (uint32_t t = lead; t < 4; ++t) m.coeffs[4 * (row + j) + t] = T::abi(g[t]);
             const F rj = hash(g + lead, (int)(4 - lead));
-            m.r[row + j] = GP::abi(rj);
+            m.r[row + j] = T::abi(rj);
             s = add(a, mul(b, rj));
             for (size_t i = 0; i < h; ++i) {
-                A[i] = GP::lerp(A[i], A[i + h], rj);
-                B[i] = GP::lerp(B[i], B[i + h], rj);
+                A[i] = T::lerp(A[i], A[i + h], rj);
+                B[i] = T::lerp(B[i], B[i + h], rj);
             }
             A.resize(h);
             B.resize(h);
         }
-        m.evals[2 * (k - 2)] = GP::abi(A[0]);
-        m.evals[2 * (k - 2) + 1] = GP::abi(B[0]);
+        m.evals[2 * (k - 2)] = T::abi(A[0]);
+        m.evals[2 * (k - 2) + 1] = T::abi(B[0]);
         std::vector<gkr_fr> zn((size_t)k + 1);
-        GP::next_claim(k, m.evals.data() + 2 * (k - 2), m.r.data() + row, hash, zn.data());
+        T::next_link<Gate>(k, m.evals.data() + 2 * (k - 2), m.r.data() + row, hash, zn.data());
         z.clear();
         for (const gkr_fr& c : zn) z.push_back(V::load(c));
     }
@@ -136,17 +141,17 @@ struct Got {
 
 // the verdict of a proof against its own table (value: V~(z^(n)) where the proof has a point, else zero); check -1: a missing hash
 Got run(const Made& m, bool with_product, bool hashes = true) {
-    const GP::Proof p = m.view(with_product);
-    const GP::Pre pre = GP::pre_relations(m.n, p, hash);
-    const size_t R = GP::rounds(m.n);
+    const T::Proof p = m.view(with_product);
+    const T::Pre<Gate> pre = T::pre_relations<Gate>(m.n, p, hash);
+    const size_t R = T::rounds(m.n);
     std::vector<V::HashSlot> slots(R);
     for (size_t s = 0; s < R; ++s) {
         slots[s].valid = 0;
         if (hashes) V::hash_slot(m.coeffs.data() + 4 * s, 4u, m.len[s], &slots[s], hash);
     }
-    const F value = pre.point ? mle(m.table, pre.z.data() + GP::layer_row(m.n), m.n) : kZero;
-    GP::Verdict v;
-    if (!GP::verdict(m.n, p, pre, slots.data(), value, &v)) return Got{-1, 0, 0};
+    const F value = pre.point ? mle(m.table, pre.z.data() + T::layer_row(m.n), m.n) : kZero;
+    T::Verdict v;
+    if (!T::verdict<Gate>(m.n, p, pre, slots.data(), &value, &v)) return Got{-1, 0, 0};
     return Got{(int)v.check, (int)v.layer, (int)v.round};
 }
 
@@ -171,7 +176,14 @@ int main() {
             const Made m = make(n, kind, (uint64_t)(1000 * n + kind));
             if (!(run(m, true) == ok) || !(run(m, false) == ok)) return fail("the honest proof is rejected", n, kind, run(m, true).check, 0);
             if (!(run(m, true, false) == Got{-1, 0, 0})) return fail("a missing hash goes unnoticed", n, kind, 0, 0);
-            if (!V::same(V::load(m.product), GP::head_product(m.head.data()))) return fail("the head's product", n, kind, 0, 0);
+            F root;
+            Gate::root(m.head.data(), &root);
+            if (!V::same(V::load(m.product), root)) return fail("the head's product", n, kind, 0, 0);
+            {   // the chain's hashes: the head's two and one tau per layer -- no lambda is drawn
+                const size_t before = g_hashes;
+                T::pre_relations<Gate>(n, m.view(true), hash);
+                if (g_hashes - before != 2 + (size_t)(n - 2)) return fail("the number of multi-hash calls of pre_relations", n, kind, (int)(g_hashes - before), 0);
+            }
             {   // another table: the chain holds, the evaluation does not
                 Made u = m;
                 u.table[1] = add(u.table[1], kOne);
@@ -195,7 +207,7 @@ int main() {
             }
             for (int k = 2; k < n; ++k) {
                 for (int j = 0; j < k; ++j) {
-                    const size_t row = GP::layer_row(k) + (size_t)j;
+                    const size_t row = T::layer_row(k) + (size_t)j;
                     for (uint32_t t = 4 - m.len[row]; t < 4; ++t) {
                         Made u = m;
                         u.coeffs[4 * row + t] = plus_one(u.coeffs[4 * row + t]);
