@@ -30,6 +30,8 @@ GKR_VERIFY_MATRIX, GKR_VERIFY_WITNESS = 11, 12
 GKR_VERIFY_FINAL_CLAIM, GKR_VERIFY_PRODUCT = 6, 13
 # the fractional sum verifier's own (gkr_fraction_sum_verify*): the head's Q is zero, a claimed (P, Q) against the head's root
 GKR_VERIFY_ZERO_DENOMINATOR, GKR_VERIFY_FRACTION_SUM = 14, 15
+# the lookup verifier's own (gkr_lookup_verify*): the head's P is not zero
+GKR_VERIFY_LOOKUP = 16
 
 # rows of an R1CS matrix with more terms than this get a wave each on the device (GKR_R1CS_LONG_ROW)
 GKR_R1CS_LONG_ROW = 32
@@ -59,6 +61,8 @@ SYMBOLS = [
     "gkr_selftest_grand_product_geometry", "gkr_devtest_grand_product_tree", "gkr_devtest_grand_product_chunk",
     "gkr_fraction_sum_batch_device", "gkr_fraction_sum", "gkr_fraction_sum_verify_batch_device", "gkr_fraction_sum_verify",
     "gkr_selftest_fraction_sum_geometry", "gkr_devtest_fraction_sum_tree", "gkr_devtest_fraction_sum_chunk",
+    "gkr_lookup_multiplicities_device", "gkr_lookup_batch_device", "gkr_lookup_verify_batch_device", "gkr_lookup", "gkr_lookup_verify",
+    "gkr_selftest_lookup_slot", "gkr_devtest_lookup_pair",
     "gkr_mle_eval_batch_device", "gkr_sumcheck_mle_verify_batch_device", "gkr_sumcheck_mle_verify",
     "gkr_sumcheck_layer", "gkr_sumcheck_layer_sharded", "gkr_sumcheck_layer_device", "gkr_resident_layer_create", "gkr_resident_layer_sumcheck", "gkr_resident_layer_sumcheck_wdev", "gkr_resident_layer_free", "gkr_exchange_limbs", "gkr_resident_layer_sumcheck_dev", "gkr_exchange_limbs_mle", "gkr_sumcheck_mle_sharded_dev", "gkr_exchange_rccl_unique_id", "gkr_exchange_rccl_create", "gkr_exchange_rccl_dev",
     "gkr_exchange_rccl_calls", "gkr_exchange_rccl_destroy", "gkr_exchange_rccl_error", "gkr_fr_widen", "gkr_fr_narrow", "gkr_predicate_tables", "gkr_layer_eval", "gkr_proof_sizes", "gkr_prove", "gkr_prove_batch",
@@ -219,6 +223,22 @@ def lib():
                     ("gkr_devtest_%s_chunk", [ctypes.c_void_p] + [ctypes.c_int] * 2 + [ctypes.c_void_p])):
                 getattr(L, fn % name).restype = ctypes.c_int
                 getattr(L, fn % name).argtypes = argtypes
+        # the lookup: W = (ctx, d_witness, n_w, d_table, n_t, shared_table); (W, batch, d_mult, out_missing, out_first_missing);
+        # (W, d_mult, alpha, batch, the fractional sum's eight outputs); (W, d_mult, alpha, batch, head, coeffs, len, r, evals, accept,
+        # failed_layer, failed_round, failed_check, out_sums); the host forms (ctx, witness, n_w, table, n_t, ..); (v, log_slots, slot);
+        # (W, d_mult, alpha, batch, d_pair)
+        W = [ctypes.c_void_p] * 2 + [ctypes.c_int, ctypes.c_void_p] + [ctypes.c_int] * 2
+        H = [ctypes.c_void_p] * 2 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
+        for fn, argtypes in (
+                ("gkr_lookup_multiplicities_device", W + [ctypes.c_int] + [ctypes.c_void_p] * 3),
+                ("gkr_lookup_batch_device", W + [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 8),
+                ("gkr_lookup_verify_batch_device", W + [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 10),
+                ("gkr_lookup", H + [ctypes.c_void_p] * 12),
+                ("gkr_lookup_verify", H + [ctypes.c_void_p] * 11),
+                ("gkr_selftest_lookup_slot", [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+                ("gkr_devtest_lookup_pair", W + [ctypes.c_void_p] * 2 + [ctypes.c_int, ctypes.c_void_p])):
+            getattr(L, fn).restype = ctypes.c_int
+            getattr(L, fn).argtypes = argtypes
         # the R1CS zero-check: the CSR form (host only), the resident handle, the rows, the zero-check on them
         L.gkr_r1cs_csr_info.restype = ctypes.c_int
         L.gkr_r1cs_csr_info.argtypes = [ctypes.c_void_p] * 2

@@ -5,7 +5,8 @@
 // such products; capi_zerocheck.hip: the zero-check -- the entry points and shape checks of the three, whose one driver is
 // capi_resident.hip; capi_r1cs.hip: an R1CS's tables in front of it; capi_r1cs_verify.hip: the verifier of that pair of
 // sumchecks; capi_grand_product.hip: the grand product, a product tree and a zero-check per layer, and its verifier;
-// capi_fraction_sum.hip: the fractional sum, a tree of fractions and a zero-check per layer, and its verifier; capi_verify.hip
+// capi_fraction_sum.hip: the fractional sum, a tree of fractions and a zero-check per layer, and its verifier; capi_lookup.hip:
+// the lookup, multiplicities and the pair (N, D) in front of the fractional sum's two entry points; capi_verify.hip
 // and capi_mle_verify.hip: the verifiers of whole proofs and of the sumchecks over resident tables; verify_chunk.h: the pieces the
 // five files with a batch verifier build a chunk from): the context, its caches and workspaces, profiling brackets, the host
 // transcript's helpers, the hand-off wait, the plain sumcheck's group hand-off.  Not a public header.

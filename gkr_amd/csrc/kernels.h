@@ -363,6 +363,21 @@ void launch_fs_round(const ProductPartial* partials, uint32_t nblk, uint32_t rou
                      const Fr* z, Fr* s_slot, const Fr* work, size_t work_stride, Fr* out_coeffs, uint32_t* out_len, Fr* out_r, FixedMul* rtab,
                      Fr* evals, Fr* eq_out, hipStream_t s);
 
+// ---- the lookup argument's preparation (kernels_lookup.hip): the table's index, the multiplicities, the pair (N, D) ----
+// Every launch: blocks of 256 threads, a thread per item, lk_blocks(log2 items) = ceil(2^log2 / 256) blocks per table / column / pair.
+uint32_t lk_blocks(uint32_t log2_items);
+// index: tables x 2^(n_t+1) words, all 0xFFFFFFFF before the launch; table t at + t * 2^n_t
+void launch_lk_build(const Fr* table, uint32_t n_t, uint32_t tables, uint32_t* index, hipStream_t s);
+// counts: batch x 2^n_t words and missing: batch words, zero before the launch; first_missing: batch words, 0xFFFFFFFF before it;
+// witness column b at + b * 2^n_w; shared_table: one table and one index for every column
+void launch_lk_count(const Fr* witness, uint32_t n_w, const Fr* table, uint32_t n_t, bool shared_table, const uint32_t* index, uint32_t batch,
+                     uint32_t* counts, uint32_t* missing, uint32_t* first_missing, hipStream_t s);
+// mult: batch x 2^n_t canonical elements
+void launch_lk_mult(const uint32_t* counts, uint32_t n_t, uint32_t batch, Fr* mult, hipStream_t s);
+// pair: batch x 2 x 2^L elements (N then D), L = max(n_w, n_t) + 1; alpha: batch canonical elements in device memory
+void launch_lk_pair(const Fr* witness, uint32_t n_w, const Fr* table, uint32_t n_t, bool shared_table, const Fr* mult, const Fr* alpha, uint32_t L,
+                    uint32_t batch, Fr* pair, hipStream_t s);
+
 void launch_layer_eval(uint32_t gates, const uint8_t* gate_type, const uint32_t* left, const uint32_t* right,
                        const Fr* prev, Fr* out, uint32_t batch, uint32_t prev_stride, hipStream_t s, const GateSet* sets = nullptr);
 // words 32-bit words src -> dst (16-byte aligned when words >= 4); either side may be pinned host memory

@@ -747,6 +747,80 @@ class Context:
             raise GkrError(N.GKR_ERR_INVALID, "two tables of 2^n values, eight head values and n - 2 layers expected")
         return self._tree_verify(N.lib().gkr_fraction_sum_verify, 2, (num, den), head, layers, sums)
 
+    # -- the lookup (LogUp with multiplicities): every witness value lies in the table iff the fractional sum of the pair
+    # (1, alpha - W) | (-M, alpha - T) is zero; multiplicities and pair are built on the device, the proof is the fractional sum's
+    @staticmethod
+    def lookup_pair_log2(n_w, n_t):
+        """L = max(n_w, n_t) + 1: the pair of a lookup has 2^L entries, its proof is a fractional sum's with n = L."""
+        return max(n_w, n_t) + 1
+
+    @staticmethod
+    def _alphas(alpha, batch):
+        a = np.ascontiguousarray(alpha if isinstance(alpha, np.ndarray) else to_limbs([int(x) for x in alpha]), dtype=np.uint64)
+        if a.shape != (batch, 4):
+            raise GkrError(N.GKR_ERR_INVALID, "one alpha per column expected")
+        return a
+
+    def lookup_multiplicities_device(self, d_witness, n_w, d_table, n_t, shared_table, batch, d_mult):
+        """gkr_lookup_multiplicities_device: the multiplicities of `batch` resident witness columns of 2^n_w values in their tables of
+        2^n_t values (one table for all with shared_table), written to d_mult (batch x 2^n_t elements on the device); the lowest
+        index of a repeated table value takes the whole count.  -> (missing, first_missing), (batch,) uint32 each: the entries of a
+        column that are not in its table and the lowest such index (0xFFFFFFFF: none)."""
+        if batch < 1:
+            raise GkrError(N.GKR_ERR_INVALID, "batch >= 1 expected")
+        missing, first = np.zeros(batch, dtype=np.uint32), np.zeros(batch, dtype=np.uint32)
+        self._check(N.lib().gkr_lookup_multiplicities_device(self._h, d_witness, n_w, d_table, n_t, int(bool(shared_table)), batch, d_mult,
+                                                             _ptr(missing), _ptr(first)))
+        return missing, first
+
+    def lookup_batch_device(self, d_witness, n_w, d_table, n_t, shared_table, d_mult, alpha, batch, out=None):
+        """gkr_lookup_batch_device: the pairs of `batch` lookups built on the device from W, T, d_mult and alpha (batch integers, or
+        (batch, 4) limbs), then their fractional sums.  -> fraction_sum_batch_device's (S, H, C, L, R, E, Z, K) with
+        n = lookup_pair_log2(n_w, n_t), byte for byte what that call returns on the same pairs; S[b] = (0, Q) where the lookup holds."""
+        a = self._alphas(alpha, batch)
+        fn = lambda h, d, n, b, *outs: N.lib().gkr_lookup_batch_device(h, d, n_w, d_table, n_t, int(bool(shared_table)), d_mult, _ptr(a), b, *outs)
+        return self._tree_batch_device(fn, 2, d_witness, self.lookup_pair_log2(n_w, n_t), batch, out)
+
+    def verify_lookup_batch_device(self, d_witness, n_w, d_table, n_t, shared_table, d_mult, alpha, batch, H, C, L, R, E):
+        """gkr_lookup_verify_batch_device on the resident tables, d_mult, alpha and the arrays lookup_batch_device returned (its H, C,
+        L, R, E).  -> (accept (batch,) bool, failed_layer, failed_round, failed_check (batch,) uint32, sums (batch, 2, 4): the heads'
+        roots): the fractional sum's verdict on the rebuilt pair, and GKR_VERIFY_LOOKUP at (0, 0) for a head whose P is not 0.
+        verifier.verify_lookup is the same verdict on plain integers."""
+        a = self._alphas(alpha, batch)
+        fn = lambda h, d, n, b, claimed, *rest: N.lib().gkr_lookup_verify_batch_device(h, d, n_w, d_table, n_t, int(bool(shared_table)), d_mult, _ptr(a),
+                                                                                      b, *rest)
+        return self._tree_verify_batch_device(fn, 2, "sums", d_witness, self.lookup_pair_log2(n_w, n_t), batch, H, C, L, R, E, None)
+
+    @staticmethod
+    def _lookup_tables(witness, table):
+        w, t = as_limbs(witness), as_limbs(table)
+        n_w, n_t = w.shape[0].bit_length() - 1, t.shape[0].bit_length() - 1
+        if n_w < 2 or n_t < 2 or w.shape[0] != 1 << n_w or t.shape[0] != 1 << n_t:
+            raise GkrError(N.GKR_ERR_INVALID, "a witness of 2^n_w and a table of 2^n_t values, n_w, n_t >= 2, expected")
+        return w, n_w, t, n_t
+
+    def prove_lookup(self, witness, table, alpha):
+        """gkr_lookup: the multiplicities of the witness in the table and the proof that, with them, every witness value lies in the
+        table.  -> (mult, (missing, first_missing), (P, Q), head, layers, point, claims): mult the 2^n_t multiplicities, the rest
+        prove_fraction_sum's result on the lookup's pair; P = 0 where the lookup holds.  alpha is taken before the multiplicities
+        exist: a convenience, not a sound composition (include/gkr_amd.h).  verifier.verify_lookup checks it on plain integers."""
+        w, n_w, t, n_t = self._lookup_tables(witness, table)
+        a = to_limbs([int(alpha)])
+        M, miss, first = np.zeros((1 << n_t, 4), dtype=np.uint64), ctypes.c_uint32(0), ctypes.c_uint32(0)
+        fn = lambda h, pw, v, *outs: N.lib().gkr_lookup(h, pw, n_w, _ptr(t), n_t, _ptr(a), _ptr(M), ctypes.byref(miss), ctypes.byref(first), *outs)
+        S, head, layers, point, K = self._tree_prove(fn, 2, (w,), self.lookup_pair_log2(n_w, n_t))
+        return from_limbs(M), (int(miss.value), int(first.value)), tuple(S), head, layers, point, tuple(K)
+
+    def verify_lookup(self, witness, table, mult, alpha, head, layers):
+        """gkr_lookup_verify on host tables and what prove_lookup returned (its mult, head and layers).  -> (check, layer, round),
+        (0, 0, 0) for an accepted proof: verifier.verify_lookup's verdict."""
+        w, n_w, t, n_t = self._lookup_tables(witness, table)
+        m, a = as_limbs(mult), to_limbs([int(alpha)])
+        if m.shape[0] != 1 << n_t or len(head) != 8 or len(layers) + 2 != self.lookup_pair_log2(n_w, n_t):
+            raise GkrError(N.GKR_ERR_INVALID, "2^n_t multiplicities, eight head values and max(n_w, n_t) - 1 layers expected")
+        fn = lambda h, pw, n, claimed, *rest: N.lib().gkr_lookup_verify(h, pw, n_w, _ptr(t), n_t, _ptr(m), _ptr(a), *rest)
+        return self._tree_verify(fn, 2, (w,), head, layers, None)
+
     # -- the R1CS zero-check: Az, Bz, Cz of resident witnesses built on the device, then eq(z, .) (A B - C)
     def r1cs_rows(self, r1cs) -> R1csRows:
         """gkr_r1cs_rows_prepare: the CSR form of `r1cs` (convert.R1cs) resident on this context's device."""
@@ -1346,6 +1420,10 @@ def prove_grand_product(table, v):
 
 def prove_fraction_sum(numerators, denominators, v):
     return default_context().prove_fraction_sum(numerators, denominators, v)
+
+
+def prove_lookup(witness, table, alpha):
+    return default_context().prove_lookup(witness, table, alpha)
 
 
 def prove_r1cs_zerocheck(r1cs, witness, z):

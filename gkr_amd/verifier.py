@@ -440,6 +440,31 @@ def verify_fraction_sum(head: List[int], layers, numerators=None, denominators=N
     return _verify_tree(head, layers, _FRACTION_SUM, None if numerators is None else [numerators, denominators], sums)
 
 
+def lookup_pair(witness: List[int], table: List[int], mult: List[int], alpha: int):
+    """(N, D) of a lookup (include/gkr_amd.h, LOOKUP): 2^L entries each, L = max(n_w, n_t) + 1; (1, alpha - W[i]) then (0, 1) on the
+    first half, (-M[j], alpha - T[j]) then (0, 1) on the second."""
+    half = max(len(witness), len(table))
+    if len(witness) < 4 or len(table) < 4 or len(witness) & (len(witness) - 1) or len(table) & (len(table) - 1) or len(mult) != len(table):
+        raise ValueError("a witness of 2^n_w values, a table and multiplicities of 2^n_t values, n_w, n_t >= 2, expected")
+    num = [1] * len(witness) + [0] * (half - len(witness)) + [-int(m) % P for m in mult] + [0] * (half - len(table))
+    den = [(alpha - int(w)) % P for w in witness] + [1] * (half - len(witness)) + [(alpha - int(t)) % P for t in table] + [1] * (half - len(table))
+    return num, den
+
+
+def verify_lookup(witness: List[int], table: List[int], mult: List[int], alpha: int, head: List[int], layers):
+    """The verifier of a lookup proof (Context.prove_lookup) on plain integers: what Context.verify_lookup_batch_device decides on the
+    device.  verify_fraction_sum's verdict on the pair lookup_pair(witness, table, mult, alpha), without claimed sums, with one
+    addition: LOOKUP at (0, 0) where the head's P (fraction_root) is not 0 -- after SHAPE, NON_CANONICAL and ZERO_DENOMINATOR, before
+    the layers' relations and EVALUATION."""
+    num, den = lookup_pair(witness, table, mult, alpha)
+    if len(layers) + 2 != len(num).bit_length() - 1:
+        raise ValueError("max(n_w, n_t) - 1 layers expected")
+    verdict = verify_fraction_sum(head, layers, num, den, None)
+    if verdict[0] in (N.GKR_VERIFY_SHAPE, N.GKR_VERIFY_NON_CANONICAL, N.GKR_VERIFY_ZERO_DENOMINATOR):
+        return verdict
+    return (N.GKR_VERIFY_LOOKUP, 0, 0) if fraction_root(head)[0] != 0 else verdict
+
+
 def verify(proof: Proof, circuit: GKRCircuit) -> bool:
     """python/gkr.py:202-231 on the Rust-shaped proof."""
     L = circuit.depth()

@@ -704,6 +704,92 @@ int  gkr_devtest_fraction_sum_tree(gkr_ctx *ctx, const void *d_tables, int n, in
  * min(what fits, 32768, batch), at least 1.  No device work.  The argument checks of gkr_fraction_sum_verify_batch_device. */
 int  gkr_devtest_fraction_sum_chunk(gkr_ctx *ctx, int n, int batch, uint32_t *out);
 
+/* ---- LOOKUP (LogUp with multiplicities): every value of a resident witness column lies in a resident table -----------------------
+ * The first application of the fractional sum above: the multiplicities and the pair (N, D) are built on the device
+ * (csrc/kernels_lookup.hip), the proof is gkr_fraction_sum_batch_device's proof of that pair.  The reference has no such argument.
+ *   inputs    `batch` witness columns W of 2^n_w canonical values, column b at d_witness + b * 2^n_w elements; tables T of 2^n_t
+ *             canonical values: with shared_table != 0 ONE table at d_table for every column, else column b's own at
+ *             d_table + b * 2^n_t; a challenge alpha per column, the CALLER's.  The library has no commitments (z and rho of
+ *             the R1CS calls are the caller's for the same reason), which is why the multiplicities are a call of their own: a
+ *             caller who wants soundness (1) fixes the multiplicities M, (2) commits to W, T and M, (3) derives alpha from the
+ *             commitments -- in this order -- and only then proves.
+ *   pair      L = max(n_w, n_t) + 1; the pair has 2^L entries, variable 1 = the most significant index bit.  The top-bit-0
+ *             half is the witness side: (N, D)[i] = (1, alpha - W[i]) for i < 2^n_w, (0, 1) beyond; the top-bit-1 half is the
+ *             table side: (N, D)[2^(L-1) + j] = (-M[j] mod r, alpha - T[j]) for j < 2^n_t, (0, 1) beyond.  Every witness value
+ *             lies in T with M its multiplicities iff sum N / D = 0 as a rational function of alpha: the proof is the fractional
+ *             sum's proof of this pair (n = L), and the verdict adds P == 0.
+ *   M         M[j] = the number of i with W[i] = T[j] if j is the LOWEST index with T's value T[j], else 0: a value T holds
+ *             several times gives its whole count to its first copy, so M is a function of (W, T).
+ *   index     counting is a join of 256-bit keys.  Per table an open-addressing index, linear probing, 2^(n_t+1) slots of one
+ *             uint32_t (load factor <= 1/2), empty = 0xFFFFFFFF.  A thread per table entry j, from slot h(T[j]) on:
+ *             atomicCAS(slot, empty, j); claimed: done; the slot holds an index whose entry equals T[j] on all eight limbs:
+ *             atomicMin(slot, j), done; else the next slot, wrapping at the end.  A slot's key never changes once claimed, so
+ *             value -> lowest index does not depend on the order of arrival.  A launch of its own then counts: a thread per
+ *             witness entry probes until the keys are equal and adds one to that index's uint32_t counter (counts <= 2^30); at an
+ *             empty slot the entry is a miss.  With a shared table the index is built once; M is per column all the same.
+ *   h         the slot of a canonical value v = (v0, v1, v2, v3), 64-bit limbs, least significant first, among 2^s slots,
+ *             arithmetic modulo 2^64:  x = 0x9E3779B97F4A7C15;  for i = 0 .. 3: x = (x ^ v_i) * 0xFF51AFD7ED558CCD, x = x ^ (x >> 32);
+ *             x = x * 0xC4CEB9FE1A85EC53;  x = x ^ (x >> 29);  h(v, s) = x >> (64 - s).  All four limbs are mixed (witness values are
+ *             often small integers, and often differ in high limbs only); csrc/lookup_rules.h, gkr_selftest_lookup_slot.
+ * Limits: 2 <= n_w, n_t; L <= GKR_MAX_MLE_N; batch in 1 .. 65535; batch * 2^(L+1) <= 2^30 (the fractional sum's own limit).
+ * Anything else, or a NULL ctx or required pointer, is GKR_ERR_INVALID before a device or the context is touched (plain returns).
+ * The index, the counters and the pair live in context workspace under slot names of this path's own (lk.*): a fractional-sum,
+ * grand-product, zero-check, SOP or product call on the same context is unaffected.  Inputs are not modified. */
+
+/* The multiplicities.  d_mult: batch x 2^n_t canonical elements in device memory, column b's at d_mult + b * 2^n_t -- a PROVER
+ * output.  out_missing[b]: the number of entries of column b that are not in its table; out_first_missing[b]: the lowest such
+ * index, or 0xFFFFFFFF.  A column with misses is not an error of the call: M counts the hits, the proof still runs and stays
+ * exact, and the verifier rejects (GKR_VERIFY_LOOKUP) -- as the fractional sum does with a zero in D. */
+int  gkr_lookup_multiplicities_device(gkr_ctx *ctx, const void *d_witness, int n_w, const void *d_table, int n_t, int shared_table,
+                                      int batch, void *d_mult, uint32_t *out_missing, uint32_t *out_first_missing);
+
+/* The proofs.  Builds the pairs from W, T, d_mult (as the call above left it, or any batch x 2^n_t canonical elements) and
+ * alpha[batch] in context workspace, pair b being N then D -- one launch, a thread per pair entry, one modular subtraction or
+ * negation each, the padding included -- then runs gkr_fraction_sum_batch_device on them with n = L.  The outputs are exactly that
+ * call's arrays and layouts, byte for byte what it returns on the same pair:
+ *   out_sums  batch x 2 (P, Q)    out_head  batch x 8    out_coeffs  batch x R rows of 4 slots, R = L (L - 1) / 2 - 1
+ *   out_len   batch x R           out_r     batch x R    out_evals   batch x (L - 2) x 4, or NULL
+ *   out_point batch x L, or NULL  out_claims batch x 2, or NULL
+ * GKR_ERR_NON_CANONICAL (through the context) for an alpha >= r. */
+int  gkr_lookup_batch_device(gkr_ctx *ctx, const void *d_witness, int n_w, const void *d_table, int n_t, int shared_table,
+                             const void *d_mult, const gkr_fr *alpha, int batch, gkr_fr *out_sums, gkr_fr *out_head,
+                             gkr_fr *out_coeffs, uint32_t *out_len, gkr_fr *out_r, gkr_fr *out_evals /* or NULL */,
+                             gkr_fr *out_point /* or NULL */, gkr_fr *out_claims /* or NULL */);
+
+/* Verifier of gkr_lookup_batch_device's proofs against the same tables, d_mult and alpha: it reads W, T and M once to rebuild the
+ * pair in workspace, runs gkr_fraction_sum_verify_batch_device on it without claimed sums (which reads the pair at z^(L)) and
+ * reports that verifier's (failed_check, failed_layer, failed_round) with one addition:
+ *   GKR_VERIFY_LOOKUP   the head's P != 0; at (0, 0).  It stands where GKR_VERIFY_FRACTION_SUM stands in that verifier's order --
+ *                       after SHAPE, NON_CANONICAL and ZERO_DENOMINATOR, before the layers' relations and EVALUATION -- and is
+ *                       decided from the root the inner call returns for every proof that passes SHAPE and NON_CANONICAL.
+ * What follows from that:   alpha equal to a witness or table value: ZERO_DENOMINATOR;   M or alpha other than the prover's:
+ * EVALUATION at (L, L);   a prover that ran on a wrong M, or on a witness with misses: LOOKUP.
+ * accept[batch] required; failed_* (batch each) and out_sums (batch x 2: the heads' roots, zeros for a proof that fails SHAPE or
+ * NON_CANONICAL) may be NULL.  The return value is the status of the CALL; GKR_ERR_NON_CANONICAL for an alpha >= r. */
+int  gkr_lookup_verify_batch_device(gkr_ctx *ctx, const void *d_witness, int n_w, const void *d_table, int n_t, int shared_table,
+                                    const void *d_mult, const gkr_fr *alpha, int batch, const gkr_fr *head, const gkr_fr *coeffs,
+                                    const uint32_t *len, const gkr_fr *r, const gkr_fr *evals, int *accept, uint32_t *failed_layer,
+                                    uint32_t *failed_round, uint32_t *failed_check, gkr_fr *out_sums /* or NULL */);
+
+/* One column and one table in host memory: upload, count, prove; out_mult takes the 2^n_t multiplicities, out_missing and
+ * out_first_missing one word each.  It takes alpha BEFORE M exists, so it is a convenience, not a sound composition (see `inputs`
+ * above).  GKR_ERR_NON_CANONICAL for an entry or an alpha >= r. */
+int  gkr_lookup(gkr_ctx *ctx, const gkr_fr *witness, int n_w, const gkr_fr *table, int n_t, const gkr_fr *alpha, gkr_fr *out_mult,
+                uint32_t *out_missing, uint32_t *out_first_missing, gkr_fr *out_sum, gkr_fr *out_head, gkr_fr *out_coeffs,
+                uint32_t *out_len, gkr_fr *out_r, gkr_fr *out_evals, gkr_fr *out_point, gkr_fr *out_claims);
+/* its counterpart: upload + gkr_lookup_verify_batch_device with batch 1.  GKR_ERR_NON_CANONICAL for an entry of witness, table or
+ * mult, or an alpha, >= r. */
+int  gkr_lookup_verify(gkr_ctx *ctx, const gkr_fr *witness, int n_w, const gkr_fr *table, int n_t, const gkr_fr *mult,
+                       const gkr_fr *alpha, const gkr_fr *head, const gkr_fr *coeffs, const uint32_t *len, const gkr_fr *r,
+                       const gkr_fr *evals, int *accept, uint32_t *failed_layer, uint32_t *failed_round, uint32_t *failed_check);
+
+/* h (host logic, the function the kernels call): *slot = h(*v, log_slots).  GKR_ERR_INVALID: NULL pointer, log_slots outside 1 .. 32. */
+int  gkr_selftest_lookup_slot(const gkr_fr *v, int log_slots, uint32_t *slot);
+/* The pair alone, into the CALLER's device buffer instead of the context's workspace: d_pair takes batch x 2 x 2^L elements, pair b
+ * (N then D) at d_pair + b * 2^(L+1).  The argument checks of gkr_lookup_batch_device. */
+int  gkr_devtest_lookup_pair(gkr_ctx *ctx, const void *d_witness, int n_w, const void *d_table, int n_t, int shared_table,
+                             const void *d_mult, const gkr_fr *alpha, int batch, void *d_pair);
+
 /* ---- GKR layer sumcheck: prove_sumcheck_opt, sumcheck.rs:36-44 ----------- */
 /* Layer i has 2^k_i gates; gate g is add (0) or mult (1) of entries left[g],
  * right[g] of layer i+1, which has 2^k_next entries W.  z: k_i challenges.
@@ -1008,7 +1094,8 @@ enum {
     GKR_VERIFY_WITNESS = 12,       /* gkr_r1cs_verify* with a witness: e_w != w~(r_y) */
     GKR_VERIFY_PRODUCT = 13,       /* gkr_grand_product_verify* with claimed products: a claim != the product of the proof's head */
     GKR_VERIFY_ZERO_DENOMINATOR = 14,  /* gkr_fraction_sum_verify*: the head's Q is 0 -- the sum P / Q is undefined */
-    GKR_VERIFY_FRACTION_SUM = 15   /* gkr_fraction_sum_verify* with claimed sums: a claimed (P, Q) != the root of the proof's head */
+    GKR_VERIFY_FRACTION_SUM = 15,  /* gkr_fraction_sum_verify* with claimed sums: a claimed (P, Q) != the root of the proof's head */
+    GKR_VERIFY_LOOKUP = 16         /* gkr_lookup_verify*: the head's P is not 0 -- the fractions of witness and table do not cancel */
 };
 int  gkr_verify(const gkr_circuit_desc *circuit, const gkr_proof_buf *proof, int threads, int *accept, uint32_t *failed_layer,
                 uint32_t *failed_check);
