@@ -23,7 +23,16 @@ Contents
                verifier.r1cs_matrix_evals; its grand product
                (ogkr_grand_product: a loop of products per level, the explicit
                zero-check per layer) by tests/test_oracle_grand_product_c.py to
-               tests/grand_product_model.py and both integer verifiers
+               tests/grand_product_model.py and both integer verifiers; its
+               fractional sum (ogkr_fraction_sum: a loop of products and sums per
+               level, the explicit zero-check with the terms T0 T3 + T1 T2 +
+               lambda T2 T3 per layer) by tests/test_oracle_fraction_sum_c.py to
+               tests/fraction_sum_model.py and both integer verifiers; the
+               lookup's multiplicities and pair (ogkr_lookup_multiplicities: a
+               sort of the table's indices and a binary search per witness entry,
+               no hash table; ogkr_lookup_pair) by tests/test_oracle_lookup_c.py
+               to tests/lookup_model.py; oracle/c/fraction_sum_selfcheck.c runs
+               all three stand-alone under ASan and UBSan
 
 Pinning status (see DESIGN.md "Oracle"):
   * termlist.py / dense.py are pinned against golden vectors produced by

@@ -652,6 +652,168 @@ int ogkr_grand_product(const ogkr_fr *table, int n, ogkr_fr *out_product, ogkr_f
     return rc;
 }
 
+/* The fractional sum argument (include/gkr_amd.h, gkr_fraction_sum*; tests/fraction_sum_model.py restates the rules) from the
+ * parts above, as ogkr_grand_product: the tree is a loop of ogkr_fr_mul / ogkr_fr_add over every level,
+ * p_k[i] = p_{k+1}[i] q_{k+1}[i + 2^k] + p_{k+1}[i + 2^k] q_{k+1}[i], q_k[i] = q_{k+1}[i] q_{k+1}[i + 2^k]; the head is
+ * (p_2, q_2) with zeta_1 = multi_hash(those 8), zeta_2 = multi_hash([zeta_1]), lambda_2 = multi_hash([zeta_2]); layer k is
+ * ogkr_sumcheck_zerocheck (the EXPLICIT form) on T0, T1 = the halves of p_{k+1}, T2, T3 = the halves of q_{k+1} with the terms
+ * T0 T3 + T1 T2 + lambda_k T2 T3; tau_k = multi_hash([a0, a1, b0, b1]), cp = a0 + tau (a1 - a0), cq = b0 + tau (b1 - b0),
+ * z^(k+1) = (tau_k, r^(k)), lambda_{k+1} = multi_hash([tau_k]).  The levels are kept in one buffer, level k at 2 (2^k - 1), p_k
+ * then q_k: the library's layout for one pair, so that level k + 1 IS the layer's four tables one after the other -- as the
+ * caller's pair (N then D) is for the last layer. */
+int ogkr_fraction_sum(const ogkr_fr *num, const ogkr_fr *den, int n, ogkr_fr *out_sums, ogkr_fr *out_head, ogkr_fr *out_coeffs,
+                      uint32_t *out_len, ogkr_fr *out_r, ogkr_fr *out_evals, ogkr_fr *out_point, ogkr_fr *out_claims, ogkr_fr *out_levels,
+                      int threads) {
+    if (n < 3 || n > 29 || !num || !den || !out_sums || !out_head || !out_coeffs || !out_len || !out_r || !out_evals || !out_point ||
+        !out_claims)
+        return -1;
+    const ogkr_fr zero = {{0, 0, 0, 0}}, one = {{1, 0, 0, 0}};
+    const int nt = set_threads(threads);
+    (void)nt;
+    const size_t size = (size_t)1 << n;
+    ogkr_fr *levels = out_levels ? out_levels : malloc(2 * (size - 1) * sizeof(ogkr_fr));
+    ogkr_fr *top = malloc(2 * size * sizeof(ogkr_fr));      /* N then D: the last layer's four tables */
+    if (!levels || !top) {
+        if (!out_levels) free(levels);
+        free(top);
+        return -2;
+    }
+    memcpy(top, num, size * sizeof(ogkr_fr));
+    memcpy(top + size, den, size * sizeof(ogkr_fr));
+    for (int k = n - 1; k >= 0; --k) {
+        const size_t h = (size_t)1 << k;
+        const ogkr_fr *up = k + 1 == n ? top : levels + 2 * (2 * h - 1), *uq = up + 2 * h;
+        ogkr_fr *p = levels + 2 * (h - 1), *q = p + h;
+#pragma omp parallel for schedule(static) num_threads(nt)
+        for (size_t i = 0; i < h; ++i) {
+            ogkr_fr x, y;
+            ogkr_fr_mul(&up[i], &uq[i + h], &x);
+            ogkr_fr_mul(&up[i + h], &uq[i], &y);
+            ogkr_fr_add(&x, &y, &p[i]);
+            ogkr_fr_mul(&uq[i], &uq[i + h], &q[i]);
+        }
+    }
+    out_sums[0] = levels[0];
+    out_sums[1] = levels[1];
+    memcpy(out_head, levels + 6, 8 * sizeof(ogkr_fr));
+    ogkr_fr z[30], lam, eq, t[4];
+    ogkr_multi_hash(out_head, 8, &zero, &z[0]);
+    ogkr_multi_hash(&z[0], 1, &zero, &z[1]);
+    ogkr_multi_hash(&z[1], 1, &zero, &lam);
+    /* cp_2, cq_2 = p_2~(z^(2)), q_2~(z^(2)): variable 1 is the most significant index bit */
+    for (int w = 0; w < 2; ++w) {
+        const ogkr_fr *v = out_head + 4 * w;
+        for (int i = 0; i < 2; ++i) {
+            ogkr_fr d;
+            ogkr_fr_sub(&v[i + 2], &v[i], &d);
+            ogkr_fr_mul(&z[0], &d, &d);
+            ogkr_fr_add(&v[i], &d, &t[i]);
+        }
+        ogkr_fr_sub(&t[1], &t[0], &t[2]);
+        ogkr_fr_mul(&z[1], &t[2], &t[2]);
+        ogkr_fr_add(&t[0], &t[2], &out_claims[w]);
+    }
+    const ogkr_sop_term terms[3] = {{2, {0, 3, 0}}, {2, {1, 2, 0}}, {2, {2, 3, 0}}};
+    int rc = 0;
+    for (int k = 2; k < n && !rc; ++k) {
+        const size_t row = (size_t)k * (size_t)(k - 1) / 2 - 1;
+        const ogkr_fr *up = k + 1 == n ? top : levels + 2 * (((size_t)2 << k) - 1);
+        const ogkr_fr cf[3] = {one, one, lam};
+        ogkr_fr *v = out_evals + 4 * (size_t)(k - 2), tau, d;
+        rc = ogkr_sumcheck_zerocheck(up, k, 4, terms, cf, 3, z, out_coeffs + 4 * row, out_len + row, out_r + row, v, &eq, threads);
+        if (rc) break;
+        ogkr_multi_hash(v, 4, &zero, &tau);
+        for (int w = 0; w < 2; ++w) {
+            ogkr_fr_sub(&v[2 * w + 1], &v[2 * w], &d);
+            ogkr_fr_mul(&tau, &d, &d);
+            ogkr_fr_add(&v[2 * w], &d, &out_claims[w]);
+        }
+        z[0] = tau;
+        memcpy(z + 1, out_r + row, (size_t)k * sizeof(ogkr_fr));
+        ogkr_multi_hash(&tau, 1, &zero, &lam);
+    }
+    if (!rc) memcpy(out_point, z, (size_t)n * sizeof(ogkr_fr));
+    if (!out_levels) free(levels);
+    free(top);
+    return rc;
+}
+
+/* The lookup argument's multiplicities and pair (include/gkr_amd.h, gkr_lookup*; tests/lookup_model.py restates the rules).
+ * Counting is by ORDER: the table's indices sorted by (value, index), a binary search per witness entry for the first index of
+ * its value.  No hash table, no slot function, no probe chain. */
+static int cmp_fr(const ogkr_fr *a, const ogkr_fr *b) {
+    for (int i = 3; i >= 0; --i)
+        if (a->l[i] != b->l[i]) return a->l[i] < b->l[i] ? -1 : 1;
+    return 0;
+}
+
+static const ogkr_fr *sort_table;
+static int cmp_index(const void *x, const void *y) {
+    const uint32_t a = *(const uint32_t *)x, b = *(const uint32_t *)y;
+    const int c = cmp_fr(&sort_table[a], &sort_table[b]);
+    return c ? c : (a < b ? -1 : a > b);
+}
+
+int ogkr_lookup_multiplicities(const ogkr_fr *witness, int n_w, const ogkr_fr *table, int n_t, ogkr_fr *out_mult, uint32_t *out_missing,
+                               uint32_t *out_first_missing) {
+    if (n_w < 0 || n_w > 30 || n_t < 0 || n_t > 30 || !witness || !table || !out_mult || !out_missing || !out_first_missing) return -1;
+    const size_t nw = (size_t)1 << n_w, nt = (size_t)1 << n_t;
+    uint32_t *order = malloc(nt * sizeof(uint32_t));
+    uint64_t *count = calloc(nt, sizeof(uint64_t));
+    if (!order || !count) {
+        free(order);
+        free(count);
+        return -2;
+    }
+    for (size_t j = 0; j < nt; ++j) order[j] = (uint32_t)j;
+    sort_table = table;       /* (one sort at a time: the callers are single-threaded tests) */
+    qsort(order, nt, sizeof(uint32_t), cmp_index);
+    uint32_t missing = 0, first = 0xFFFFFFFFu;
+    for (size_t i = 0; i < nw; ++i) {
+        size_t lo = 0, hi = nt;                    /* the first position whose value is >= W[i] */
+        while (lo < hi) {
+            const size_t mid = lo + (hi - lo) / 2;
+            if (cmp_fr(&table[order[mid]], &witness[i]) < 0) lo = mid + 1;
+            else hi = mid;
+        }
+        if (lo < nt && cmp_fr(&table[order[lo]], &witness[i]) == 0) {
+            ++count[order[lo]];                    /* equal values are in index order: this is the lowest index */
+        } else {
+            ++missing;
+            if (first == 0xFFFFFFFFu) first = (uint32_t)i;
+        }
+    }
+    for (size_t j = 0; j < nt; ++j) {
+        const ogkr_fr m = {{count[j], 0, 0, 0}};
+        out_mult[j] = m;
+    }
+    *out_missing = missing;
+    *out_first_missing = first;
+    free(order);
+    free(count);
+    return 0;
+}
+
+int ogkr_lookup_pair(const ogkr_fr *witness, int n_w, const ogkr_fr *table, int n_t, const ogkr_fr *mult, const ogkr_fr *alpha,
+                     ogkr_fr *out_pair) {
+    if (n_w < 0 || n_w > 30 || n_t < 0 || n_t > 30 || !witness || !table || !mult || !alpha || !out_pair) return -1;
+    const ogkr_fr zero = {{0, 0, 0, 0}}, one = {{1, 0, 0, 0}};
+    const size_t nw = (size_t)1 << n_w, nt = (size_t)1 << n_t, half = nw > nt ? nw : nt, size = 2 * half;
+    ogkr_fr *N = out_pair, *D = out_pair + size;
+    for (size_t i = 0; i < half; ++i) {
+        N[i] = i < nw ? one : zero;
+        D[i] = one;
+        if (i < nw) ogkr_fr_sub(alpha, &witness[i], &D[i]);
+        N[half + i] = zero;
+        D[half + i] = one;
+        if (i < nt) {
+            ogkr_fr_sub(&zero, &mult[i], &N[half + i]);
+            ogkr_fr_sub(alpha, &table[i], &D[half + i]);
+        }
+    }
+    return 0;
+}
+
 /* ------------------------------------------------------------------ R1CS tables
  * The tables of the R1CS zero-check and inner sumcheck (tests/r1cs_rows_model.py, tests/r1cs_cols_model.py and
  * verifier.r1cs_matrix_evals restate the rules) on the flat records as they stand: counts[3 i + m] records for the combination

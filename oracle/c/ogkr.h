@@ -95,6 +95,34 @@ int ogkr_sumcheck_zerocheck(const ogkr_fr *tables, int n, int n_tables, const og
 int ogkr_grand_product(const ogkr_fr *table, int n, ogkr_fr *out_product, ogkr_fr *out_head, ogkr_fr *out_coeffs, uint32_t *out_len,
                        ogkr_fr *out_r, ogkr_fr *out_evals, ogkr_fr *out_point, ogkr_fr *out_claim, ogkr_fr *out_levels, int threads);
 
+/* The fractional sum sum_i num[i] / den[i] = P / Q of 2^n pairs of canonical values as GKR on the binary tree of fractions
+ * (include/gkr_amd.h, gkr_fraction_sum*): the C twin of tests/fraction_sum_model.fraction_sum.  The tree
+ * p_k[i] = p_{k+1}[i] q_{k+1}[i + 2^k] + p_{k+1}[i + 2^k] q_{k+1}[i], q_k[i] = q_{k+1}[i] q_{k+1}[i + 2^k] is a loop of
+ * ogkr_fr_mul / ogkr_fr_add; the head is (p_2, q_2), z^(2) = (zeta_1, zeta_2) = (multi_hash(head), multi_hash([zeta_1])),
+ * lambda_2 = multi_hash([zeta_2]); layer k = 2 .. n - 1 is ogkr_sumcheck_zerocheck with the terms T0 T3 + T1 T2 + lambda_k T2 T3 on
+ * the halves of p_{k+1} (T0, T1) and q_{k+1} (T2, T3) at z^(k), then tau_k = multi_hash([a0, a1, b0, b1]),
+ * cp = a0 + tau_k (a1 - a0), cq = b0 + tau_k (b1 - b0), z^(k+1) = (tau_k, r^(k)), lambda_{k+1} = multi_hash([tau_k]).  With
+ * R = n (n - 1) / 2 - 1 and layer k's rows from k (k - 1) / 2 - 1 on: out_sums 2 (P, Q), out_head 8, out_coeffs R rows of 4 slots
+ * (right-aligned, highest degree first, unused slots zero), out_len R, out_r R, out_evals (n - 2) x 4, out_point n the point
+ * z^(n), out_claims 2 (cp_n, cq_n).  out_levels, if not NULL, takes the levels 0 .. n - 1, level k at 2 (2^k - 1), p_k then q_k
+ * (2 (2^n - 1) elements: the library's layout for one pair).  -1: n < 3, n > 29 or a NULL pointer (out_levels apart); -2: no memory. */
+int ogkr_fraction_sum(const ogkr_fr *num, const ogkr_fr *den, int n, ogkr_fr *out_sums, ogkr_fr *out_head, ogkr_fr *out_coeffs,
+                      uint32_t *out_len, ogkr_fr *out_r, ogkr_fr *out_evals, ogkr_fr *out_point, ogkr_fr *out_claims, ogkr_fr *out_levels,
+                      int threads);
+
+/* The lookup argument's inputs (include/gkr_amd.h, gkr_lookup*): the C twins of tests/lookup_model.multiplicities and .pair.
+ *   multiplicities: out_mult[j] = #{i: witness[i] = table[j]} if j is the lowest index with table's value table[j], else 0 --
+ *                   counted by sorting the table's indices by (value, index) and a binary search per witness entry (no hash
+ *                   table); *out_missing the witness entries outside the table, *out_first_missing the lowest such index or
+ *                   0xFFFFFFFF.  Not thread-safe (one sort at a time).
+ *   pair:           out_pair = N then D, 2^L each, L = max(n_w, n_t) + 1: (1, alpha - witness[i]) for i < 2^n_w, (0, 1) up to
+ *                   2^(L-1), then (-mult[j], alpha - table[j]) for j < 2^n_t, (0, 1) up to 2^L.
+ * -1: n_w or n_t outside 0 .. 30 or a NULL pointer; -2: no memory. */
+int ogkr_lookup_multiplicities(const ogkr_fr *witness, int n_w, const ogkr_fr *table, int n_t, ogkr_fr *out_mult, uint32_t *out_missing,
+                               uint32_t *out_first_missing);
+int ogkr_lookup_pair(const ogkr_fr *witness, int n_w, const ogkr_fr *table, int n_t, const ogkr_fr *mult, const ogkr_fr *alpha,
+                     ogkr_fr *out_pair);
+
 /* The tables of the R1CS zero-check and inner sumcheck on the flat form of an R1CS: counts[3 * n_constraints] (the records of A,
  * B, C per constraint), wires[] and canonical coeffs[], one record after the other -- the C twins of tests/r1cs_rows_model.rows,
  * tests/r1cs_cols_model.cols_table and verifier.r1cs_matrix_evals, as loops over the records as they stand.  A zero coefficient

@@ -227,6 +227,70 @@ def grand_product_raw(table_limbs, n, threads=0, levels=False):
     return tuple(out) + ((lv,) if levels else ())
 
 
+def fraction_sum_raw(pair_limbs, n, threads=0, levels=False):
+    """ogkr_fraction_sum on one pair, N then D ((2, 2^n, 4) or (2^(n+1), 4) limbs) -> (S (2, 4), H (8, 4), C (R, 4, 4) right-aligned,
+    L (R,) uint32, R (R, 4), E (n - 2, 4, 4), Z (n, 4), K (2, 4)) with R = n (n - 1) / 2 - 1: one proof's slice of the eight arrays
+    gkr_fraction_sum_batch_device returns.  levels=True: a ninth array (2 (2^n - 1), 4), level k of the tree at 2 (2^k - 1), p_k
+    then q_k."""
+    pair_limbs = np.ascontiguousarray(pair_limbs, dtype=np.uint64)
+    rounds = n * (n - 1) // 2 - 1 if n >= 3 else 0
+    good = 3 <= n <= 29 and pair_limbs.size == 8 << n
+    out = [np.zeros(s, dtype=np.uint64) for s in ((2, 4), (8, 4), (rounds, 4, 4))] + [np.zeros(rounds, dtype=np.uint32)]
+    out += [np.zeros(s, dtype=np.uint64) for s in ((rounds, 4), (max(n - 2, 0), 4, 4), (max(n, 0), 4), (2, 4))]
+    lv = np.zeros((2 * ((1 << n) - 1), 4), dtype=np.uint64) if levels and good else None
+    flat = pair_limbs.reshape(-1, 4)
+    fn = lib().ogkr_fraction_sum
+    fn.restype = ctypes.c_int
+    rc = fn(_p(flat) if good else None, _p(flat[1 << n:]) if good else None, ctypes.c_int(n), *[_p(a) for a in out],
+            _p(lv) if lv is not None else None, _threads(threads))
+    if rc:
+        raise ValueError("ogkr_fraction_sum rc=%d" % rc)
+    return tuple(out) + ((lv,) if levels else ())
+
+
+def _log2_exact(rows):
+    return rows.bit_length() - 1 if rows > 0 and rows & (rows - 1) == 0 else -1
+
+
+def lookup_multiplicities_raw(witness_limbs, table_limbs):
+    """ogkr_lookup_multiplicities on (2^n_w, 4) and (2^n_t, 4) limbs -> (M (2^n_t, 4), missing, first_missing)."""
+    witness_limbs = np.ascontiguousarray(witness_limbs, dtype=np.uint64).reshape(-1, 4)
+    table_limbs = np.ascontiguousarray(table_limbs, dtype=np.uint64).reshape(-1, 4)
+    M = np.zeros_like(table_limbs)
+    missing, first = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    fn = lib().ogkr_lookup_multiplicities
+    fn.restype = ctypes.c_int
+    rc = fn(_p(witness_limbs), ctypes.c_int(_log2_exact(witness_limbs.shape[0])), _p(table_limbs), ctypes.c_int(_log2_exact(table_limbs.shape[0])),
+            _p(M), ctypes.byref(missing), ctypes.byref(first))
+    if rc:
+        raise ValueError("ogkr_lookup_multiplicities rc=%d" % rc)
+    return M, int(missing.value), int(first.value)
+
+
+def lookup_pair_raw(witness_limbs, table_limbs, mult_limbs, alpha_limbs):
+    """ogkr_lookup_pair -> (2, 2^L, 4) limbs: N then D, L = max(n_w, n_t) + 1."""
+    witness_limbs = np.ascontiguousarray(witness_limbs, dtype=np.uint64).reshape(-1, 4)
+    table_limbs = np.ascontiguousarray(table_limbs, dtype=np.uint64).reshape(-1, 4)
+    mult_limbs = np.ascontiguousarray(mult_limbs, dtype=np.uint64).reshape(-1, 4)
+    alpha_limbs = np.ascontiguousarray(alpha_limbs, dtype=np.uint64).reshape(-1)
+    n_w, n_t = _log2_exact(witness_limbs.shape[0]), _log2_exact(table_limbs.shape[0])
+    if n_w < 0 or n_t < 0 or mult_limbs.shape != table_limbs.shape or alpha_limbs.shape != (4,):
+        raise ValueError("a witness and a table of a power of two entries, a multiplicity per table entry and one alpha expected")
+    out = np.zeros((2, 2 << max(n_w, n_t), 4), dtype=np.uint64)
+    fn = lib().ogkr_lookup_pair
+    fn.restype = ctypes.c_int
+    rc = fn(_p(witness_limbs), ctypes.c_int(n_w), _p(table_limbs), ctypes.c_int(n_t), _p(mult_limbs), _p(alpha_limbs), _p(out))
+    if rc:
+        raise ValueError("ogkr_lookup_pair rc=%d" % rc)
+    return out
+
+
+def lookup_raw(witness_limbs, table_limbs, mult_limbs, alpha_limbs, threads=0, levels=False):
+    """The lookup's proof: fraction_sum_raw of lookup_pair_raw, n = L."""
+    pair = lookup_pair_raw(witness_limbs, table_limbs, mult_limbs, alpha_limbs)
+    return fraction_sum_raw(pair, pair.shape[1].bit_length() - 1, threads, levels)
+
+
 def _r1cs_flat(counts, wires, coeffs):
     """The flat form of an R1CS (what gkr_r1cs_export writes): counts (3 * n_constraints,) uint32, wires (records,) uint32, coeffs
     (records, 4) uint64, checked against each other -> (n_constraints, counts, wires, coeffs)."""

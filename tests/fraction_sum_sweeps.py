@@ -14,6 +14,9 @@ to get it:
   an unused slot             never read, whatever it holds: accepted;
   a challenge + 1            the round's sum still holds, its hash does not: CHALLENGE at (k, j);
   a length -> 0 or 5         SHAPE at (k, j);
+  a length + 1 or - 1        (length_steps) + 1: beyond four SHAPE, else a leading zero joins the used slots -- same sum, same value
+                             at r_j, another hash: CHALLENGE at (k, j).  - 1: 0 is SHAPE, else the leading coefficient (non-zero: the
+                             prover drops leading zeros) leaves the sum: ROUND_SUM at (k, j);
   a0, a1, b0 or b1 + 1       eq(z^(k), r^(k)) (a0 b1 + a1 b0 + lambda_k b0 b1) moves by eq times the value's cofactor -- b1, b0,
                              a1 + lambda_k b1, a0 + lambda_k b0: FINAL_CLAIM at (k, k);
   an entry of N or D + 1     N~(z^(n)) or D~(z^(n)) moves by eq(z^(n), i): EVALUATION at (n, n);
@@ -44,15 +47,21 @@ def check_inputs(g, n, num, den):
     """The sweep's inputs have no zero cofactor: every entry of N and D non-zero, Q != 0, no q_2 entry 0 or r - 1, and per layer
     eq(z^(k), r^(k)) and the four values' cofactors non-zero; the changed table entries have non-zero weights at z^(n)."""
     assert all(x % P for x in num) and all(x % P for x in den)
+    check_cofactors(g, n)
+    assert all(_eq_weight(g["point"], i) for i in table_entries(n))
+
+
+def check_cofactors(g, n):
+    """The part of check_inputs that needs the proof alone (a pair with zero numerators, as a lookup's, can pass it)."""
     assert head_root(g["head"])[1] != 0 and all(q not in (0, P - 1) for q in g["head"][4:])
     for k, (_, _, (a0, a1, b0, b1)) in enumerate(g["layers"], start=2):
         lam = g["lambdas"][k - 2]
         assert g["eqs"][k - 2] and b1 and b0 and (a1 + lam * b1) % P and (a0 + lam * b0) % P, k
-    assert all(_eq_weight(g["point"], i) for i in table_entries(n))
 
 
-def tamperings(g, n, with_sums, with_tables):
-    """-> [(name, what, (check, layer, round))] for the proof g = fraction_sum_model.fraction_sum(N, D, n)."""
+def tamperings(g, n, with_sums, with_tables, length_steps=False):
+    """-> [(name, what, (check, layer, round))] for the proof g = fraction_sum_model.fraction_sum(N, D, n); length_steps adds a
+    length + 1 and a length - 1 per round."""
     out = []
     for t in range(8):
         out.append(("head %d + 1" % t, ("head", t, "+1"), (FRACTION_SUM, 0, 0) if with_sums else (ROUND_SUM, 2, 0)))
@@ -74,6 +83,9 @@ def tamperings(g, n, with_sums, with_tables):
             out.append(("layer %d challenge %d >= r" % (k, j), ("r", k, j, ">=r"), (NON_CANONICAL, k, j)))
             out.append(("layer %d length %d -> 0" % (k, j), ("len", k, j, 0), (SHAPE, k, j)))
             out.append(("layer %d length %d -> 5" % (k, j), ("len", k, j, 5), (SHAPE, k, j)))
+            if length_steps:
+                out.append(("layer %d length %d + 1" % (k, j), ("len", k, j, len(vec) + 1), (SHAPE if len(vec) == 4 else CHALLENGE, k, j)))
+                out.append(("layer %d length %d - 1" % (k, j), ("len", k, j, len(vec) - 1), (SHAPE if len(vec) == 1 else ROUND_SUM, k, j)))
         for w in range(4):
             out.append(("layer %d value %d + 1" % (k, w), ("eval", k, w, "+1"), (FINAL_CLAIM, k, k)))
             out.append(("layer %d value %d >= r" % (k, w), ("eval", k, w, ">=r"), (NON_CANONICAL, k, k)))
