@@ -51,7 +51,7 @@ SYMBOLS = [
     "gkr_strerror", "gkr_version", "gkr_ctx_create", "gkr_ctx_create_multi", "gkr_ctx_device_count", "gkr_ctx_destroy", "gkr_last_error",
     "gkr_ctx_set_transcript", "gkr_ctx_set_host_threads", "gkr_ctx_set_option", "gkr_ctx_get_option", "gkr_option_count", "gkr_option_name", "gkr_option_doc", "gkr_option_env", "gkr_host_help_while", "gkr_host_accounting", "gkr_host_accounting_read", "gkr_prove_many", "gkr_ctx_device_name", "gkr_ctx_profile", "gkr_ctx_profile_get", "gkr_ctx_profile_samples",
     "gkr_ctx_profile_reset", "gkr_mimc7_multi_hash", "gkr_mimc7_hash", "gkr_mimc7_constant",
-    "gkr_selftest_mul", "gkr_selftest_wide_sum", "gkr_selftest_fold", "gkr_selftest_dot", "gkr_selftest_hash8", "gkr_selftest_host_pass", "gkr_selftest_host_prod_pass", "gkr_selftest_host_tail", "gkr_selftest_pass_schedule", "gkr_selftest_product_geometry", "gkr_selftest_layer_dense_geometry", "gkr_selftest_line_restriction", "gkr_selftest_seg_item", "gkr_devtest_field", "gkr_devtest_lazy", "gkr_devtest_reduce", "gkr_devtest_lanes", "gkr_devtest_gate_plan", "gkr_devtest_predicates", "gkr_sumcheck_mle", "gkr_sumcheck_mle_batch_device",
+    "gkr_selftest_mul", "gkr_selftest_wide_sum", "gkr_selftest_fold", "gkr_selftest_dot", "gkr_selftest_hash8", "gkr_selftest_host_pass", "gkr_selftest_host_prod_pass", "gkr_selftest_host_tail", "gkr_selftest_pass_schedule", "gkr_selftest_mle_plan", "gkr_selftest_mle_plan_ctx", "gkr_selftest_product_geometry", "gkr_selftest_layer_dense_geometry", "gkr_selftest_line_restriction", "gkr_selftest_seg_item", "gkr_devtest_field", "gkr_devtest_lazy", "gkr_devtest_reduce", "gkr_devtest_lanes", "gkr_devtest_gate_plan", "gkr_devtest_predicates", "gkr_sumcheck_mle", "gkr_sumcheck_mle_batch_device",
     "gkr_sumcheck_product", "gkr_sumcheck_product_batch_device",
     "gkr_sumcheck_product_verify_batch_device", "gkr_sumcheck_product_verify",
     "gkr_sumcheck_sop_batch_device", "gkr_sumcheck_sop",
@@ -294,6 +294,11 @@ def lib():
         L.gkr_r1cs_verify.argtypes = [ctypes.c_void_p] * 13 + [ctypes.c_size_t] + [ctypes.c_void_p] * 4
         L.gkr_selftest_product_geometry.restype = ctypes.c_int
         L.gkr_selftest_product_geometry.argtypes = [ctypes.c_int] * 2 + [ctypes.c_void_p] * 2
+        # (n, batch, hash_threads, option_names, option_values, n_options, header, rows, row_capacity, n_rows); (ctx, n, batch, header, ..)
+        L.gkr_selftest_mle_plan.restype = ctypes.c_int
+        L.gkr_selftest_mle_plan.argtypes = [ctypes.c_int] * 3 + [ctypes.c_void_p] * 2 + [ctypes.c_size_t] + [ctypes.c_void_p] * 2 + [ctypes.c_size_t, ctypes.c_void_p]
+        L.gkr_selftest_mle_plan_ctx.restype = ctypes.c_int
+        L.gkr_selftest_mle_plan_ctx.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 2 + [ctypes.c_size_t, ctypes.c_void_p]
         # (ctx, k_i, k_next, gate_type, left, right, form, counts)
         L.gkr_devtest_gate_plan.restype = ctypes.c_int
         L.gkr_devtest_gate_plan.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 5

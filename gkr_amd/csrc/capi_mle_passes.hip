@@ -93,8 +93,21 @@ static int mle_pass_tables(gkr_ctx* ctx, const std::string& prefix, const Fr* in
 constexpr double kFusedPublishBytes = 64.0 * 1024 * 1024;
 constexpr uint32_t kFusedPublishBlocks = 256;   // blocks per launch: each pays one L2 write-back (~30 ns, one after the other)
 constexpr size_t kArrivalCounters = 4096;       // (one size: zeroed once per allocation, every pass leaves them zero)
+// ---- the launch plan: every decision below as a value (gkr_selftest_mle_plan reports them; include/gkr_amd.h GKR_MLE_*).  Host
+// arithmetic only: the launches call these functions and do what they say, the self-test walks them without a device.
+enum : uint32_t {
+    kMleKindSmall0 = GKR_MLE_KIND_SMALL0, kMleKindSub0 = GKR_MLE_KIND_SUB_SUMS /* + the form, 0 .. 3 */, kMleKindRollPub = GKR_MLE_KIND_ROLL_PUB,
+    kMleKindFineSums = GKR_MLE_KIND_FINE_SUMS, kMleKindFold2 = GKR_MLE_KIND_FOLD2, kMleKindFoldSmall = GKR_MLE_KIND_FOLD_SMALL,
+    kMleKindFoldMfma = GKR_MLE_KIND_FOLD_MFMA, kMleKindFoldValu = GKR_MLE_KIND_FOLD_VALU, kMleKindHostFold = GKR_MLE_KIND_HOST_FOLD
+};
+struct MleLaunchPlan {
+    uint32_t kind = 0, nblk = 1, chunk = 0;   // the kernel form, blocks per table, entries per block
+    uint32_t publisher = GKR_MLE_PUB_SELF;
+};
+// the arrival counters of passes that publish from their last block: wanted at all?
+static bool mle_wants_arrivals(size_t len) { return gkr::opt(gkr::OPT_no_fused_reduce) == 0 && (double)len * 32.0 <= kFusedPublishBytes; }
 static int mle_arrival_counters(gkr_ctx* ctx, size_t len, MlePassTables& T) {
-    if (gkr::opt(gkr::OPT_no_fused_reduce) != 0 || (double)len * 32.0 > kFusedPublishBytes) return GKR_OK;
+    if (!mle_wants_arrivals(len)) return GKR_OK;
     WS(ctx, "mlep.arrivals", uint32_t, kArrivalCounters, T.arrivals);
     if (ctx->mle_arrivals_zeroed != T.arrivals) {
         HIP_TRY(ctx, hipMemsetAsync(T.arrivals, 0, sizeof(uint32_t) * kArrivalCounters, ctx->stream));
@@ -102,14 +115,16 @@ static int mle_arrival_counters(gkr_ctx* ctx, size_t len, MlePassTables& T) {
     }
     return GKR_OK;
 }
-static bool fused_publish(const MlePassTables& T, int b0, int nb, uint32_t nblk, double bytes_read, uint32_t ticket, int jout, gkr::MlePublish& pub) {
-    if (!T.arrivals || (size_t)(b0 + nb) > kArrivalCounters || bytes_read > kFusedPublishBytes || (uint64_t)nblk * nb > kFusedPublishBlocks || nblk > 128u)
-        return false;
+static bool fused_publish_applies(bool arrivals, int b0, int nb, uint32_t nblk, double bytes_read) {
+    return arrivals && (size_t)(b0 + nb) <= kArrivalCounters && bytes_read <= kFusedPublishBytes && (uint64_t)nblk * nb <= kFusedPublishBlocks && nblk <= 128u;
+}
+static gkr::MlePublish fused_publish(const MlePassTables& T, int b0, uint32_t ticket, int jout) {
+    gkr::MlePublish pub;
     pub.rec = T.rec + b0;
     pub.arrivals = T.arrivals + b0;
     pub.ticket = ticket;
     pub.jout = (uint32_t)jout;
-    return true;
+    return pub;
 }
 
 constexpr uint32_t kMleTailLog2 = 7;   // the host tail (run_mle_batch_passes): tables of 2^7 entries and fewer
@@ -133,20 +148,38 @@ static void queue_sub_reduce(gkr_ctx* ctx, const MlePassTables& T, int b0, int n
     Timed t(ctx, "mle_sub_reduce", 0.0, st, true);
     gkr::launch_mle_sub_reduce(T.partials + (size_t)b0 * gkr::kMaxBlocksPerTable, nblk, (uint32_t)jout, nb, T.rec + b0, ticket, st);
 }
+// pass 0 of the sumchecks [b0, b0 + nb) of tables of `len` entries, as a plan: arrivals = the run has arrival counters (T.arrivals)
+static MleLaunchPlan plan_pass0(size_t len, bool arrivals, int b0, int nb, int jout, const MlePassPolicy& P) {
+    MleLaunchPlan L;
+    if (len <= gkr::kSmallPassEntries) {
+        L.kind = kMleKindSmall0;
+        L.chunk = (uint32_t)len;
+        return L;
+    }
+    L.nblk = pass0_blocks(len, jout, nb, P);
+    L.chunk = (uint32_t)(len / L.nblk);
+    const bool fused = fused_publish_applies(arrivals, b0, nb, L.nblk, (double)nb * len * 32.0);
+    const int form = gkr::mle_sub_sums_stream_form((uint32_t)len, (uint32_t)nb, L.nblk, fused);
+    const bool flagged = P.flagged && !fused && gkr::mle_sub_sums_publishes_flagged(form, L.nblk);
+    L.kind = flagged ? kMleKindRollPub : kMleKindSub0 + (uint32_t)form;
+    L.publisher = fused ? GKR_MLE_PUB_FUSED : (flagged ? GKR_MLE_PUB_FLAGGED : GKR_MLE_PUB_REDUCE);
+    return L;
+}
 // pass 0 of the sumchecks [b0, b0 + nb): the 2^jout sub-block sums of the input tables.  true: its blocks publish flag-in-word
 // records (P.flagged and a launch that takes the publishing kernel), which the host totals -- no reduce launch was queued
 static bool queue_pass0(gkr_ctx* ctx, const MlePassTables& T, int b0, int nb, int jout, uint32_t ticket, hipStream_t st, const MlePassPolicy& P) {
     const size_t len = T.in_stride;
     const Fr* src = T.input + (size_t)b0 * len;
     const double bytes = (double)nb * len * 32.0;
-    if (len <= gkr::kSmallPassEntries) {
+    const MleLaunchPlan L = plan_pass0(len, T.arrivals != nullptr, b0, nb, jout, P);
+    if (L.kind == kMleKindSmall0) {
         Timed t(ctx, "mle_pass_small", bytes, st, true);
         gkr::launch_mle_multifold_small(0, src, len, nullptr, 0, (uint32_t)len, (uint32_t)jout, nb, T.h_w + (size_t)b0 * gkr::kMleMaxSub, T.rec + b0, ticket, st);
         return false;
     }
-    const uint32_t nblk = pass0_blocks(len, jout, nb, P);
-    gkr::MlePublish pub;
-    const bool fused = fused_publish(T, b0, nb, nblk, bytes, ticket, jout, pub);
+    const uint32_t nblk = L.nblk;
+    const bool fused = L.publisher == GKR_MLE_PUB_FUSED;
+    const gkr::MlePublish pub = fused ? fused_publish(T, b0, ticket, jout) : gkr::MlePublish{};
     bool flagged;
     {
         Timed t(ctx, P.row, bytes, st, fused);
@@ -155,6 +188,21 @@ static bool queue_pass0(gkr_ctx* ctx, const MlePassTables& T, int b0, int nb, in
     }
     if (!fused && !flagged) queue_sub_reduce(ctx, T, b0, nb, nblk, jout, ticket, st);
     return flagged;
+}
+// a fold pass of tables of 2^m_src entries that binds jin variables, as a plan
+static MleLaunchPlan plan_fold(bool arrivals, int b0, int nb, int m_src, int jin, int jout) {
+    MleLaunchPlan L;
+    const size_t src_len = (size_t)1 << m_src, S = src_len >> jin;
+    if (S <= gkr::kSmallPassEntries) {
+        L.kind = kMleKindFoldSmall;
+        L.chunk = (uint32_t)S;
+        return L;
+    }
+    L.nblk = gkr::mle_multifold_blocks((uint32_t)S, (uint32_t)jout, nb);
+    L.chunk = (uint32_t)(S / L.nblk);
+    L.kind = gkr::mle_multifold_uses_mfma((uint32_t)S, L.nblk) ? kMleKindFoldMfma : kMleKindFoldValu;
+    L.publisher = fused_publish_applies(arrivals, b0, nb, L.nblk, (double)nb * (double)src_len * 32.0) ? GKR_MLE_PUB_FUSED : GKR_MLE_PUB_REDUCE;
+    return L;
 }
 // a fold pass: bind the jin variables just hashed of tables of 2^m_src entries (the input, or work), produce the sums of the next jout rounds
 static void queue_fold(gkr_ctx* ctx, const MlePassTables& T, int b0, int nb, bool from_input, int m_src, int jin, int jout, uint32_t ticket,
@@ -165,15 +213,16 @@ static void queue_fold(gkr_ctx* ctx, const MlePassTables& T, int b0, int nb, boo
     Fr* dst = T.work + (size_t)b0 * T.work_len;
     const Fr* w = T.h_w + (size_t)b0 * gkr::kMleMaxSub;
     const double bytes = (double)nb * ((double)src_len * P.src_planes + (double)S) * 32.0;
-    if (S <= gkr::kSmallPassEntries) {
+    const MleLaunchPlan L = plan_fold(T.arrivals != nullptr, b0, nb, m_src, jin, jout);
+    if (L.kind == kMleKindFoldSmall) {
         Timed t(ctx, "mle_pass_small", bytes, st, true);
         gkr::launch_mle_multifold_small(jin, src, src_stride, dst, T.work_len, (uint32_t)S, (uint32_t)jout, nb, w, T.rec + b0, ticket, st, P.export_tail,
                                         1u << kMleTailLog2, P.src_planes, (uint32_t)src_len);
         return;
     }
-    const uint32_t nblk = gkr::mle_multifold_blocks((uint32_t)S, (uint32_t)jout, nb);
+    const uint32_t nblk = L.nblk;
     unsigned char* plan = T.plans + (size_t)b0 * gkr::mle_fold_plan_bytes();
-    if (gkr::mle_multifold_uses_mfma((uint32_t)S, nblk)) {
+    if (L.kind == kMleKindFoldMfma) {
         // the digit matrices only depend on the weights the host just wrote: built on the side stream, the main stream (busy
         // with another group's pass) pays one event wait, not a launch round trip -- where the caller asks for it
         if (P.plan_event < 0) {
@@ -187,8 +236,8 @@ static void queue_fold(gkr_ctx* ctx, const MlePassTables& T, int b0, int nb, boo
             (void)hipStreamWaitEvent(st, ctx->aux_events[P.plan_event], 0);
         }
     }
-    gkr::MlePublish pub;
-    const bool fused = fused_publish(T, b0, nb, nblk, (double)nb * (double)src_len * 32.0, ticket, jout, pub);
+    const bool fused = L.publisher == GKR_MLE_PUB_FUSED;
+    const gkr::MlePublish pub = fused ? fused_publish(T, b0, ticket, jout) : gkr::MlePublish{};
     {
         Timed t(ctx, P.row, bytes, st, fused);
         gkr::launch_mle_multifold(jin, src, src_stride, dst, T.work_len, (uint32_t)S, nb, nblk, w, plan, T.partials + (size_t)b0 * gkr::kMaxBlocksPerTable, st,
@@ -278,6 +327,133 @@ static MleSchedule mle_schedule(int n, int batch, int hash_threads, bool is_tail
     // variables itself: exact field arithmetic, the same canonical sums.
     sc.tail_on = o.v[gkr::OPT_host_tail_log2] >= 0 && sc.n_dev == 0 && batch <= (o.v[gkr::OPT_host_tail_max_batch] > 0 ? o.v[gkr::OPT_host_tail_max_batch] : 8);
     return sc;
+}
+// ---- what the driver decides per pass from the schedule (host arithmetic; the driver and the launch plan both call these)
+// a group's small late passes have a stream of their own
+static bool mle_late_stream(const MleSchedule& sc) { return !gkr::opt(gkr::OPT_no_late_stream) && sc.groups > 1; }
+// the small launches beside the streaming passes (the fold's digit matrices, the fine sums, the second level's weights) go to the side stream
+static bool mle_side_launches(const MleSchedule& sc) { return !gkr::opt(gkr::OPT_plan_main) && sc.groups != 1; }
+// flag-in-word records (option stream_publish): where another group's launch waits behind a streaming pass's reduce -- several
+// host-hashed groups on the two-level schedule
+static bool mle_flag_records(const MleSchedule& sc) { return gkr::opt(gkr::OPT_stream_publish) != 1 && sc.two_level && sc.groups > 1; }
+static bool mle_group_two_level(const MleSchedule& sc, bool chain) { return sc.two_level && !chain; }
+// pass 0 of a group is offered the flag-in-word records
+static bool mle_pass0_flagged(const MleSchedule& sc, bool chain, int j) {
+    return mle_flag_records(sc) && mle_group_two_level(sc, chain) && j == gkr::kMlePassMaxRounds;
+}
+// the stream of a fold pass over tables of 2^m_src entries (GKR_MLE_STREAM_*): small source tables make a latency-bound late pass, not to
+// be queued behind other groups' streaming passes
+static uint32_t mle_fold_stream(const MleSchedule& sc, int n, bool chain, int m_src) {
+    if (chain) return GKR_MLE_STREAM_CHAIN;
+    return m_src != n && m_src <= 16 && mle_late_stream(sc) ? GKR_MLE_STREAM_LATE : GKR_MLE_STREAM_MAIN;
+}
+// its digit matrices on the side stream?  (one group: nothing else is streaming, and the event between the two streams costs the
+// round path ~10 us more than a second launch on the same stream -- 15 us against 5 between the plan and the fold)
+static bool mle_fold_plan_on_side(const MleSchedule& sc, uint32_t stream) { return stream == GKR_MLE_STREAM_MAIN && mle_side_launches(sc); }
+// the fold leaves tables of 2^m entries whose sums cover j rounds: small enough for the host to finish, and there is a pass left to save
+static bool mle_fold_exports_tail(const MleSchedule& sc, bool chain, int m, int j) {
+    return sc.tail_on && !chain && m <= (int)kMleTailLog2 && m - j > 0;
+}
+
+// ---- the launch plan of a call (gkr_selftest_mle_plan, include/gkr_amd.h): the passes of every group in the order the driver
+// (MlePassRun::step, queue_device_chain) takes them, each decided by the functions above.
+// SHARED with the launches: every value of a row -- pass0_blocks, plan_pass0, plan_fold, mle_multifold2_blocks, the stream, plan,
+// tail and record predicates, mle_pass_rounds.  RESTATED here, and so not held by the plan's tests: the ORDER of a group's passes
+// (pass 0, then fine sums and the two-level fold where the group takes them, then folds until the sums cover the last round; step,
+// launch_fine_sums, launch_fold2, host_fold, queue_device_chain), with what they carry from pass to pass (m, j, `planes` set by
+// launch_fold2 and cleared by the fold behind it, `on_host` set by launch_fold and kept by host_fold).  A change to that sequencing
+// has to be made here too; the byte comparisons of tests/test_gpu_mle_plan.py hold the driver's own.
+struct MlePlanRow {
+    uint32_t w[GKR_MLE_PLAN_ROW_WORDS];
+};
+static MlePlanRow mle_plan_row(int g, size_t pass, const MleLaunchPlan& L, int m_src, int jin, int jout, uint32_t stream, int b0, int nb) {
+    MlePlanRow r{};
+    const uint32_t v[] = {(uint32_t)g, (uint32_t)pass, L.kind, (uint32_t)m_src, (uint32_t)jin, (uint32_t)jout, L.nblk, L.chunk, L.publisher, stream};
+    memcpy(r.w, v, sizeof(v));
+    r.w[12] = 1;
+    r.w[13] = (uint32_t)b0;
+    r.w[14] = (uint32_t)nb;
+    return r;
+}
+static void mle_plan_group(const MleSchedule& sc, int n, int g, int b0, int nb, bool chain, std::vector<MlePlanRow>& rows) {
+    const size_t len = (size_t)1 << n, first = rows.size();
+    const bool arrivals = mle_wants_arrivals(len), two = mle_group_two_level(sc, chain);
+    const uint32_t own = chain ? GKR_MLE_STREAM_CHAIN : GKR_MLE_STREAM_MAIN;
+    int m = n, j = sc.j_first;
+    bool planes = false, on_host = false;
+    MlePassPolicy P0;
+    if (two) P0.blocks_jout = kMleTwoLevelRounds;
+    P0.flagged = mle_pass0_flagged(sc, chain, j);
+    rows.push_back(mle_plan_row(g, 0, plan_pass0(len, arrivals, b0, nb, j, P0), n, 0, j, own, b0, nb));
+    while (m - j > 0) {
+        const size_t pass = rows.size() - first;
+        if (m == n && two) {
+            // the fine sums and the digit matrices of rounds 1-5 (launch_fine_sums), then the fold of ten variables (launch_fold2)
+            const bool side = mle_side_launches(sc);
+            MlePassPolicy Pb;
+            Pb.blocks_jout = kMleTwoLevelRounds;
+            MleLaunchPlan F;
+            F.kind = kMleKindFineSums;
+            F.nblk = pass0_blocks(len, j, nb, Pb);
+            F.chunk = (uint32_t)(len / F.nblk);
+            rows.push_back(mle_plan_row(g, pass, F, n, j, gkr::kMlePassMaxRounds, side ? GKR_MLE_STREAM_SIDE : GKR_MLE_STREAM_MAIN, b0, nb));
+            rows.back().w[10] = side ? GKR_MLE_PLAN_SIDE_STREAM : GKR_MLE_PLAN_OWN_STREAM;
+            const uint32_t S = 1u << (n - gkr::kMlePassMaxRounds);
+            MleLaunchPlan L;
+            L.kind = kMleKindFold2;
+            L.nblk = gkr::mle_multifold2_blocks(S);
+            L.chunk = S / L.nblk;
+            L.publisher = mle_flag_records(sc) && gkr::mle_multifold2_publishes_flagged(S) ? GKR_MLE_PUB_FLAGGED : GKR_MLE_PUB_REDUCE;
+            rows.push_back(mle_plan_row(g, pass + 1, L, n, kMleTwoLevelRounds, gkr::kMlePassMaxRounds, GKR_MLE_STREAM_MAIN, b0, nb));
+            m = n - kMleTwoLevelRounds;
+            j = gkr::kMlePassMaxRounds;
+            planes = true;
+            on_host = false;
+            continue;
+        }
+        const int m_src = m, jin = j;
+        m -= jin;
+        j = mle_pass_rounds(m, n, sc.jmax);
+        if (on_host) {
+            MleLaunchPlan H;
+            H.kind = kMleKindHostFold;
+            H.chunk = 1u << m;
+            H.publisher = GKR_MLE_PUB_HOST;
+            rows.push_back(mle_plan_row(g, pass, H, m_src, jin, j, GKR_MLE_STREAM_HOST, b0, nb));
+            continue;
+        }
+        const uint32_t stream = mle_fold_stream(sc, n, chain, m_src);
+        const MleLaunchPlan L = plan_fold(arrivals, b0, nb, m_src, jin, j);
+        on_host = mle_fold_exports_tail(sc, chain, m, j);
+        rows.push_back(mle_plan_row(g, pass, L, m_src, jin, j, stream, b0, nb));
+        MlePlanRow& r = rows.back();
+        if (L.kind == kMleKindFoldMfma) r.w[10] = mle_fold_plan_on_side(sc, stream) ? GKR_MLE_PLAN_SIDE_STREAM : GKR_MLE_PLAN_OWN_STREAM;
+        r.w[11] = on_host && L.kind == kMleKindFoldSmall;   // (launch_mle_multifold_small is what takes the tail pointer)
+        r.w[12] = planes ? gkr::kMleFold2Planes : 1u;
+        planes = false;
+    }
+}
+// (the options are the calling thread's: an OptionScope around the call)
+static int mle_plan(int n, int batch, int hash_threads, uint32_t* header, uint32_t* out_rows, size_t row_capacity, size_t* n_rows) {
+    if (!header || !n_rows || (!out_rows && row_capacity) || n < 2 || n > GKR_MAX_MLE_N || batch < 1 || batch > 65535 ||
+        ((unsigned long long)batch << n) > (1ull << 30) || hash_threads < 1)
+        return GKR_ERR_INVALID;
+    const gkr::Options* o = gkr::current_options();
+    const MleSchedule sc = mle_schedule(n, batch, hash_threads, false, o ? *o : gkr::default_options());
+    std::vector<MlePlanRow> rows;
+    for (int g = 0; g < sc.groups; ++g) mle_plan_group(sc, n, g, sc.bound[g], sc.bound[g + 1] - sc.bound[g], false, rows);
+    if (sc.n_dev) mle_plan_group(sc, n, sc.groups, 0, sc.n_dev, true, rows);
+    memset(header, 0, sizeof(uint32_t) * GKR_MLE_PLAN_HEADER_WORDS);
+    const bool flags = mle_flag_records(sc) && gkr::mle_multifold2_publishes_flagged(1u << (n - gkr::kMlePassMaxRounds));
+    const uint32_t h[] = {(uint32_t)sc.jmax, (uint32_t)sc.j_first, (uint32_t)sc.n_dev, (uint32_t)sc.groups, (uint32_t)sc.depth, sc.tail_on, sc.two_level,
+                          flags ? (uint32_t)sc.groups - 1u : 0u, sc.two_level ? (flags ? 1u : (uint32_t)sc.groups) : 0u, (uint32_t)hash_threads};
+    memcpy(header, h, sizeof(h));
+    static_assert(10 + kMaxGroups + 1 + kMaxGroups <= GKR_MLE_PLAN_HEADER_WORDS, "the header holds every bound and chunk");
+    for (int g = 0; g <= sc.groups; ++g) header[10 + g] = (uint32_t)sc.bound[g];
+    for (int g = 0; g < sc.groups; ++g) header[10 + kMaxGroups + 1 + g] = sc.chunk[g];
+    *n_rows = rows.size();
+    for (size_t i = 0; i < rows.size() && i < row_capacity; ++i) memcpy(out_rows + i * GKR_MLE_PLAN_ROW_WORDS, rows[i].w, sizeof(rows[i].w));
+    return GKR_OK;
 }
 
 // ------------------------------------------------------------- the driver
@@ -398,7 +574,7 @@ struct MlePassRun {
         MlePassPolicy P;
         P.row = G.chain ? "mle_sub_sums_dev" : "mle_sub_sums";
         if (two_level(G)) P.blocks_jout = kMleTwoLevelRounds;
-        P.flagged = scan && two_level(G) && G.j == gkr::kMlePassMaxRounds;
+        P.flagged = scan && mle_pass0_flagged(sc, G.chain != nullptr, G.j);
         if (queue_pass0(ctx, T, G.b0, G.nb, G.j, G.ticket, G.chain ? G.chain : s, P)) arm_totals(G, false);
     }
     void launch_next_first() {
@@ -408,28 +584,25 @@ struct MlePassRun {
     void launch_fold(PassGroup& G, int jin) {
         const int m_src = G.m;
         const bool from_input = m_src == n;
-        // small source tables: a latency-bound late pass, not to be queued behind other groups' streaming passes
-        hipStream_t st = G.chain ? G.chain : ((!from_input && m_src <= 16) ? late : s);
+        const uint32_t where = mle_fold_stream(sc, n, G.chain != nullptr, m_src);
+        hipStream_t st = where == GKR_MLE_STREAM_CHAIN ? G.chain : (where == GKR_MLE_STREAM_LATE ? late : s);
         after_stream_pass(G, st);
         advance(G, jin);
         MlePassPolicy P;
         // late passes run beside other groups' streaming passes: their elapsed time is not their own cost, so they
         // are booked under their own name and stay out of the streaming fold pass's bandwidth figure
         P.row = G.chain ? "mle_multifold_dev" : (st == s ? "mle_multifold" : "mle_multifold_late");
-        // (one group: nothing else is streaming, and the event between the two streams costs the round path ~10 us
-        // more than a second launch on the same stream -- 15 us against 5 between the plan and the fold)
-        if (!gkr::opt(gkr::OPT_plan_main) && st == s && sc.groups != 1) P.plan_event = G.index;
-        // (the table it leaves is small enough for the host to finish, and there is a pass left to save)
-        G.on_host = sc.tail_on && !G.chain && G.m <= (int)kMleTailLog2 && G.m - G.j > 0;
+        if (mle_fold_plan_on_side(sc, where)) P.plan_event = G.index;
+        G.on_host = mle_fold_exports_tail(sc, G.chain != nullptr, G.m, G.j);
         if (G.on_host) P.export_tail = T.h_tail + ((size_t)G.b0 << kMleTailLog2);
         if (G.planes) P.src_planes = gkr::kMleFold2Planes;
         G.planes = false;
         queue_fold(ctx, T, G.b0, G.nb, from_input, m_src, jin, G.j, G.ticket, st, P);
     }
     // ---- the two-level first fold of a host-hashed group (kernels.hip, capi_internal.h mle_two_level_first_fold)
-    bool two_level(const PassGroup& G) const { return sc.two_level && !G.chain; }
+    bool two_level(const PassGroup& G) const { return mle_group_two_level(sc, G.chain != nullptr); }
     // the small launches beside the streaming passes: on the side stream, as the fold's digit matrices are (launch_fold)
-    bool side_launches() const { return !gkr::opt(gkr::OPT_plan_main) && sc.groups != 1; }
+    bool side_launches() const { return mle_side_launches(sc); }
     // rounds 1-5 are hashed: the digit matrices of their weights, and the sums of rounds 6-10 from pass 0's partials, which
     // stay as they are until the record of these sums has landed (the fold writes its own only after that)
     void launch_fine_sums(PassGroup& G) {
@@ -692,16 +865,15 @@ int run_mle_batch_passes(gkr_ctx* ctx, const Fr* d_tables, int n, int batch, gkr
         HIP_TRY(ctx, ctx->pinned_host("mlep.w2", sizeof(Fr) * gkr::kMleMaxSub * batch, reinterpret_cast<void**>(&R.T.h_w2)));
         WS(ctx, "mlep.d_w2", Fr, (size_t)batch * gkr::kMleMaxSub, R.T.d_w2);
     }
-    // Flag-in-word records (option stream_publish): where another group's launch waits behind a streaming pass's reduce -- several
-    // host-hashed groups on the two-level schedule -- the pass's blocks publish their sums themselves and the hashing threads total them
-    if (gkr::opt(gkr::OPT_stream_publish) != 1 && sc.two_level && sc.groups > 1) {
+    // Flag-in-word records (mle_flag_records): the pass's blocks publish their sums themselves and the hashing threads total them
+    if (mle_flag_records(sc)) {
         HIP_TRY(ctx, ctx->pinned_host("mlep.flag", sizeof(uint64_t) * gkr::kFlagRecWords * gkr::kFlagRecsPerTable * batch, reinterpret_cast<void**>(&R.T.h_flag)));
         R.scan.reset(new FlagScan[batch]);
     }
     HIP_TRY(ctx, ctx->aux_stream(sc.groups));
     if (R.scan) HIP_TRY(ctx, ctx->stream_end_events(sc.groups));
     if (sc.tail_on) HIP_TRY(ctx, ctx->pinned_host("mlep.tail", sizeof(Fr) * ((size_t)batch << kMleTailLog2), reinterpret_cast<void**>(&R.T.h_tail)));
-    if (!gkr::opt(gkr::OPT_no_late_stream) && sc.groups > 1) HIP_TRY(ctx, ctx->late_stream(&R.late));
+    if (mle_late_stream(sc)) HIP_TRY(ctx, ctx->late_stream(&R.late));
     R.dep_last = std::vector<uint32_t>(batch, 0);
     R.grp = std::vector<PassGroup>(sc.groups);
     for (int g = 0; g < sc.groups; ++g) {
@@ -835,6 +1007,31 @@ struct MleShardRun {
 }  // namespace gkr_host
 
 extern "C" {
+
+// ---- the launch plan of the multi-round driver, without a device (mle_plan above)
+int gkr_selftest_mle_plan(int n, int batch, int hash_threads, const char* const* option_names, const long long* option_values, size_t n_options,
+                          uint32_t* header, uint32_t* rows, size_t row_capacity, size_t* n_rows) {
+    if ((n_options && (!option_names || !option_values)) || hash_threads > 256) return GKR_ERR_INVALID;
+    gkr::Options o;
+    for (int i = 0; i < gkr::OPT_COUNT; ++i) o.v[i] = gkr::option_table()[i].def;
+    for (size_t i = 0; i < n_options; ++i) {
+        const int at = gkr::option_index(option_names[i]);
+        if (at < 0) return GKR_ERR_INVALID;
+        o.v[at] = option_values[i];
+    }
+    gkr::OptionScope scope(&o);
+    return mle_plan(n, batch, hash_threads, header, rows, row_capacity, n_rows);
+}
+
+int gkr_selftest_mle_plan_ctx(gkr_ctx* ctx, int n, int batch, uint32_t* header, uint32_t* rows, size_t row_capacity, size_t* n_rows) {
+    if (!ctx) return GKR_ERR_INVALID;
+    if (ctx->transcript != GKR_TRANSCRIPT_HOST || ctx->options.v[gkr::OPT_mle_per_round])
+        return ctx->fail(GKR_ERR_INVALID, "the launch plan is the multi-round driver's: host transcript, option mle_per_round off");
+    gkr::OptionScope scope(&ctx->options);
+    // (the threads the driver would hash with: its pool's workers and the driving thread)
+    const int rc = mle_plan(n, batch, (int)ctx->host_pool()->workers() + 1, header, rows, row_capacity, n_rows);
+    return rc ? ctx->fail(rc, "gkr_selftest_mle_plan_ctx: NULL pointer or a shape gkr_sumcheck_mle_batch_device refuses") : GKR_OK;
+}
 
 // ---- one plain sumcheck split over ranks, on the multi-round schedule -----------------------------------------------
 // prove_sumcheck (sumcheck.rs:158-214) with the reduce over the hypercube (the rayon reduce of :62) split over P = 2^lp

@@ -130,6 +130,11 @@ constexpr int kMlePass0Stream = 3;   // what option pass0_stream = 0 means: 1 k_
 // wave: 2 partials x 12 resident waves x 256 CUs x 4 generations.  Reasoned, not tuned: only 128 tables x 1024 partials was measured
 // (profiles/r22); what smaller launches take is a guess that keeps their block count at the chip's size or above
 constexpr uint64_t kMlePass0DeepMinPartials = 2u * 12u * 256u * 4u;
+// Host arithmetic only (the launch and the launch plan, capi_mle_passes.hip, both call them): the form launch_mle_sub_sums gives a launch
+// -- 0 k_mle_sub_sums, 1 k_mle_sub_sums_stream<8, 1>, 2 k_mle_sub_sums_stream<16, 2>, 3 k_mle_sub_sums_roll -- and whether a launch of that
+// form that is offered flag-in-word records publishes there (k_mle_sub_sums_roll_pub)
+int mle_sub_sums_stream_form(uint32_t len, uint32_t batch, uint32_t nblk, bool publishes);
+bool mle_sub_sums_publishes_flagged(int form, uint32_t nblk);
 // Every pass: per-block partial sums, then a reduce kernel that writes the pinned host record.
 // flagged != nullptr (pinned: batch x kFlagRecsPerTable flag-in-word records, flagged_rec.h): the rolling form with kFlagRecsPerTable
 // blocks per table publishes its blocks' sums there under flag_ticket and returns true -- the host totals them, no reduce launch
@@ -157,8 +162,11 @@ void launch_mle_multifold_small(int jin, const Fr* src, size_t src_stride, Fr* d
 // launch_mle_copy_weights) and leaves eight partial planes of S / 32 entries and mle_multifold2_partials(S) partials per table.
 constexpr uint32_t kMleFold2Planes = 8;
 uint32_t mle_multifold2_partials(uint32_t S);
+// host arithmetic only: a launch_mle_multifold2 that is offered flag-in-word records publishes there
+bool mle_multifold2_publishes_flagged(uint32_t S);
 // tiles of 64 entries a block of the fold takes: one, or what option fold2_tiles forces
 uint32_t mle_multifold2_tiles(uint32_t S);
+uint32_t mle_multifold2_blocks(uint32_t S);   // the launch's blocks per table: (S / 256) / tiles
 void launch_mle_fine_sums(const MleSubPartial* partials, uint32_t nblk, const Fr* weights, uint32_t batch, MleHostRecSub* host_rec, uint32_t ticket,
                           hipStream_t s);
 void launch_mle_copy_weights(const Fr* src, Fr* dst, uint32_t batch, hipStream_t s);

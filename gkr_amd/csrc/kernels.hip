@@ -3035,7 +3035,7 @@ uint32_t mle_pass_blocks(uint32_t items, uint32_t jout, uint32_t batch) {
 // partial per wave, blocks of four waves, every XCD on its own eighth of the launch -- the variant that won in the step
 // (profiles/r25; <16, 2> in blocks of two waves was level with it and stretched the side stream's kernels).  The other launches are
 // what option 2 makes them.
-static int mle_sub_sums_stream_form(uint32_t len, uint32_t batch, uint32_t nblk, bool publishes) {
+int mle_sub_sums_stream_form(uint32_t len, uint32_t batch, uint32_t nblk, bool publishes) {
     const long long o = opt(OPT_pass0_stream);
     const long long want = o >= 1 && o <= 3 ? o : kMlePass0Stream;
     if (want < 2 || publishes || nblk == 0 || len % nblk != 0) return 0;
@@ -3043,6 +3043,7 @@ static int mle_sub_sums_stream_form(uint32_t len, uint32_t batch, uint32_t nblk,
     if (chunk % 512u == 0 && nblk % 8u == 0 && (uint64_t)batch * nblk >= kMlePass0DeepMinPartials) return want == 3 ? 3 : 2;
     return chunk % 256u == 0 && nblk % 4u == 0 ? 1 : 0;
 }
+bool mle_sub_sums_publishes_flagged(int form, uint32_t nblk) { return form == 3 && nblk == 4u * kFlagRecsPerTable; }
 
 // flagged (may be null; pinned, batch x kFlagRecsPerTable records): where the launch takes the rolling form with kFlagRecsPerTable
 // blocks per table, its blocks publish there under flag_ticket and the return value is true -- NO reduce launch is to follow.  Every
@@ -3050,7 +3051,7 @@ static int mle_sub_sums_stream_form(uint32_t len, uint32_t batch, uint32_t nblk,
 bool launch_mle_sub_sums(const Fr* tables, size_t stride, uint32_t len, uint32_t batch, uint32_t nblk, MleSubPartial* partials,
                          hipStream_t s, const MlePublish* publish, uint64_t* flagged, uint32_t flag_ticket) {
     const int form = mle_sub_sums_stream_form(len, batch, nblk, publish != nullptr);
-    if (form == 3 && flagged && nblk == 4u * kFlagRecsPerTable) {
+    if (flagged && mle_sub_sums_publishes_flagged(form, nblk)) {
         hipLaunchKernelGGL((k_mle_sub_sums_roll_pub<16, true>), dim3(nblk / 4u, batch), dim3(256), 0, s, tables, stride, len / nblk, nblk, partials, flagged,
                            flag_ticket);
         return true;
@@ -3163,6 +3164,9 @@ uint32_t mle_multifold2_partials(uint32_t S) {
     const uint32_t I = S >> kMfmaMaxJ, sub = I >> 5;
     return 8u * (I / (sub < 64u ? sub : 64u));
 }
+bool mle_multifold2_publishes_flagged(uint32_t S) {
+    return mle_multifold2_partials(S) == kFlagRecsPerTable && (S >> (2 * kMfmaMaxJ)) >= 16u;   // (g = min(I / 32, 64))
+}
 
 void launch_mle_fine_sums(const MleSubPartial* partials, uint32_t nblk, const Fr* weights, uint32_t batch, MleHostRecSub* host_rec, uint32_t ticket,
                           hipStream_t s) {
@@ -3187,6 +3191,10 @@ uint32_t mle_multifold2_tiles(uint32_t S) {
     return T;
 }
 
+// blocks per table of the two-level first fold, each of mle_multifold2_tiles(S) tiles of 256 outputs (host arithmetic: the launch and the
+// launch plan both call it)
+uint32_t mle_multifold2_blocks(uint32_t S) { return (S >> 8) / mle_multifold2_tiles(S); }
+
 // S = 2^(n-5) with 2^13 <= S <= 2^19; dst: eight planes of S / 32 entries per table; w2: device memory
 // flagged / flag_ticket / return value: as launch_mle_sub_sums' (here for launches of kFlagRecsPerTable partials per table, each of at
 // least sixteen entries: 2^19 <= table <= 2^21).  `ended` (may be null; with a publishing launch): an event the kernel's own completion
@@ -3195,13 +3203,13 @@ uint32_t mle_multifold2_tiles(uint32_t S) {
 bool launch_mle_multifold2(const Fr* src, size_t src_stride, Fr* dst, size_t dst_stride, uint32_t S, uint32_t batch, const void* plans, const Fr* w2,
                            MleSubPartial* partials, hipStream_t s, uint64_t* flagged, uint32_t flag_ticket, hipEvent_t ended) {
     const uint32_t T = mle_multifold2_tiles(S);
-    const bool pub = flagged && mle_multifold2_partials(S) == kFlagRecsPerTable && (S >> (2 * kMfmaMaxJ)) >= 16u;   // (g = min(I / 32, 64))
+    const bool pub = flagged && mle_multifold2_publishes_flagged(S);
     const MfmaFoldPlan* pl = static_cast<const MfmaFoldPlan*>(plans);
     if (pub)
-        hipExtLaunchKernelGGL(k_mle_multifold2_mfma<true>, dim3((S >> 8) / T, batch), dim3(256), 0, s, nullptr, ended, 0, src, src_stride, dst, dst_stride, S, pl,
+        hipExtLaunchKernelGGL(k_mle_multifold2_mfma<true>, dim3(mle_multifold2_blocks(S), batch), dim3(256), 0, s, nullptr, ended, 0, src, src_stride, dst, dst_stride, S, pl,
                               w2, partials, T, flagged, flag_ticket);
     else
-        hipLaunchKernelGGL(k_mle_multifold2_mfma<false>, dim3((S >> 8) / T, batch), dim3(256), 0, s, src, src_stride, dst, dst_stride, S, pl, w2, partials, T,
+        hipLaunchKernelGGL(k_mle_multifold2_mfma<false>, dim3(mle_multifold2_blocks(S), batch), dim3(256), 0, s, src, src_stride, dst, dst_stride, S, pl, w2, partials, T,
                            (uint64_t*)nullptr, 0u);
     return pub;
 }

@@ -209,6 +209,39 @@ int  gkr_selftest_dot(const gkr_fr *a, const gkr_fr *b, size_t n, gkr_fr *out);
  * fold's (up to 5 rounds per pass), 0 the v_mad_u64_u32 fold's (up to 3), 2 the matrix-core fold's with the first fold at
  * two levels where it applies (18 <= n <= 24: 10 | 5 | ..., option first_fold_levels = 2).  *passes = number of passes. */
 int  gkr_selftest_pass_schedule(int n, int mfma, uint32_t *rounds, size_t capacity, size_t *passes);
+/* The launch plan of gkr_sumcheck_mle_batch_device(n, batch) on the host transcript's multi-round schedule (host logic, from the
+ * functions the driver and its launches call; no device work): which kernel reads which table, with how many blocks, on which stream.
+ * gkr_selftest_mle_plan: for `hash_threads` hashing threads (the driving one included) and the option table's defaults with
+ * option_values[i] laid over option_names[i], i < n_options -- no context, no environment.  gkr_selftest_mle_plan_ctx: for the
+ * context's options and thread count.
+ * header: GKR_MLE_PLAN_HEADER_WORDS words: 0 jmax, 1 j_first, 2 n_dev (sumchecks hashed on the device), 3 groups, 4 depth, 5 tail_on,
+ * 6 two_level, 7 / 8 the two-level first folds that publish flag-in-word records / through a reduce launch (groups - 1 and 1 where
+ * the records are in use: the fold launched LAST keeps the reduce, whichever group's it is), 9 hash_threads, 10 .. 42 bound[0 .. 32],
+ * 43 .. 74 chunk[0 .. 31] (unused entries 0).
+ * rows: GKR_MLE_PLAN_ROW_WORDS words per pass, group by group (the device-hashed chain last, as group `groups`), passes in order:
+ * 0 group, 1 pass, 2 kind (GKR_MLE_KIND_*), 3 m_src (log2 entries of the tables read), 4 jin (variables bound; the fine sums: the
+ * rounds whose weights they take), 5 jout (rounds the sums cover), 6 blocks per table (the fine sums: partials per table they total),
+ * 7 entries per block, 8 publisher (GKR_MLE_PUB_*; a two-level fold: FLAGGED where header word 7 counts it), 9 stream
+ * (GKR_MLE_STREAM_*), 10 the fold's digit matrices (GKR_MLE_PLAN_*; with the fine sums: theirs and the two-level fold's), 11 the fold
+ * leaves its tables to the host tail, 12 planes its source is the sum of, 13 / 14 the group's first sumcheck / its sumchecks, 15 zero.
+ * What depends on the order in which hashes land (which fold is launched last, event waits between streams) is not reported.
+ * *n_rows = rows of the plan; rows beyond row_capacity are not written (rows may be NULL with row_capacity 0).
+ * GKR_ERR_INVALID: NULL header or n_rows, n outside 2 .. GKR_MAX_MLE_N, batch outside 1 .. 65535, batch * 2^n above 2^30,
+ * hash_threads outside 1 .. 256, an unknown option name; the context's form also: a context on the device transcript or with option
+ * mle_per_round (another driver runs those). */
+enum {
+    GKR_MLE_KIND_SMALL0 = 0, GKR_MLE_KIND_SUB_SUMS = 1 /* + form: 1 k_mle_sub_sums, 2 stream<8,1>, 3 stream<16,2>, 4 roll */,
+    GKR_MLE_KIND_ROLL_PUB = 5, GKR_MLE_KIND_FINE_SUMS = 6, GKR_MLE_KIND_FOLD2 = 7, GKR_MLE_KIND_FOLD_SMALL = 8, GKR_MLE_KIND_FOLD_MFMA = 9,
+    GKR_MLE_KIND_FOLD_VALU = 10, GKR_MLE_KIND_HOST_FOLD = 11
+};
+enum { GKR_MLE_PUB_SELF = 0, GKR_MLE_PUB_FUSED = 1, GKR_MLE_PUB_REDUCE = 2, GKR_MLE_PUB_FLAGGED = 3, GKR_MLE_PUB_HOST = 4 };
+enum { GKR_MLE_STREAM_MAIN = 0, GKR_MLE_STREAM_LATE = 1, GKR_MLE_STREAM_SIDE = 2, GKR_MLE_STREAM_CHAIN = 3, GKR_MLE_STREAM_HOST = 4 };
+enum { GKR_MLE_PLAN_NONE = 0, GKR_MLE_PLAN_OWN_STREAM = 1, GKR_MLE_PLAN_SIDE_STREAM = 2 };
+#define GKR_MLE_PLAN_HEADER_WORDS 80
+#define GKR_MLE_PLAN_ROW_WORDS 16
+int  gkr_selftest_mle_plan(int n, int batch, int hash_threads, const char *const *option_names, const long long *option_values,
+                           size_t n_options, uint32_t *header, uint32_t *rows, size_t row_capacity, size_t *n_rows);
+int  gkr_selftest_mle_plan_ctx(gkr_ctx *ctx, int n, int batch, uint32_t *header, uint32_t *rows, size_t row_capacity, size_t *n_rows);
 /* the launch geometry of gkr_sumcheck_product_batch_device (host logic, the process-default options; the degree does not enter):
  * nblk[j] = blocks per sumcheck of round j's pass (j = 0 .. n-1; round 0 the value pass, later rounds the fold-and-value pass),
  * chunk[j] = the entries a block walks, as the kernels derive it: ((items + nblk - 1) / nblk + 255) & ~255 with items = 2^(n-1-j).

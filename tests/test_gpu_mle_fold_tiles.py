@@ -1,6 +1,7 @@
 """The two-level first fold as a loop over tiles with a rolling load buffer (csrc/kernels.hip k_mle_multifold2_mfma,
 csrc/mfma_fold.h), one tile per block by default, more with option fold2_tiles.  No value of it changes a byte: (C, L, R) is
-compared with the C oracle (cdense.sumcheck_mle_raw) and with the run at one tile per block."""
+compared with the C oracle (cdense.sumcheck_mle_raw) and with the run at one tile per block.  Every run first asserts the tiles per block
+it means to reach on the context's plan (tests/mle_plan.py pin: the library's own launch plan against tests/mle_shapes.py)."""
 
 import ctypes
 import functools
@@ -11,6 +12,8 @@ import sys
 import numpy as np
 import pytest
 
+import mle_plan as mp
+import mle_shapes as ms
 from gkr_amd import Context
 from oracle import cdense
 from oracle.field import P
@@ -50,6 +53,9 @@ def _filled_batch(ctx, n, batch, tiles):
     d = ctx.alloc(batch * count * 32)
     ctx.set_option("fold2_tiles", tiles)
     try:
+        # the fold's row: the largest power of two of tiles that is at most what was asked and at most 2^(n-16), one for 0
+        T = 1 << (max(min(tiles, 1 << (n - 16)), 1).bit_length() - 1)
+        mp.pin(ctx, n, batch, row=2, kind=ms.FOLD2, chunk=256 * T, nblk=(1 << (n - 13)) // T, jin=10)
         for b in range(batch):
             ctx.fill_table(ctypes.c_void_p(d.value + b * count * 32), count, _seed(n, b))
         return ctx.sumcheck_mle_batch_device(d, n, batch)
@@ -97,6 +103,7 @@ def test_extreme_bytes_and_length_rule_at_four_tiles(ctx):
               "all_ff": np.repeat(ff, count, axis=0), "no_x_n": base[idx >> 1], "one_entry": one_entry}
     ctx.set_option("fold2_tiles", 4)
     try:
+        mp.pin(ctx, n, 1, row=2, kind=ms.FOLD2, chunk=1024, nblk=8)
         for name, t in tables.items():
             t = np.ascontiguousarray(t)
             assert _same(ctx.sumcheck_mle_raw(t, n), cdense.sumcheck_mle_raw(t, n)), name
@@ -126,6 +133,8 @@ def test_twenty_calls_give_the_same_bytes(ctx):
     d = ctx.alloc(batch * count * 32)
     ctx.set_option("group_size", 2)
     try:
+        assert mp.context_plan(ctx, n, batch)[0][10:15] == [0, 1, 3, 5, 7]   # (four groups: 1 + 2 + 2 + 2 by the bounds' rounding)
+        mp.pin(ctx, n, batch, group=1, row=2, kind=ms.FOLD2, chunk=256, nblk=32, nb=2)
         for b in range(batch):
             ctx.fill_table(ctypes.c_void_p(d.value + b * count * 32), count, _seed(n, b))
         before = ctx.download(d, (batch * count, 4))

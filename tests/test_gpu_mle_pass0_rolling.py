@@ -5,7 +5,8 @@ as it has been added, and with the blocks that share an XCD on one contiguous ei
 partial per wave in blocks of four waves; it takes the launches the two-set <16, 2> takes with option 2: at least 24 576 partials
 of whole 512 entries (kernels.h kMlePass0DeepMinPartials); every other launch keeps what option 2 gives it.  The partials are the
 same integers, so every case is checked byte for byte against the C oracle (cdense.sumcheck_mle_raw), or against pass0_stream = 1
-where the oracle would take too long."""
+where the oracle would take too long.  A case that names the launch it means to reach first asserts it on the context's plan
+(tests/mle_plan.py pin: the library's own launch plan against tests/mle_shapes.py)."""
 
 import ctypes
 import functools
@@ -16,6 +17,8 @@ import sys
 import numpy as np
 import pytest
 
+import mle_plan as mp
+import mle_shapes as ms
 from gkr_amd import Context
 from oracle import cdense
 from oracle.field import P
@@ -107,9 +110,11 @@ def test_deep_launch_matches_oracle(ctx, n):
         special[at] = np.ascontiguousarray(t)
         at += 1
     assert at <= batch
+    assert mp.context_plan(ctx, n, batch)[0][3] == 2   # (the default schedule: two groups)
     ctx.set_option("group_size", batch)
     d = ctx.alloc(batch * count * 32)
     try:
+        mp.pin(ctx, n, batch, kind=ms.ROLL, nblk=1024, chunk=chunk, nb=batch, publisher=ms.PUB_REDUCE)
         for b, seed in enumerate(seeds):
             where = ctypes.c_void_p(d.value + b * count * 32)
             if b in special:
@@ -132,10 +137,14 @@ def test_launcher_conditions_same_bytes_with_every_option(ctx, n, batch):
     """Launches that publish from their last block, chunks of 256 entries in few blocks, launches below the rolling kernel's
     threshold: the same bytes with options 1, 2 and 3, whichever kernel each launch takes, and the oracle's."""
     seeds = [25500 + 31 * n + b for b in range(batch)]
+    fused = n == 13 or (batch == 1 and n <= 15)   # (32 blocks per table at n = 13; 64 and 128 blocks of a lone table)
+    form = {"kind": ms.SUB_SUMS if fused else ms.STREAM_8_1, "chunk": 256, "publisher": ms.PUB_FUSED if fused else ms.PUB_REDUCE}
+    mp.pin(ctx, n, batch, **form)   # (below the rolling kernel's threshold: what option 2 gives the launch)
     got = _batch_of_seeds(ctx, n, seeds)
     try:
         for other in (1, 2):
             ctx.set_option("pass0_stream", other)
+            mp.pin(ctx, n, batch, **(form if other == 2 else dict(form, kind=ms.SUB_SUMS)))
             assert _same(got, _batch_of_seeds(ctx, n, seeds)), other
     finally:
         ctx.set_option("pass0_stream", 3)
@@ -144,9 +153,11 @@ def test_launcher_conditions_same_bytes_with_every_option(ctx, n, batch):
 
 
 def test_one_large_table_same_bytes_with_either_kernel(ctx):
-    """n = 24: 2048 partials of 8192 entries."""
+    """n = 24: 2048 partials of 8192 entries -- below the rolling kernel's 24 576 partials: the shallow pipelined form against
+    k_mle_sub_sums, as the plan says."""
     n = 24
     count = 1 << n
+    mp.pin(ctx, n, 1, kind=ms.STREAM_8_1, nblk=2048, chunk=8192)
     d = ctx.alloc(count * 32)
     try:
         ctx.fill_table(d, count, 25000 + n)
@@ -183,6 +194,7 @@ def test_twenty_calls_same_bytes_and_inputs_untouched(ctx, batch):
     ctx.set_option("group_size", batch)
     d = ctx.alloc(batch * count * 32)
     try:
+        mp.pin(ctx, n, batch, kind=ms.ROLL if batch == 24 else ms.STREAM_8_1, nblk=1024, chunk=512, nb=batch)
         for b, seed in enumerate(seeds):
             ctx.fill_table(ctypes.c_void_p(d.value + b * count * 32), count, seed)
         before = ctx.download(d, (batch * count, 4))
@@ -216,6 +228,7 @@ def test_block_count_no_multiple_of_eight(ctx):
             ctx.set_option("pass0_stream", option)
             ctx.set_option("rounds_per_pass", 3)
             ctx.set_option("group_size", batch)
+            mp.pin(ctx, n, batch, kind=ms.ROLL if option == 3 else ms.SUB_SUMS, nblk=16, chunk=1024, nb=batch, jout=3)
             got[option] = ctx.sumcheck_mle_batch_device(d, n, batch)
     finally:
         ctx.free(d)

@@ -3,7 +3,8 @@ one or two partials, 16-byte pieces per lane, half-entry sums joined once per pa
 Streaming launches take it (nothing published from the last block, chunks of whole 256 entries, whole blocks of waves) -- eight
 loads per lane and a partial per wave, or sixteen and two where the launch has at least 24 576 partials of whole 512 entries;
 every other launch keeps k_mle_sub_sums.  The partials are the same integers, so every case is checked byte for byte against the C oracle
-(cdense.sumcheck_mle_raw), or against pass0_stream = 1 where the oracle would take too long."""
+(cdense.sumcheck_mle_raw), or against pass0_stream = 1 where the oracle would take too long.  A case that names the launch it means to
+reach first asserts it on the context's plan (tests/mle_plan.py pin: the library's own launch plan against tests/mle_shapes.py)."""
 
 import ctypes
 import functools
@@ -14,6 +15,8 @@ import sys
 import numpy as np
 import pytest
 
+import mle_plan as mp
+import mle_shapes as ms
 from gkr_amd import Context
 from oracle import cdense
 from oracle.field import P
@@ -60,10 +63,16 @@ def _batch_of_seeds(ctx, n, seeds):
 @pytest.mark.parametrize("n,batch", [(18, 1), (18, 3), (19, 3), (20, 1), (20, 3)])
 def test_sizes_match_oracle(ctx, n, batch, levels):
     """Chunks of 256, 512 and 1024 entries ahead of the two-level first fold (one, two and four rounds of eight loads per
-    partial; n = 18 is the smallest case of the kernel); first_fold_levels = 1 gives pass 0 another number of blocks."""
+    partial; n = 18 is the smallest case of the kernel; a lone 2^20 fills the chip with 2048 blocks of 512).  first_fold_levels = 1
+    gives the passes BEHIND pass 0 another form; pass 0 itself has the same blocks at these sizes, as the plan shows (few tables: the
+    chip's 2048 blocks decide, not the sub-blocks) -- eight tables of 2^18, where one level takes 256 blocks and two take 1024, are
+    tests/test_gpu_mle_plan.py's cases one-level-256-blocks-n18-b8 and two-level-1024-blocks-n18-b8."""
     seeds = [22000 + 97 * n + b for b in range(batch)]
+    chunk = {(18, 1): 256, (18, 3): 256, (19, 3): 512, (20, 1): 512, (20, 3): 1024}[(n, batch)]
     ctx.set_option("first_fold_levels", levels)
     try:
+        rows = mp.pin(ctx, n, batch, kind=ms.STREAM_8_1, nblk=(1 << n) // chunk, chunk=chunk, publisher=ms.PUB_REDUCE)
+        assert rows[1]["kind"] == (ms.FINE_SUMS if levels == 2 else ms.FOLD_MFMA)
         C, L, R = _batch_of_seeds(ctx, n, seeds)
     finally:
         ctx.set_option("first_fold_levels", 0)
@@ -95,9 +104,11 @@ def test_launches_of_many_partials_match_oracle(ctx, n):
     lone = np.zeros((count, 4), dtype=np.uint64)
     lone[274 * chunk:275 * chunk] = base[274 * chunk:275 * chunk]
     special[7] = lone
+    assert mp.context_plan(ctx, n, batch)[0][3] == 2   # (the default schedule: two groups)
     ctx.set_option("group_size", batch)
     d = ctx.alloc(batch * count * 32)
     try:
+        mp.pin(ctx, n, batch, kind=ms.STREAM_16_2, nblk=1024, chunk=chunk, nb=batch, publisher=ms.PUB_REDUCE)
         for b, seed in enumerate(seeds):
             at = ctypes.c_void_p(d.value + b * count * 32)
             if b in special:
@@ -120,9 +131,12 @@ def test_small_tables_same_bytes_with_either_kernel(ctx, n, batch):
     """Around the launcher's conditions (launches that publish from their last block, chunks of 256 entries in few blocks): the
     same bytes with options 1 and 2, whichever kernel each launch takes, and the oracle's."""
     seeds = [22500 + 31 * n + b for b in range(batch)]
+    fused = n == 13 or (batch == 1 and n <= 15)   # (32 blocks per table at n = 13; 64 and 128 blocks of a lone table)
+    mp.pin(ctx, n, batch, kind=ms.SUB_SUMS if fused else ms.STREAM_8_1, chunk=256, publisher=ms.PUB_FUSED if fused else ms.PUB_REDUCE)
     got = _batch_of_seeds(ctx, n, seeds)
     ctx.set_option("pass0_stream", 1)
     try:
+        mp.pin(ctx, n, batch, kind=ms.SUB_SUMS, chunk=256)
         want = _batch_of_seeds(ctx, n, seeds)
     finally:
         ctx.set_option("pass0_stream", 2)
@@ -135,12 +149,15 @@ def test_small_tables_same_bytes_with_either_kernel(ctx, n, batch):
 def test_large_tables_same_bytes_with_either_kernel(ctx, n):
     """n = 24: 2048 partials of 8192 entries (32 rounds of loads each); n = 25: the one-level schedule's pass 0."""
     count = 1 << n
+    rows = mp.pin(ctx, n, 1, kind=ms.STREAM_8_1, nblk=2048, chunk=count // 2048)
+    assert (rows[1]["kind"] == ms.FINE_SUMS) == (n == 24)
     d = ctx.alloc(count * 32)
     try:
         ctx.fill_table(d, count, 22000 + n)
         got = ctx.sumcheck_mle_batch_device(d, n, 1)
         ctx.set_option("pass0_stream", 1)
         try:
+            mp.pin(ctx, n, 1, kind=ms.SUB_SUMS, nblk=2048)
             want = ctx.sumcheck_mle_batch_device(d, n, 1)
         finally:
             ctx.set_option("pass0_stream", 2)
@@ -208,6 +225,7 @@ def test_twenty_calls_same_bytes_and_inputs_untouched(ctx):
     """The partial slots are shared call after call; the kernel only reads the tables."""
     n, seeds = 18, [22950, 22951]
     count = 1 << n
+    mp.pin(ctx, n, len(seeds), kind=ms.STREAM_8_1, nblk=1024, chunk=256)
     d = ctx.alloc(len(seeds) * count * 32)
     try:
         for b, seed in enumerate(seeds):

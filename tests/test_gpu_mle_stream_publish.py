@@ -8,7 +8,8 @@ batch 50 with group_size 24 (three groups of 16 / 17 / 17: pass 0 below the roll
 publish -- both forms in one call); n = 18, batch 48 (pass 0 takes the <8, 1> form and keeps its reduce, and so does the fold, whose
 partials are shorter than a record).  Which kernels ran is read from the context's profile rows (launches of k_mle_sub_reduce).
 Tables 0 - 3 of every batch: all zero (valid records that carry zero data), r - 1 everywhere (the carry limbs), constant in x_n, and
-constant in x_n but for the last pair (dep from exactly one block)."""
+constant in x_n but for the last pair (dep from exactly one block).  Every call first asserts the context's launch plan against the model
+(tests/mle_plan.py, tests/mle_shapes.py); the reduce launches the profile counts are held against the plan's as well."""
 
 import ctypes
 import functools
@@ -16,6 +17,8 @@ import functools
 import numpy as np
 import pytest
 
+import mle_plan as mp
+import mle_shapes as ms
 from gkr_amd import Context
 from oracle import cdense
 from oracle.field import P
@@ -83,14 +86,29 @@ def pools(ctx):
         ctx.free(d)
 
 
-def _run(ctx, d, n, batch, **options):
+def _planned_reduces(ctx, n, batch):
+    """k_mle_sub_reduce launches the context's plan (asserted against the model) holds for the call: a row per pass that publishes
+    through one, and the one two-level fold that keeps its reduce where the others publish records."""
+    header, rows = mp.context_plan(ctx, n, batch)
+    mp.assert_plan(ctx, n, batch)
+    return sum(r[8] == ms.PUB_REDUCE for r in rows) + (1 if header[7] else 0)
+
+
+def _run_planned(ctx, d, n, batch, **options):
+    """(outputs, the k_mle_sub_reduce launches the plan holds for the call, group 1's rows -- or group 0's of a one-group call)."""
     for k, v in options.items():
         ctx.set_option(k, v)
     try:
-        return ctx.sumcheck_mle_batch_device(d, n, batch)
+        planned = _planned_reduces(ctx, n, batch)
+        rows = mp.assert_plan(ctx, n, batch, group=1) or mp.assert_plan(ctx, n, batch, group=0)
+        return ctx.sumcheck_mle_batch_device(d, n, batch), planned, rows
     finally:
         for k in options:
             ctx.set_option(k, 0)
+
+
+def _run(ctx, d, n, batch, **options):
+    return _run_planned(ctx, d, n, batch, **options)[0]
 
 
 def _check(got, n, batch, what):
@@ -105,12 +123,18 @@ def test_length_rule_of_the_special_tables():
 
 
 def _reduce_launches(ctx, d, n, batch, **options):
-    """(outputs, launches of k_mle_sub_reduce in the call) -- from the context's profile rows, every kernel timed."""
+    """(outputs, launches of k_mle_sub_reduce in the call) -- from the context's profile rows, every kernel timed; held to the plan's
+    count and, if `kinds` = (pass 0's kind, the two-level fold's publisher) is given, to those of the context's plan rows."""
+    kinds = options.pop("kinds", None)
     ctx.profile(1)
     try:
         ctx.profile_reset()
-        out = _run(ctx, d, n, batch, **options)
-        return out, ctx.profile_get("mle_sub_reduce")["launches"]
+        out, planned, rows = _run_planned(ctx, d, n, batch, **options)
+        launches = ctx.profile_get("mle_sub_reduce")["launches"]
+        assert launches == planned, (launches, planned)
+        if kinds:
+            assert (rows[0]["kind"], rows[2]["kind"], rows[2]["publisher"]) == (kinds[0], ms.FOLD2, kinds[1]), (n, batch, options)
+        return out, launches
     finally:
         ctx.profile(0)
         ctx.profile_reset()
@@ -127,8 +151,11 @@ REDUCES = {19: (1, 4), 20: (4, 6), 18: (4, 4)}
 @pytest.mark.parametrize("depth", [1, 3])
 @pytest.mark.parametrize("n,batch", [(19, 48), (20, 50), (18, 48)])
 def test_published_records_match_reduce_kernel_and_oracle(ctx, pools, n, batch, depth):
-    new, new_reduces = _reduce_launches(ctx, pools[n], n, batch, stream_publish=2, group_size=24, pass_queue_depth=depth)
-    old, old_reduces = _reduce_launches(ctx, pools[n], n, batch, stream_publish=1, group_size=24, pass_queue_depth=depth)
+    # (what the docstring names, on the context's plan rows: pass 0's kind and the fold's publisher of the second group)
+    new_kinds = {19: (ms.ROLL_PUB, ms.PUB_FLAGGED), 20: (ms.STREAM_8_1, ms.PUB_FLAGGED), 18: (ms.STREAM_8_1, ms.PUB_REDUCE)}[n]
+    old_kinds = {19: (ms.ROLL, ms.PUB_REDUCE), 20: (ms.STREAM_8_1, ms.PUB_REDUCE), 18: (ms.STREAM_8_1, ms.PUB_REDUCE)}[n]
+    new, new_reduces = _reduce_launches(ctx, pools[n], n, batch, stream_publish=2, group_size=24, pass_queue_depth=depth, kinds=new_kinds)
+    old, old_reduces = _reduce_launches(ctx, pools[n], n, batch, stream_publish=1, group_size=24, pass_queue_depth=depth, kinds=old_kinds)
     assert (new_reduces, old_reduces) == REDUCES[n], "the publishing kernels were not the ones that ran"
     assert _same(new, old), "stream_publish 2 differs from 1"
     _check(new, n, batch, "stream_publish 2")

@@ -2,7 +2,8 @@
 variables bound in the table's second read, rounds 6-10 hashed from sums the device forms out of pass 0's partials, the
 folded table left in eight partial planes for the one-block pass behind it.  Host-hashed sumchecks of 2^18 .. 2^24 points take
 it; everything is checked byte for byte against the C oracle (cdense.sumcheck_mle_raw), or against the one-level schedule
-where the oracle would take too long."""
+where the oracle would take too long.  A case that names the launches it means to reach first asserts them on the context's plan
+(tests/mle_plan.py pin: the library's own launch plan against tests/mle_shapes.py)."""
 
 import ctypes
 import os
@@ -12,12 +13,15 @@ import sys
 import numpy as np
 import pytest
 
+import mle_plan as mp
+import mle_shapes as ms
 from gkr_amd import Context
 from oracle import cdense
 from oracle.field import P
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
+TWO_LEVEL = [ms.STREAM_8_1, ms.FINE_SUMS, ms.FOLD2, ms.FOLD_SMALL]   # (pass 0, the fine sums, the fold of ten variables, the pass that reads its planes)
 
 
 @pytest.fixture(scope="module")
@@ -74,6 +78,8 @@ def test_random_tables_match_oracle(ctx, n, batch):
     """n = 18 is the smallest size on the new path (pass 0 with 1024 one-iteration blocks, sub-blocks of 8 entries behind the fold),
     19 has sub-blocks of 16, 20 is the headline's (half-wave sub-blocks)."""
     count = 1 << n
+    rows = mp.pin(ctx, n, batch, row=3, kinds=TWO_LEVEL, src_planes=8, chunk=1 << (n - 15), m_src=n - 10)
+    assert rows[0]["nblk"] % 1024 == 0 and (n != 18 or (rows[0]["nblk"], rows[0]["chunk"]) == (1024, 256))
     d = ctx.alloc(batch * count * 32)
     try:
         for b in range(batch):
@@ -89,6 +95,7 @@ def test_random_tables_match_oracle(ctx, n, batch):
 def test_below_the_new_path_matches_oracle(ctx):
     """n = 17: the one-level schedule, whatever the option says."""
     n = 17
+    assert ms.FOLD2 not in [r["kind"] for r in mp.pin(ctx, n, 1, row=1, kind=ms.FOLD_MFMA, m_src=17, jin=5)]
     table = cdense.fill_table(1 << n, 21717)
     assert _same(ctx.sumcheck_mle_raw(table, n), cdense.sumcheck_mle_raw(table, n))
 
@@ -98,12 +105,17 @@ def test_boundary_sizes_match_the_one_level_schedule(ctx, n):
     """n = 24 is the last size on the new path (2^14-entry planes, 2048 partials per table, a one-block pass of 512 outputs behind
     the fold), n = 25 the first above it: identical (C, L, R) bytes with first_fold_levels = 1."""
     count = 1 << n
+    if n == 24:
+        mp.pin(ctx, n, 1, row=3, kinds=TWO_LEVEL + [ms.FOLD_SMALL], src_planes=8, chunk=512, m_src=14)
+    else:
+        mp.pin(ctx, n, 1, row=1, kind=ms.FOLD_MFMA, m_src=25, jin=5)
     d = ctx.alloc(count * 32)
     try:
         ctx.fill_table(d, count, 21000 + n)
         got = ctx.sumcheck_mle_batch_device(d, n, 1)
         ctx.set_option("first_fold_levels", 1)
         try:
+            mp.pin(ctx, n, 1, row=1, kind=ms.FOLD_MFMA, m_src=n, jin=5)
             want = ctx.sumcheck_mle_batch_device(d, n, 1)
         finally:
             ctx.set_option("first_fold_levels", 2)
@@ -172,6 +184,7 @@ def test_fifty_calls_give_the_same_bytes(ctx):
     """Tickets, and the partial slots that pass 0, the fine sums and the fold share, call after call."""
     n, batch = 18, 2
     count = 1 << n
+    mp.pin(ctx, n, batch, kinds=TWO_LEVEL, nblk=1024, chunk=256)
     d = ctx.alloc(batch * count * 32)
     try:
         for b in range(batch):

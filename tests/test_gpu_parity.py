@@ -14,6 +14,8 @@ from gkr_amd import Context, GKRCircuit, GkrError, Layer
 from gkr_amd import _native as N
 from oracle import cdense, dense
 from oracle.field import P
+import mle_plan as mp
+import mle_shapes as ms
 from helpers import ints, layers_of, right_aligned_equal, terms_as_set
 
 pytestmark = pytest.mark.gpu
@@ -150,11 +152,26 @@ def test_fold_pass_variants_match_oracle(env):
         assert out.returncode == 0 and "OK" in out.stdout, out.stdout + out.stderr
 
 
+# (n, batch) -> groups, rounds per pass and kinds of the first group's passes on the host transcript (tests/mle_shapes.py)
+_S0, _B0, _ST, _FS, _F2, _F1, _FM, _HF = ms.SMALL0, ms.SUB_SUMS, ms.STREAM_8_1, ms.FINE_SUMS, ms.FOLD2, ms.FOLD_SMALL, ms.FOLD_MFMA, ms.HOST_FOLD
+PASS_SCHEDULES = {(6, 40): (2, [5, 1], [_S0, _F1]), (9, 33): (2, [5, 4], [_S0, _F1]), (10, 17): (2, [5, 5], [_B0, _F1]),
+                  (11, 9): (1, [5, 5, 1], [_B0, _F1, _F1]), (12, 130): (4, [5, 5, 2], [_B0, _F1, _F1]),
+                  (15, 7): (1, [3, 5, 5, 2], [_ST, _FM, _F1, _HF]), (17, 5): (1, [5, 5, 5, 2], [_ST, _FM, _F1, _HF]),
+                  (18, 3): (1, [5, 5, 5, 3], [_ST, _FS, _F2, _F1]), (19, 2): (1, [5, 5, 5, 4], [_ST, _FS, _F2, _F1]),
+                  (21, 1): (1, [5, 5, 5, 5, 1], [_ST, _FS, _F2, _F1, _HF])}
+
+
 @pytest.mark.parametrize("n,batch", [(6, 40), (9, 33), (10, 17), (11, 9), (12, 130), (15, 7), (17, 5), (18, 3), (19, 2), (21, 1)])
 def test_mle_every_pass_schedule_matches_oracle(ctx, n, batch):
     """Table sizes on both sides of every switch in the pass schedule (one-block passes up to 2^9 entries, fold
-    passes that stop at 2^12, 3/4/5 rounds per pass, one to four groups per batch), ragged batch sizes."""
+    passes that stop at 2^12, 3/4/5 rounds per pass, one to four groups per batch), ragged batch sizes.  On the host transcript
+    the context's launch plan is asserted first: the groups, the rounds of every pass, the kernel forms (PASS_SCHEDULES)."""
     count = 1 << n
+    if ctx._mode == "host":
+        groups, rounds, kinds = PASS_SCHEDULES[(n, batch)]
+        rows = mp.assert_plan(ctx, n, batch, kinds=kinds)
+        assert mp.context_plan(ctx, n, batch)[0][3] == groups and [r["jout"] for r in rows] == rounds
+        assert [r["kind"] for r in rows if r["m_src"] - r["jin"] == 12 and r["kind"] == _FM] == ([_FM] if n in (15, 17) else [])
     d = ctx.alloc(batch * count * 32)
     try:
         for b in range(batch):
